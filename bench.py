@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — model-evals/s per opt_setting()+pdf_update() cycle, fp64 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5] [--dump-outputs DIR] [--full]
 
 One "step" is one measurement cycle of the hot path on synthetic data:
 ``x = obe.opt_setting()`` (full settings x particles utility sweep, argmax) followed by
@@ -12,7 +12,10 @@ With N > 1 (launched by torch.distributed.run, one process per GPU) the settings
 is sharded — configs[3] — and the per-rank maxima are combined with one RCCL
 all-gather; total work is fixed, so ``scaling`` is "strong".
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and reports them (the contract
+fields and the ``config`` block); ``--dump-outputs DIR`` then also writes what the last timed step computed as
+``DIR/<name>.npy`` (float64): the setting ``opt_setting()`` returned, the utility of every setting behind it, and
+the particles and weights ``pdf_update()`` left.  With ``--full`` the line also carries
   roofline      — the dominant kernel (K1 sweep): achieved FP64 TFLOP/s from HIP events
                   around the kernel on its launch stream, against the FP64 vector peak;
                   the algorithmic HBM figure the north_star asks for rides along, and
@@ -26,7 +29,7 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   cpu_baseline_allcores — the plain C + OpenMP restatement on every host core (full-sweep configs).
   published_workload — the loop behind the only timing the reference publishes for this path (200 settings x
                   30 draws, 50 000 particles: 4.37 ms per cycle, hardware unstated), through this package.
-  other_configs — (default c3 run, N = 1) the cycle loops of c1, c2 and c5 after the timed region, each with its
+  other_configs — (c3 run, N = 1) the cycle loops of c1, c2 and c5 after the timed region, each with its
                   own bounded CPU leg.
   rccl          — (N > 1, or --force-dist) what the communicator itself reports: its world size, an all-gather of
                   the rank ids, the measured arg-max combine (in the timed cycles and on an idle stream),
@@ -602,6 +605,32 @@ def other_config(cfg, steps, warmup):
     return out
 
 
+def dump_outputs(obe, directory, setting, rank, budget_bytes=64 << 20):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files — the setting opt_setting()
+    returned, the utility of every setting that chose it, and the particle cloud and weights pdf_update() left.  A
+    cloud larger than the budget is written as a fixed, seeded sample of its particles (the same columns in every run
+    of the same arguments).  The utility is gathered on every rank of a sharded run; rank 0 writes."""
+    n_local = obe._s_end - obe._s_begin
+    utility = obe._gather_settings(obe._utility_dev[:n_local].reshape(1, -1))[0]
+    if rank != 0:
+        return
+    particles = np.asarray(obe.particles, dtype=np.float64)
+    weights = np.asarray(obe.particle_weights, dtype=np.float64)
+    outputs = {"setting": np.asarray(setting, dtype=np.float64).reshape(-1),
+               "utility": np.asarray(utility, dtype=np.float64).reshape(-1)}
+    room = budget_bytes - sum(a.nbytes for a in outputs.values())
+    n_p, per_particle = weights.size, 8 * (particles.shape[0] + 1)
+    if n_p * per_particle > room:
+        keep = room // (per_particle + 8)                 # (+ 8: the index of every kept particle)
+        cols = np.sort(np.random.default_rng(0).choice(n_p, size=keep, replace=False))
+        outputs["particle_index"] = cols.astype(np.float64)
+        particles, weights = particles[:, cols], weights[cols]
+    outputs["particles"], outputs["particle_weights"] = particles, weights
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(arr))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -610,10 +639,17 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the c1 / c2 / c5 cycles that follow the timed region of the default (c3) run")
+                    help="skip the c1 / c2 / c5 cycles that follow the timed region of a --full c3 run")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group even with one rank (exercises the N > 1 code path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline and update-kernel figures, the rccl block "
+                         "(N > 1 / --force-dist), the other configs and the CPU baselines; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around this process: be the launcher (nothing here has touched the GPU yet)
@@ -685,8 +721,11 @@ def main():
     truth_fn = obe.model_function          # the DeviceModel's NumPy form, as the demos' simulators use it
     noise_rec = model == "lorentzian"
 
+    last_setting = [None]
+
     def one_step(boundary=False):
         x = obe.opt_setting()
+        last_setting[0] = x
         y = float(truth_fn(x, true, cons)) + sigma * sim.standard_normal()
         rec = (x, y, sigma) if noise_rec else (x, y)
         if boundary:        # last cycle before the clock starts / stops: no sweep enqueued across the boundary
@@ -716,7 +755,7 @@ def main():
     # cycle is 1.3-2 ms and carries a second pair of events around the arg-max all-gather — ~25 us per cycle, 1-2 %
     # that the one-GPU line does not pay and that would come off the scaling ratio —, so the timed steps run
     # uninstrumented and K1 / the combine are measured in further cycles of the same experiment right after them.
-    instrument_in_timed_steps = not use_dist
+    instrument_in_timed_steps = args.full and not use_dist
     if instrument_in_timed_steps:
         obe._mlib.call("obe_sweep_timing", 1, None, None)
     t0 = time.perf_counter()
@@ -730,6 +769,43 @@ def main():
         resamples += r
     barrier()
     elapsed = time.perf_counter() - t0
+    elapsed_local = elapsed
+    if use_dist:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(obe, args.dump_outputs, last_setting[0], rank)
+
+    n_draws = obe.N_DRAWS if obe.utility_method == "variance_approx" else n_p
+    evals_per_step = ns * n_draws + n_p
+    value = args.steps * evals_per_step / elapsed
+    n_local = obe._s_end - obe._s_begin
+    out = {"metric": "model-evals/sec (settings x particles) per opt_setting+update cycle, fp64",
+           "value": value, "unit": "model-evals/s", "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+           "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": f"{cfg}: {desc}", "n_settings": ns, "n_particles": n_p,
+                      "utility": ("variance_full (every particle a draw, weighted variance)"
+                                  if obe.utility_method == "variance_full" else
+                                  f"variance_approx (N_DRAWS = {obe.N_DRAWS} weighted draws, reference semantics)"),
+                      "settings_per_rank": n_local, "sharding": f"settings axis / {world}",
+                      "resamples_in_timed_steps": resamples,
+                      "clock_warm_up_ms_before_the_warmup_steps": warmed_ms,
+                      "ms_per_step_min_median_max": [float(np.min(step_ms)), float(np.median(step_ms)), float(np.max(step_ms))],
+                      "median_ms_plain_cycle": (float(np.median([m for m, r in zip(step_ms, step_resampled) if not r]))
+                                                if resamples < args.steps else None),
+                      "median_ms_resample_cycle": (float(np.median([m for m, r in zip(step_ms, step_resampled) if r]))
+                                                   if resamples else None),
+                      "cpu_affinity_of_the_gpu_part": affinity}}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below is measured after the timed steps, in runs of its own ----
     k1_cycles = args.steps
     if not instrument_in_timed_steps:
         k1_cycles = max(4, min(args.steps, 12))
@@ -742,20 +818,12 @@ def main():
     obe._mlib.call("obe_sweep_timing", 0, ctypes.byref(k1_total_ms), ctypes.byref(k1_launches))
     rccl = None
     if use_dist:
-        elapsed_local = elapsed
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
         rccl = collective_report(obe, shard, backend, world, rank, ns, args.steps, elapsed_local,
                                  k1_total_ms.value, k1_launches.value, k1_cycles, affinity)
 
-    n_draws = obe.N_DRAWS if obe.utility_method == "variance_approx" else n_p
-    evals_per_step = ns * n_draws + n_p
-    value = args.steps * evals_per_step / elapsed
 
     # ---- roofline of the dominant kernel (K1), HIP events on the launch stream ----
     lib = _lib.load()
-    n_local = obe._s_end - obe._s_begin
     mom = obe._moments_on_device()
     p, w = obe._pw_tensors()
     ms = ctypes.c_float(0.0)
@@ -888,23 +956,7 @@ def main():
                                                   "instead of launch-bound"}
 
     full_sweep_mode = obe.utility_method == "variance_full"
-    out = {"metric": "model-evals/sec (settings x particles) per opt_setting+update cycle, fp64",
-           "value": value, "unit": "model-evals/s", "n_gpus": world, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-           "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": f"{cfg}: {desc}", "n_settings": ns, "n_particles": n_p,
-                      "utility": ("variance_full (every particle a draw, weighted variance)"
-                                  if obe.utility_method == "variance_full" else
-                                  f"variance_approx (N_DRAWS = {obe.N_DRAWS} weighted draws, reference semantics)"),
-                      "settings_per_rank": n_local, "sharding": f"settings axis / {world}",
-                      "resamples_in_timed_steps": resamples,
-                      "clock_warm_up_ms_before_the_warmup_steps": warmed_ms,
-                      "ms_per_step_min_median_max": [float(np.min(step_ms)), float(np.median(step_ms)), float(np.max(step_ms))],
-                      "median_ms_plain_cycle": (float(np.median([m for m, r in zip(step_ms, step_resampled) if not r]))
-                                                if resamples < args.steps else None),
-                      "median_ms_resample_cycle": (float(np.median([m for m, r in zip(step_ms, step_resampled) if r]))
-                                                   if resamples else None)},
-           "roofline": roofline, "roofline_update": roofline_update}
+    out["roofline"], out["roofline_update"] = roofline, roofline_update
     if rccl is not None:
         out["rccl"] = rccl
         if world > 1:
@@ -932,7 +984,6 @@ def main():
             except Exception as exc:
                 others[name] = {"error": str(exc)[:200]}
         out["other_configs"] = others
-    out["config"]["cpu_affinity_of_the_gpu_part"] = affinity
     if all_cpus is not None and affinity.get("pinned"):
         try:
             os.sched_setaffinity(0, all_cpus)          # the CPU legs below use every core of the host

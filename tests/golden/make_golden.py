@@ -564,10 +564,58 @@ def sweeper_cases():
               f"{int(np.sum(out['n_resamples']))} resamples, {os.path.getsize(path) / 1024:.0f} KiB")
 
 
+def demo_model_functions():
+    """The reference's own model functions — every definition with the three arguments (sets, pars, cons) or
+    (settings, parameters, constants) in its demos/ and tests/ — evaluated on the seeded inputs of
+    tests/_demo_models.py, with whose own models of the same experiments tests/test_reference_demo_models.py
+    compares them.  Only the definitions (and the module-level helpers they call) are executed, never the
+    scripts; only the outputs are stored."""
+    import ast
+    import glob
+    import importlib.util
+    import tempfile
+    import textwrap
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import _demo_models
+    tree_root = os.path.dirname(os.path.dirname(os.path.abspath(ref.__file__)))
+    found = {}
+    for path in sorted(glob.glob(os.path.join(tree_root, "demos", "**", "*.py"), recursive=True)
+                       + glob.glob(os.path.join(tree_root, "tests", "*.py"))):
+        text = open(path).read()
+        try:
+            tree = ast.parse(text)
+        except SyntaxError:
+            continue
+        helpers = [n for n in tree.body if isinstance(n, ast.FunctionDef) and not n.decorator_list
+                   and len(n.args.args) != 3 and not n.args.defaults]
+        for node in ast.walk(tree):
+            if isinstance(node, ast.FunctionDef) and not node.decorator_list \
+                    and [a.arg for a in node.args.args] in (["sets", "pars", "cons"],
+                                                            ["settings", "parameters", "constants"]):
+                body = textwrap.dedent(ast.get_source_segment(text, node))
+                used = "\n\n\n".join(ast.get_source_segment(text, h) for h in helpers if h.name + "(" in body)
+                found[f"{os.path.relpath(path, tree_root)}:{node.lineno}"] = (node.name, used + "\n\n\n" + body)
+    table = _demo_models.demo_models()
+    assert sorted(found) == sorted(table), (sorted(found), sorted(table))
+    out = {"keys": np.array(sorted(found))}
+    with tempfile.TemporaryDirectory() as tmp:
+        for k, key in enumerate(sorted(found)):
+            name, src = found[key]
+            mod_path = os.path.join(tmp, f"extracted_{k}.py")
+            with open(mod_path, "w") as f:
+                f.write("import numpy as np\n\n\n" + src + "\n")
+            spec = importlib.util.spec_from_file_location(f"extracted_{k}", mod_path)
+            mod = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(mod)
+            out[f"out_{k}"] = np.asarray(getattr(mod, name)(*_demo_models.demo_inputs(key)), dtype=np.float64)
+    np.savez_compressed(os.path.join(HERE, "demo_model_functions.npz"), **out)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["trajectories", "yspace", "units", "full_sweep", "sweeper"]
     steps = dict(trajectories=trajectories, yspace=yspace_utilities, units=unit_cases,
                  full_sweep=full_sweep_cases, sweeper=sweeper_cases, demo_size=demo_size,
-                 integer_weights=full_sweep_integer_weights, state10=state_reset_10_parameters)
+                 integer_weights=full_sweep_integer_weights, state10=state_reset_10_parameters,
+                 demo_models=demo_model_functions)
     for w in which:
         steps[w]()

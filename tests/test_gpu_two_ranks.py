@@ -15,6 +15,9 @@ import torch.multiprocessing as mp
 
 pytestmark = pytest.mark.gpu
 
+#: the shared MI355X machines the suite runs on end a run in which more than this many processes hold a GPU open
+GPU_PROCESS_CAP = 6
+
 
 def _free_port():
     s = socket.socket()
@@ -234,18 +237,28 @@ def test_unseeded_sharded_objects_stay_one_experiment(hip):
 @pytest.mark.parametrize("world", [2, 8])
 def test_bench_starts_its_own_ranks(hip, world):
     """`python bench.py --gpus N` with no launcher around it (the shape of the driver's command), N = 2 and N = 8
-    (the driver's largest run): the ranks share this box's one GPU over gloo (the numbers of such a run mean
-    nothing), one JSON line, exit code 0.  Eight fresh interpreters at once also exercise what eight real ranks do
-    to the shared files — the library / plugin build locks — and the launcher's bookkeeping of its children."""
+    (the driver's largest run), over gloo: one GPU per rank where the box has N, else the ranks share its first GPU
+    (the numbers of such a run mean nothing); one JSON line, exit code 0.  Eight fresh interpreters at once also
+    exercise what eight real ranks do to the shared files — the library / plugin build locks — and the launcher's
+    bookkeeping of its children.  Ranks that share a GPU count against GPU_PROCESS_CAP: N = 8 needs 8 GPUs."""
     import json
     import subprocess
     import sys
+    n_gpus = torch.cuda.device_count()
+    # this pytest process holds the GPU; under the delivery audit (OBE_CHECK_DELIVERY) its parent pytest does too
+    holders = 2 if os.environ.get("OBE_CHECK_DELIVERY") else 1
+    if n_gpus < world and world + holders > GPU_PROCESS_CAP:
+        pytest.skip(f"needs {world} GPUs, found {n_gpus}: {world} ranks on one GPU next to the {holders} pytest "
+                    f"process(es) holding it exceed the {GPU_PROCESS_CAP} processes a shared GPU may be opened by")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env.update(OBE_BENCH_BACKEND="gloo", OBE_BENCH_ONE_DEVICE="1")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT",
+                                                             "OBE_BENCH_ONE_DEVICE")}
+    env["OBE_BENCH_BACKEND"] = "gloo"
+    if n_gpus < world:
+        env["OBE_BENCH_ONE_DEVICE"] = "1"
     steps = 4 if world == 2 else 3
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--config", "c2", "--steps",
-                        str(steps), "--warmup", "2"], env=env, capture_output=True, text=True, timeout=900)
+                        str(steps), "--warmup", "2", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -299,7 +312,7 @@ def test_bench_line_of_a_one_rank_rccl_world_carries_the_rccl_block(hip):
                                                              "OBE_BENCH_BACKEND", "OBE_BENCH_ONE_DEVICE")}
     env["MASTER_PORT"] = str(_free_port())
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--config", "c2", "--steps", "4",
-                        "--warmup", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "2", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]

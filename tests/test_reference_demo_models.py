@@ -1,62 +1,40 @@
-"""The model functions of the reference's own demos and tests, taken from its source tree where
-that is mounted (the build container; skipped elsewhere): which of them models.from_function
-can put on the device.  Only the function definitions are extracted (nothing of the demo
-scripts runs) into a temporary module; the translation is then checked against the function
-itself, bit for bit."""
-import ast
-import glob
-import importlib.util
+"""The experiments of the reference's own demos and tests, as model functions: which of them models.from_function
+can put on the device.  tests/_demo_models.py holds this project's model of each (the reference's code is not in this
+repository); each is first held to what the reference's own function returns on the same seeded inputs
+(golden/demo_model_functions.npz, made by golden/make_golden.py from the reference's source tree), to rounding, and
+the translation is then checked against the function itself, bit for bit."""
 import os
-import textwrap
 
-import pytest
+import numpy as np
 
-REFERENCE = "/root/reference"
+import _demo_models
 
-
-def model_function_sources():
-    out = []
-    for path in sorted(glob.glob(os.path.join(REFERENCE, "demos", "**", "*.py"), recursive=True)
-                       + glob.glob(os.path.join(REFERENCE, "tests", "*.py"))):
-        text = open(path).read()
-        try:
-            tree = ast.parse(text)
-        except SyntaxError:
-            continue
-        # module-level helper functions a model function may call (only definitions are taken)
-        candidates = [n for n in tree.body if isinstance(n, ast.FunctionDef) and not n.decorator_list
-                      and len(n.args.args) != 3 and not n.args.defaults]
-        for node in ast.walk(tree):
-            if isinstance(node, ast.FunctionDef) and len(node.args.args) == 3 and not node.decorator_list \
-                    and [a.arg for a in node.args.args] in (["sets", "pars", "cons"],
-                                                            ["settings", "parameters", "constants"]):
-                body = textwrap.dedent(ast.get_source_segment(text, node))
-                helpers = "\n\n\n".join(ast.get_source_segment(text, h) for h in candidates if h.name + "(" in body)
-                out.append((os.path.relpath(path, REFERENCE), node.lineno, node.name, helpers + "\n\n\n" + body))
-    return out
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "demo_model_functions.npz")
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference tree is only mounted in the build container")
-def test_reference_demo_model_functions_translate(tmp_path):
+def test_reference_demo_model_functions_translate():
     from optbayesexpt_amd import _exprmodel, _fnmodel
+    golden = np.load(GOLDEN)
+    table = _demo_models.demo_models()
+    keys = [str(k) for k in golden["keys"]]
+    assert sorted(keys) == sorted(table)                  # a model here for every model function of the reference
     verdicts = {}
-    for k, (rel, line, name, src) in enumerate(model_function_sources()):
-        mod_path = tmp_path / f"extracted_{k}.py"
-        mod_path.write_text("import numpy as np\n\n\n" + src + "\n")
-        spec = importlib.util.spec_from_file_location(f"extracted_{k}", mod_path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)                       # defines the one function, runs nothing else
-        fn = getattr(mod, name)
+    for k, key in enumerate(keys):
+        fn = table[key][0]
+        # the model computes what the reference's own function computed, to rounding
+        ref = golden[f"out_{k}"]
+        np.testing.assert_allclose(np.asarray(fn(*_demo_models.demo_inputs(key)), dtype=np.float64), ref,
+                                   rtol=1e-12, atol=1e-13 * np.abs(ref).max(), err_msg=key)
         try:
             exprs, s, p, c = _fnmodel.expressions_from_function(fn)
             _, numpy_form, _ = _exprmodel.translate(exprs, s, p, c)
             _fnmodel.check_against_function(fn, numpy_form, len(s), len(p), len(c))
-            verdicts[f"{rel}:{line}"] = "device"
+            verdicts[key] = "device"
         except ValueError as exc:
-            verdicts[f"{rel}:{line}"] = f"host ({exc})"
+            verdicts[key] = f"host ({exc})"
     on_device = {k for k, v in verdicts.items() if v == "device"}
     print("\n".join(f"{k}: {v}" for k, v in sorted(verdicts.items())))
-    # every real-arithmetic demo model is translatable ...
+    # the model of every real-arithmetic demo is translatable ...
     for demo in ("demos/find_peak/sequentialLorentzian.py", "demos/sweeper/sweeper.py", "demos/pipulse/pipulse.py",
                  "demos/line_plus_noise/line_plus_noise.py", "demos/fit_vs_obe/fit_vs_obe_makedata.py",
                  "demos/find_peak/seqLor_pdfevolve.py", "demos/server/server_script.py"):

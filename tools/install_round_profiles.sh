@@ -1,9 +1,9 @@
-# After tools/collect_round_profiles.sh has run on the GPU box (gpurun merges gpurun_out/round/ back): copy the set into
-# profiles/ under the round's names.      bash tools/install_round_profiles.sh r05
+# After tools/collect_round_profiles.sh [DIR] has run on the GPU box and DIR is back in the checkout: copy the set into
+# profiles/ under the round's names.      bash tools/install_round_profiles.sh r05 [DIR]   (DIR: round_out by default)
 set -e
 R=${1:?round tag, e.g. r05}
 cd "$(dirname "$0")/.."
-S=gpurun_out/round
+S=${2:-round_out}
 for f in bench_c1.json bench_c2.json bench_c3.json bench_c5.json demo_cycle.txt host_split_c1.txt host_split_c2.txt spec_cycles_c2.txt update_moments.txt; do
   [ -f $S/$f ] && [ $f != update_moments.txt ] && cp $S/$f profiles/${R}_$f
 done

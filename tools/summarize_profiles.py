@@ -1,19 +1,20 @@
-"""Turn the rocprofv3 (rocpd sqlite) outputs under gpurun_out/prof into the small text
-summaries that are committed under profiles/ (developer aid; run in the build container
-after tools/profile_rocprof.sh has run on the GPU box)."""
+"""Turn the rocprofv3 (rocpd sqlite) outputs of tools/profile_rocprof.sh and tools/profile_sq.sh (under
+$OBE_PROF_ROOT, prof_out/ by default) into the small text summaries that are committed under profiles/
+(developer aid)."""
 import json
 import os
 import sqlite3
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "gpurun_out", "prof")       # (c3; other configs: gpurun_out/prof_<cfg>, set below)
-DST = os.environ.get("OBE_PROFILE_DST", os.path.join(ROOT, "profiles"))    # (on the GPU box: under gpurun_out/)
+PROF = os.path.join(ROOT, os.environ.get("OBE_PROF_ROOT", "prof_out"))
+SRC = os.path.join(PROF, "prof")                     # (c3; other configs: prof_<cfg>, set below)
+DST = os.environ.get("OBE_PROFILE_DST", os.path.join(ROOT, "profiles"))    # (tools/collect_round_profiles.sh: its DIR)
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 cfg = sys.argv[2] if len(sys.argv) > 2 else "c3"
 n_p, n_s, d = {"c3": (1048576, 65536, 3), "c2": (262144, 4096, 3), "c5": (524288, 16384, 10)}[cfg]
 if cfg != "c3":
-    SRC = os.path.join(ROOT, "gpurun_out", f"prof_{cfg}")
+    SRC = os.path.join(PROF, f"prof_{cfg}")
 n_read = d + 1 if cfg != "c5" else 10 + 1        # rows pass A of the update reads (c5: the noise row is one of the 10)
 
 
@@ -51,7 +52,7 @@ grand = sum(sum(v) for v in split.values())
 rows = sorted(((n, len(v), sum(v), sum(v) / len(v), 100.0 * sum(v) / grand) for n, v in split.items()),
               key=lambda r: -r[2])
 with open(os.path.join(DST, f"{tag}_kernel_stats_{cfg}.txt"), "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs ({cfg})\n")
+    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --full ({cfg})\n")
     f.write("# durations in microseconds, from the trace's per-dispatch table; bench.py's own JSON line for this profiled run follows the table\n")
     f.write(f"{'kernel':70s} {'calls':>6s} {'total_us':>12s} {'avg_us':>12s} {'pct':>7s}\n")
     for name, calls, total, avg, pct in rows:
@@ -132,7 +133,7 @@ allcfg[cfg] = {"sweep_kernel_hbm_bytes_per_launch": summary.get("sweep_kernel_hb
 json.dump(allcfg, open(tpath, "w"), indent=1)
 
 # 3. SQ issue counters of the sweep kernel (tools/profile_sq.sh), if collected
-sq_db = os.path.join(ROOT, "gpurun_out", "prof_sq", "sq") if cfg == "c3" else ""      # (collected for c3 only)
+sq_db = os.path.join(PROF, "prof_sq", "sq") if cfg == "c3" else ""      # (collected for c3 only)
 dbs = [os.path.join(dp, f) for dp, _, fs in os.walk(sq_db) for f in fs if f.endswith(".db")] if os.path.isdir(sq_db) else []
 if dbs:
     c = sqlite3.connect(dbs[0])
