@@ -40,8 +40,9 @@ extern "C" {
 
 /* 2 (round 6): obe_resample_begin gained d_aos; the sweep / arg-max calls write a 32-byte record into the
  * workspace tail and the speculative pair keeps its abort word there (OBE_WS_RESULT_TAIL, OBE_WS_ABORT_WORD);
- * limits raised.  A client compiled against another version must not call in: compare obe_abi_version(). */
-#define OBE_ABI_VERSION 2
+ * limits raised.  3: two off-by-default entry points removed (the one-launch update's switch, the randoms enqueued
+ * ahead of a resample); obe_resample_begin refuses a NULL h_pcg_state4.  A client compiled against another version must not call in: compare obe_abi_version(). */
+#define OBE_ABI_VERSION 3
 #define OBE_MAX_CONSTS 8
 #define OBE_MAX_CHANNELS 8   /* output channels of a device model / of one measurement record */
 #define OBE_MAX_SETDIMS 8    /* setting dimensions of a device model */
@@ -164,18 +165,6 @@ OBE_API int obe_bayes_update_model_moments(const obe_model* m,
                                    const double* h_sigma, const int32_t* h_noise_rows,
                                    int32_t n_lik_channels, double choke, double* d_moments,
                                    void* d_ws, int64_t ws_bytes, double* h_out, void* stream);
-
-/* (Libraries built with -DOBE_ONE_PASS_UPDATE only — a measured alternative that is not in the product build,
- * where this switch is accepted and changes nothing: csrc/obe_update.hip, profiles/r05_update_moments.txt.)
- * The form obe_bayes_update_model_moments() and its enqueue variant take on the calling thread: on = 1 — both
- * passes in ONE launch (a grid barrier between the likelihood pass and the normalisation; every thread keeps its
- * particles and their unnormalised weights in registers, so the cloud is read once: 8 (D + 1) N bytes read + 8 N
- * written instead of twice that) wherever it applies (an arrival counter for the stream, at most 6 particles per
- * thread of the 768-workgroup grid, i.e. N <= 1 179 648, n_params = the model's own parameters or one more, a
- * co-resident grid, and the first-moment passes on the update's grid: OBE_FIRST_MOM_PER_CU=3), the two launches
- * otherwise; on = 0 — always two launches.  The results are the same bits either way.  Returns the previous
- * setting; on = -1 changes nothing and returns what the thread's last fused update did (1: one launch, 2: two). */
-OBE_API int obe_update_one_pass(int32_t on);
 
 /* strict sums (per calling thread; returns the previous setting, on < 0 only asks): while on, the UNFUSED updates —
  * obe_bayes_update_model, obe_bayes_update_y, obe_bayes_update_lik — form sum t and sum nan_to_num(w'^2) in the order
@@ -357,17 +346,6 @@ OBE_API int obe_resample_particles_aos_masked(const double* d_old_aos, int32_t n
                                       double* d_new, int64_t ld_new, double* d_weights,
                                       const int32_t* h_rows, int32_t n_rows, double* d_mask_partials, void* stream);
 
-/* The random numbers of a resample, enqueued AHEAD of it (round 6): the N uniforms and N x D normals that resample()
- * takes from the caller's generator (particlepdf.py:272, 296-301) depend only on the generator state and the cloud's
- * shape, and their chain is what a resample's gather ends up waiting for.  Enqueued here — on the library's side stream of
- * `stream`, typically when pdf_update() starts — it runs beside the update and the host round trips;
- * obe_resample_begin(h_pcg_state4 = NULL, the same d_uniforms / d_normals / d_zig_ws / h_i64, the same stream) then
- * launches only the cloud's chains and waits for this one.  The caller compares generator states itself and may keep
- * the numbers across updates that do not resample.  h_i64[0..1] (page-locked) are armed here; wait for them as after
- * obe_resample_begin.  -1 before anything is launched: no side streams, h_i64 not page-locked, n_dims > OBE_FAST_DIMS. */
-OBE_API int obe_resample_randoms_enqueue(const uint64_t* h_pcg_state4, int64_t n_particles, int32_t n_dims, int64_t n_raw,
-                                 double* d_uniforms, const void* d_zig_tables, double* d_normals, void* d_zig_ws,
-                                 int64_t zig_ws_bytes, int64_t* h_i64, void* stream);
 /* resample(), the device side up to the host's factorisation of the covariance, enqueued by ONE call
  * (particlepdf.py:260-301; RNG order as there: N uniforms for rng.choice, then N x D normals): the caller's
  * PCG64 stream continued on the device (h_pcg_state4 = {state hi, lo, increment hi, lo}; n_raw >= N + N D +

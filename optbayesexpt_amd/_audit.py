@@ -235,8 +235,7 @@ def _rule_resample_begin(a, args):
     else:
         a._mark(f64, 1, False)                           # (written by the host: 1.0)
     a._mark(f64 + 8 * (1 + lo), mlen - lo, True)
-    if _addr(args[5]) is not None:                       # (NULL state: the randoms were enqueued ahead, h_i64 armed then)
-        a._mark(_addr(args[19]), 2, True)
+    a._mark(_addr(args[19]), 2, True)
 
 
 def _rule_draw_indices(a, args):
@@ -268,7 +267,6 @@ _RULES = {
     "obe_sweep_utility": _rule_sweep,
     "obe_resample_begin": _rule_resample_begin,
     "obe_draw_indices": _rule_draw_indices,
-    "obe_resample_randoms_enqueue": lambda a, args: a._mark(_addr(args[9]), 2, True),
     "obe_mask_nonpositive_moments": _rule_mask_moments(8, 9, 2),
     "obe_mask_renorm_moments": _rule_mask_moments(7, 8, 2),
     # synchronous forms: they wait for their own words before they return
@@ -294,10 +292,9 @@ RULE_PARAMETERS = {
     "obe_host_words_wait": {0: "h_pinned_words", 1: "n_words"},
     "obe_bayes_update_model_moments_enqueue": {0: "m", 14: "h_pinned_out"},
     "obe_sweep_utility": {11: "shifted", 18: "h_best", 19: "h_best_idx", 20: "h_kappa"},
-    "obe_resample_begin": {2: "n_dims", 5: "h_pcg_state4", 7: "cdf_is_fresh", 8: "have_first_moments", 18: "h_f64",
+    "obe_resample_begin": {2: "n_dims", 7: "cdf_is_fresh", 8: "have_first_moments", 18: "h_f64",
                            19: "h_i64"},
     "obe_draw_indices": {3: "cdf_is_fresh", 6: "n_draws", 7: "d_idx", 8: "h_total_pinned"},
-    "obe_resample_randoms_enqueue": {9: "h_i64"},
     "obe_mask_nonpositive_moments": {2: "n_dims", 8: "h_moments", 9: "h_changed"},
     "obe_mask_renorm_moments": {2: "n_dims", 7: "h_moments", 8: "h_changed"},
     "obe_bayes_update_model": {13: "h_out"},

@@ -72,7 +72,6 @@ _SIGNATURES = {
     "obe_abi_version": (c_int, []),
     "obe_last_error": (ctypes.c_char_p, []),
     "obe_defer_host_sync": (c_int, [c_int32]),
-    "obe_update_one_pass": (c_int, [c_int32]),
     "obe_strict_sums": (c_int, [c_int32]),
     "obe_source_fingerprint": (ctypes.c_char_p, []),
     "obe_model_validate": (c_int, [ctypes.POINTER(ObeModelStruct)]),
@@ -109,7 +108,6 @@ _SIGNATURES = {
                                              _P]),
     "obe_resample_begin": (c_int, [_P, c_int64, c_int32, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int64,
                                    _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, _P]),
-    "obe_resample_randoms_enqueue": (c_int, [_P, c_int64, c_int32, c_int64, _P, _P, _P, _P, c_int64, _P, _P]),
     "obe_resample_particles_aos": (c_int, [_P, c_int32, c_int64, _P, _P, _P, _P, c_double, c_int32, _P, c_int64, _P, _P]),
     "obe_resample_particles_aos_masked": (c_int, [_P, c_int32, c_int64, _P, _P, _P, _P, c_double, c_int32, _P, c_int64, _P,
                                                   _P, c_int32, _P, _P]),
@@ -157,7 +155,7 @@ _SIGNATURES = {
 # entry points whose code depends on the model: a plugin library serves these
 MODEL_ENTRY_POINTS = ("obe_model_validate", "obe_workspace_bytes", "obe_sweep_settings_per_lane",
                       "obe_sweep_settings_per_lane_for", "obe_bayes_update_model",
-                      "obe_bayes_update_model_moments", "obe_bayes_update_model_moments_enqueue", "obe_update_one_pass",
+                      "obe_bayes_update_model_moments", "obe_bayes_update_model_moments_enqueue",
                       "obe_strict_sums",
                       "obe_bayes_update_sweep",
                       "obe_eval_over_particles",

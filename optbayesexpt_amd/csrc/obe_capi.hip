@@ -13,18 +13,12 @@
 
 namespace obe {
 
-// How long the host spins on the result words before it hands the wait to hipStreamSynchronize (microseconds;
-// OBE_HOST_SPIN_US overrides).  While it spins it asks the stream every 50 us whether it has failed or drained
+// The host spins on the result words for kHostWaitSpinUs before it hands the wait to hipStreamSynchronize.
+// While it spins it asks the stream every 50 us whether it has failed or drained
 // (hipStreamQuery, ~1 us), so a kernel that faulted or never delivered is still reported.
-static double host_spin_us() {
-    static const double us = getenv("OBE_HOST_SPIN_US") ? atof(getenv("OBE_HOST_SPIN_US")) : kHostWaitSpinUs;
-    return us;
-}
-
 int wait_host_words(const void* h_words, int64_t n, hipStream_t st) {
     const volatile uint64_t* p = static_cast<const volatile uint64_t*>(h_words);
     const auto t0 = std::chrono::steady_clock::now();
-    const double limit = host_spin_us();
     double next_query = 50.0;
     int64_t next = n - 1;            // words are checked from the last one down; `next` is the highest still armed
     for (;;) {
@@ -39,7 +33,7 @@ int wait_host_words(const void* h_words, int64_t n, hipStream_t st) {
 #endif
         }
         const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        if (us > limit) break;
+        if (us > kHostWaitSpinUs) break;
         if (us > next_query) {
             next_query = us + 50.0;
             const hipError_t q = hipStreamQuery(st);
@@ -161,8 +155,7 @@ bool side_stream_of(hipStream_t st, SideStream* out) {
     ok = ok && hipEventCreateWithFlags(&s.entry, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&s.mid, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&s.done2, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&s.pre, hipEventDisableTiming) == hipSuccess;
+         hipEventCreateWithFlags(&s.done2, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         s = SideStream{};                 // remembered: not tried again for this stream

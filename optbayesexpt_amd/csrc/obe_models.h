@@ -30,16 +30,11 @@ namespace obe {
 // of the group (product tree -> v_rcp_f64 -> correction -> back-substitution), which the wide phases of
 // the neighbouring pair have to cover: dropping the third FMA of the cubically convergent form
 // r (1 + e + e^2) (2^-73) shortened that chain and took 1.6 % off the c3 sweep (13.75 -> 13.52 ms on one
-// box) where the issue slot alone accounts for 0.85 %.  -DOBE_RCP_CUBIC restores the 1-ulp form.
+// box) where the issue slot alone accounts for 0.85 %.  exact_rcp below is the 1-ulp form.
 __device__ __forceinline__ double fast_rcp(double q) {
     const double r = __builtin_amdgcn_rcp(q);
     const double e = fma(-q, r, 1.0);
-#ifdef OBE_RCP_CUBIC
-    const double t = fma(e, e, e);
-    return fma(r, t, r);
-#else
     return fma(r, e, r);
-#endif
 }
 
 // The 1-ulp form, r (1 + e + e^2), where a reciprocal is not shared (N = 1: one setting per lane, i.e. the sweeps

@@ -658,9 +658,8 @@ int obe_pcg64_uniforms_classify(const uint64_t* h_state4, int64_t n_uniform, int
     a.inc = U128{h_state4[2], h_state4[3]};
     if ((a.inc.lo & 1) == 0) return bad_arg("obe_pcg64_uniforms_classify: PCG64 increment must be odd");
     const int64_t total = n_uniform + n_raw_normal;
-    static const int forced = getenv("OBE_RNG_BLOCKS") ? atoi(getenv("OBE_RNG_BLOCKS")) : 0;      // tuning aid
-    const int cap = forced > 0 && forced <= kRngBlocksMax ? forced : 1024;       // 34 us at 1024 (5.8 M positions), 36 at 2048, 45 at 512
-    const int blocks = static_cast<int>(std::min<int64_t>(cap, (total + kBlock - 1) / kBlock));
+    // 34 us at 1024 workgroups (5.8 M positions), 36 at 2048, 45 at 512
+    const int blocks = static_cast<int>(std::min<int64_t>(1024, (total + kBlock - 1) / kBlock));
     lcg_jump(a.inc, (uint64_t)blocks * kBlock, a.strideA, a.strideC);
     const ZigWs w = zig_carve(d_ws, n_raw_normal);
     const ZigTables t = zig_tables(d_tables);

@@ -29,7 +29,6 @@
 // catastrophically (np.var is two-pass; the shift plays the role of its first pass).
 #include <cstdlib>
 #include <cstring>
-#include <ctime>
 
 #include "obe_common.h"
 #include "obe_models.h"
@@ -66,7 +65,7 @@ struct SweepPlan {
     int nchunks_bound; // >= nchunks of this plan and of every plan with fewer draws (workspace sizing)
 };
 
-// Tuned on MI355X at 65 536 x 1 048 576 (tools/exp_sweep_launch.sh): 8 settings per lane (one
+// Tuned on MI355X at 65 536 x 1 048 576 (docs/DESIGN_rounds_1-5.md, commit 0d615a1): 8 settings per lane (one
 // batched reciprocal per 8 evaluations); 768 workgroups are resident (3 per CU at <= 168 VGPRs),
 // and the launch is fastest with about six work items per resident slot (4608: within 0.5 % of
 // the best; 1536 is 2 % slower).  Smaller grids get fewer (down to 1536: 4 096 x 262 144 takes
@@ -77,19 +76,16 @@ struct SweepPlan {
 // uneven tail costs 5 % — 1.145 / 1.146 ms against 1.093 / 1.083 ms with 4096 (same box, in cycles; 6144 and
 // 8192 no better); the one-peak 4096 x 262 144 is indifferent (0.252 vs 0.250-0.254 ms).
 static SweepPlan plan_sweep(int64_t ns, int64_t nd, int cost = 1, int max_spt = 8) {
-    static const int force_spt = getenv("OBE_SWEEP_SPT") ? atoi(getenv("OBE_SWEEP_SPT")) : 0;         // tuning aids
-    static const int force_blocks = getenv("OBE_SWEEP_BLOCKS") ? atoi(getenv("OBE_SWEEP_BLOCKS")) : 0;
     SweepPlan p;
     // (2048 settings: 8 per lane once there are draws enough for the 384 chunks that keep 1536 work items — one
     // rank's 2048 x 524 288 slice of the 10-parameter config: 1.118 vs 1.133 ms, 1.126 vs 1.146 ms, same box)
     p.spt = ns >= 4096 || (ns >= 2048 && nd >= 131072) ? 8 : (ns >= 1024 ? 4 : (ns >= 512 ? 2 : 1));
-    if (force_spt == 1 || force_spt == 2 || force_spt == 4 || force_spt == 8) p.spt = force_spt;
     // (a lane keeps 4 running values per setting and channel in registers: models with more than 4 channels get at
     // most 2 settings per lane)
     if (p.spt > max_spt) p.spt = max_spt;
     p.tiles_x = static_cast<int>((ns + (int64_t)kWave * p.spt - 1) / ((int64_t)kWave * p.spt));
     const int64_t by_work = static_cast<int64_t>((double)ns * (double)nd * (double)cost / 1.25e6);
-    const int64_t target_blocks = force_blocks > 0 ? force_blocks : std::max<int64_t>(1536, std::min<int64_t>(4608, by_work));
+    const int64_t target_blocks = std::max<int64_t>(1536, std::min<int64_t>(4608, by_work));
     int64_t want = (target_blocks + p.tiles_x - 1) / p.tiles_x;
     if (want > 8) want = (want + 7) / 8 * 8;          // whole groups of 8 chunks: one per XCD
     const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(kMaxChunks, nd / 256));   // >= 64 draws per wave
@@ -200,13 +196,8 @@ __device__ __forceinline__ int64_t wave_uniform(int64_t v) {
 
 // SAFE (models with kHasSafeEval only): evaluate with the model's sweep_eval_safe() — the repeat
 // after a sweep whose fast, branch-free batch inversions poisoned a variance (kappa = NaN).
-#ifdef OBE_SWEEP_WAVES_PER_EU          // tuning aid (tools/build_variant.py): force an occupancy
-#define OBE_SWEEP_OCCUPANCY __attribute__((amdgpu_waves_per_eu(OBE_SWEEP_WAVES_PER_EU, OBE_SWEEP_WAVES_PER_EU)))
-#else
-#define OBE_SWEEP_OCCUPANCY
-#endif
 template <class M, int SPT, bool SHIFT, bool SAFE = false>
-__global__ __launch_bounds__(kBlock) OBE_SWEEP_OCCUPANCY void sweep_kernel(SweepArgs a) {
+__global__ __launch_bounds__(kBlock) void sweep_kernel(SweepArgs a) {
     constexpr int NC = M::NC, NXS = M::NXS, NPK = M::NPK, NPKW = packed_width<M>();
     constexpr bool PAIRS = SPT >= 2 && (SAFE ? safe_pair_eval<M>::value : has_pair_eval<M>::value);
     // particles per prefetched group: two groups of packed particles live in SGPRs (~100 per wave)
@@ -1018,8 +1009,7 @@ int obe_sweep_settings_per_lane(int64_t n_settings) {
 int obe_sweep_settings_per_lane_for(int64_t n_settings, int64_t n_draws) {
     if (n_settings < 1) n_settings = 1;
     if (n_draws < 1) return obe_sweep_settings_per_lane(n_settings);
-    static const bool no_small = getenv("OBE_SWEEP_NO_SMALL") != nullptr;
-    if (!no_small && n_draws <= kSmallSweepDraws && n_settings * n_draws <= kSmallSweepEvals) return 1;   // one-workgroup path
+    if (n_draws <= kSmallSweepDraws && n_settings * n_draws <= kSmallSweepEvals) return 1;   // one-workgroup path
     return plan_sweep(n_settings, n_draws).spt;
 }
 
@@ -1075,8 +1065,7 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     }
     HostResult hr = host_result(h_best, h_best_idx, h_kappa);
     hr.tail = result_tail(d_ws, ws_bytes, sweep_ws_need);
-    static const bool no_small = getenv("OBE_SWEEP_NO_SMALL") != nullptr;      // test / tuning aid
-    if (d_draw_idx && !no_small && n_draws <= kSmallSweepDraws && n_settings * n_draws <= kSmallSweepEvals) {
+    if (d_draw_idx && n_draws <= kSmallSweepDraws && n_settings * n_draws <= kSmallSweepEvals) {
         int rc = dispatch_model(mm, [&](auto M) -> int {
             using Model = decltype(M);
             constexpr int NPKW = (Model::NPK + 2) & ~1;
@@ -1120,8 +1109,7 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     if (rc) return rc;
     int nb = static_cast<int>((n_settings + kFinSettings - 1) / kFinSettings);
     if (nb > kFinMaxBlocks) return bad_arg("obe_sweep_utility: more than 4 194 304 settings per call");
-    static const bool no_narrow = getenv("OBE_FINALIZE_NARROW") && atoi(getenv("OBE_FINALIZE_NARROW")) == 0;   // A/B
-    if (plan.nchunks >= kFinManyChunks && nb < kFinNarrowBelow && !no_narrow) {
+    if (plan.nchunks >= kFinManyChunks && nb < kFinNarrowBelow) {
         nb = static_cast<int>((n_settings + kFinNarrow - 1) / kFinNarrow);       // (< 512: within the argmax slots)
         sweep_finalize<kFinGroupsMany, kFinNarrow><<<nb, kFinGroupsMany * kFinNarrow, 0, st>>>(
             w.part1, w.part2, plan.nchunks, mm.n_channels, n_settings, d_moments, d_draw_idx == nullptr, ua, w.cs,
@@ -1194,14 +1182,9 @@ int obe_sweep_kernel_time(const obe_model* m, const double* d_settings, int64_t 
     if (iters < 0) {
         // isolated launches, as a measurement cycle issues them: the stream is drained before each
         // one, so neither the previous launch's tail nor its clocks carry over
-        static const int gap_us = getenv("OBE_TIME_GAP_US") ? atoi(getenv("OBE_TIME_GAP_US")) : 0;   // tuning aid
         double total = 0.0;
         for (int i = 0; i < -iters && !rc; ++i) {
             hipError_t e = hipStreamSynchronize(st);
-            if (gap_us > 0) {
-                timespec ts{0, gap_us * 1000L};
-                nanosleep(&ts, nullptr);
-            }
             (void)hipEventRecord(e0, st);
             rc = dispatch_model(mm, [&](auto M) -> int { return launch_sweep<decltype(M)>(plan, a, sh, st); });
             (void)hipEventRecord(e1, st);

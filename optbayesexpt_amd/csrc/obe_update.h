@@ -17,9 +17,6 @@
 #ifndef OBE_NORM_UNROLL
 #define OBE_NORM_UNROLL 2
 #endif
-#ifndef OBE_UPDATE_ONE_PASS_DEFAULT
-#define OBE_UPDATE_ONE_PASS_DEFAULT 0
-#endif
 
 namespace obe {
 
@@ -118,8 +115,7 @@ struct UpdateFold {
 
 // The tail of a launch that normalises and accumulates first moments: every workgroup publishes its row of
 // partial sums (v[2 + 2 D] = sum w'^2 rides along), the one that arrives last folds all rows in a fixed order
-// and delivers {sum t, sum w'^2}, the K3 block and (enqueue form) the resample decision.  One definition for
-// the two-launch and the one-launch update: the same bits.
+// and delivers {sum t, sum w'^2}, the K3 block and (enqueue form) the resample decision.
 template <int D, int NT = kBlock>
 __device__ __forceinline__ void publish_and_fold_update(double (&v)[3 + 2 * D], double total, double* partials_mom,
                                                         const UpdateFold& fold) {

@@ -404,10 +404,8 @@ int carve_update_ws(void* d_ws, int64_t ws_bytes, UpdateWs& w, int moments_dims)
 // Grid of the update passes: 768 workgroups (3 per CU) measured best at 1M particles
 // (18.3 us per update vs 21.3 us at 2048: fewer partials for pass B / C to fold).
 int update_blocks(int64_t n) {
-    static const int forced = getenv("OBE_UPDATE_BLOCKS") ? atoi(getenv("OBE_UPDATE_BLOCKS")) : 0;   // tuning aid
-    const int cap = forced > 0 ? forced : 768;
     const int nb = stream_blocks(n, kBlock);
-    return nb > cap ? cap : nb;
+    return nb > 768 ? 768 : nb;
 }
 
 // ---- strict sums (obe_strict_sums; tuning_parameters['strict_sums']): np.sum's ORDER of additions ----------------

@@ -31,7 +31,7 @@ def test_library_exports_every_declared_symbol(lib):
     for name in declared:
         assert hasattr(lib.cdll, name), f"{name} declared in obe_hip.h but not exported"
     assert set(declared) == set(_lib._SIGNATURES), "ctypes table and header disagree"
-    assert lib.cdll.obe_abi_version() == _lib.OBE_ABI_VERSION == 2
+    assert lib.cdll.obe_abi_version() == _lib.OBE_ABI_VERSION == 3
 
 
 def _dynamic_symbols(path):
@@ -164,6 +164,10 @@ def test_argument_errors_are_reported_not_crashed(lib):
     assert rc == -1
     with pytest.raises(_lib.ObeHipError):
         lib.call("obe_argmax", None, 0, None, None, None, 0, None)
+    dev = 1 << 20                    # (never dereferenced: a NULL generator state is the first check's refusal)
+    rc = lib.cdll.obe_resample_begin(dev, 16, 3, 16, dev, None, 0, 0, 0, 1 << 16, dev, dev, dev, dev, dev, dev, 1 << 20,
+                                     dev, dev, dev, None, dev, 1 << 20, None)
+    assert rc == -1 and lib.last_error() == "obe_resample_begin: bad pointer/size"
 
 
 def test_sharded_objects_decide_the_range_check_from_all_slices(lib):

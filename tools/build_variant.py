@@ -1,7 +1,8 @@
 """Build libobe_hip from the tree's sources with extra hipcc flags into tools/_variants/<name>.so
 (developer aid for same-box A/B measurements; the product library is untouched).
-    python tools/build_variant.py w4 -DOBE_SWEEP_WAVES_PER_EU=4
-Load it with OBE_VARIANT=w4 in tools/measure_sweep_launch.py."""
+    python tools/build_variant.py u4 -DOBE_NORM_UNROLL=4
+Load it with OBE_VARIANT=u4 in tools/measure_update.py (or measure_moments.py, measure_sweep_launch.py,
+sweep_accuracy.py)."""
 import concurrent.futures, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,9 +1,6 @@
-"""K1 launch duration: back-to-back vs isolated launches, optionally with an idle gap (developer aid).
+"""K1 launch duration: back-to-back vs isolated launches (developer aid).
 
     python tools/measure_sweep_launch.py [c3|c5|c2] [iters]
-
-Environment: OBE_SWEEP_BLOCKS / OBE_SWEEP_SPT (grid tuning), OBE_TIME_GAP_US (host sleep before
-each isolated launch).
 """
 import ctypes, os, sys
 import numpy as np
@@ -40,8 +37,7 @@ def k1(n, shifted=0):
     return ms.value
 
 
-tag = f"{os.environ.get('OBE_AB_ROOT', os.environ.get('OBE_VARIANT', 'tree'))} {cfg} ns_local={n_local} blocks={os.environ.get('OBE_SWEEP_BLOCKS', 'default')} spt={os.environ.get('OBE_SWEEP_SPT', 'default')} " \
-      f"gap_us={os.environ.get('OBE_TIME_GAP_US', '0')}"
+tag = f"{os.environ.get('OBE_AB_ROOT', os.environ.get('OBE_VARIANT', 'tree'))} {cfg} ns_local={n_local}"
 b2b = [k1(iters) for _ in range(3)]
 iso = [k1(-iters) for _ in range(3)] if not os.environ.get("OBE_AB_ROOT") else [float("nan")]
 print(f"{tag}: back-to-back {min(b2b):.3f} ms  isolated {min(iso):.3f} ms  (all: {b2b} {iso})")
