@@ -7,6 +7,9 @@ the reference's demos (demos/sweeper/obe_sweeper.py):
     import optbayesexpt_amd as obe
     my_obe = obe.OptBayesExpt(obe.models.lorentzian(), settings, parameters, constants)
 
+``save(obj, path)`` / ``load(path)`` write an experiment to a file and restore it on the GPU, and the
+classes support ``pickle`` and ``copy.deepcopy`` (see ``_state.py``).
+
 Importing the classes loads libobe_hip.so; there is no CPU fallback.
 """
 from . import models                                        # noqa: F401
@@ -16,5 +19,6 @@ from .obe_noiseparam import OptBayesExptNoiseParameter      # noqa: F401
 from .sweeper import OptBayesExptSweeper                    # noqa: F401
 from .obe_utils import MeasurementSimulator, trace_sort     # noqa: F401
 from .dist import SettingsShard                             # noqa: F401
+from ._state import save, load                              # noqa: F401
 
 __version__ = "0.1.0"

@@ -66,6 +66,22 @@ class DeviceModel:
         self.n_consts = n_consts
         self._numpy_form = numpy_form
         self.__name__ = name
+        #: how to build this model again (see ``spec()``): set by the factories of this module
+        self._recipe = None
+
+    def spec(self):
+        """The recipe this model is rebuilt from, as plain data: ``(factory name, arguments)`` of a hand-tuned
+        model (``("lorentzian", (7,))``), ``("expression", (expressions, settings, parameters, constants, name))``
+        of an expression model, ``("function", (model_function, name))`` of a ``from_function`` model (the
+        user's function itself, which pickles by reference).  ``from_spec(model.spec())`` builds an equal model;
+        a pickled DeviceModel is this recipe.  Raises ``TypeError`` for a model built by hand."""
+        if self._recipe is None:
+            raise TypeError(f"{self!r} was not made by a factory of optbayesexpt_amd.models: it has no recipe "
+                            "to be saved or pickled as")
+        return self._recipe
+
+    def __reduce__(self):
+        return from_spec, (self.spec(),)
 
     def __call__(self, sets, pars, cons):
         """Reference calling convention, for user-side simulation and plotting."""
@@ -129,8 +145,9 @@ def lorentzian(n_peaks=1):
     # the fast sweep forms (3 and more peaks: the peaks of an evaluation combined into one fraction, range-checked;
     # 1 or 2 peaks: two particles per reciprocal, poisoned by overflow) have an always-IEEE twin for the repeat:
     # the pair form with a per-batch branch to element-by-element reciprocals (csrc/obe_models.h, Lorentz<K>)
-    return DeviceModel(f"lorentzian[{n_peaks}]", MODEL_LORENTZ, n_peaks, n_peaks + 2, 1, 1, 1, form,
-                       safe_sweep=True, range_hint=in_range, safe_sweep_min_spt=2 if n_peaks < 3 else 1)
+    return _made(DeviceModel(f"lorentzian[{n_peaks}]", MODEL_LORENTZ, n_peaks, n_peaks + 2, 1, 1, 1, form,
+                             safe_sweep=True, range_hint=in_range, safe_sweep_min_spt=2 if n_peaks < 3 else 1),
+                 "lorentzian", n_peaks)
 
 
 def line_ab():
@@ -138,7 +155,7 @@ def line_ab():
     def form(sets, pars, cons):
         x, = sets
         return pars[0] + pars[1] * x
-    return DeviceModel("line_ab", MODEL_LINE_AB, 0, 2, 1, 1, 0, form)
+    return _made(DeviceModel("line_ab", MODEL_LINE_AB, 0, 2, 1, 1, 0, form), "line_ab")
 
 
 def line_mb():
@@ -146,14 +163,14 @@ def line_mb():
     def form(sets, pars, cons):
         x, = sets
         return pars[0] * x + pars[1]
-    return DeviceModel("line_mb", MODEL_LINE_MB, 0, 2, 1, 1, 0, form)
+    return _made(DeviceModel("line_mb", MODEL_LINE_MB, 0, 2, 1, 1, 0, form), "line_mb")
 
 
 def first_parameter():
     """``y = p0`` (tests/test_zinference.py:21-26)."""
     def form(sets, pars, cons):
         return pars[0]
-    return DeviceModel("first_parameter", MODEL_FIRST_PARAM, 0, 1, 1, 1, 0, form)
+    return _made(DeviceModel("first_parameter", MODEL_FIRST_PARAM, 0, 1, 1, 1, 0, form), "first_parameter")
 
 
 def rabi():
@@ -167,7 +184,7 @@ def rabi():
         f_rabi = np.hypot(delta_f - f_center, b1)
         return baseline * (1 - np.exp(-pulsetime / t1) * contrast / 2 *
                            (1 - np.cos(np.pi * 2 * f_rabi * pulsetime)) / (zz + 1))
-    return DeviceModel("rabi", MODEL_RABI, 0, 2, 2, 1, 3, form)
+    return _made(DeviceModel("rabi", MODEL_RABI, 0, 2, 2, 1, 3, form), "rabi")
 
 
 def coil():
@@ -178,7 +195,7 @@ def coil():
         L, R, C = pars[0], pars[1], pars[2]
         z = 1 / (1 / (R + 1j * w * L) + 1j * w * C)
         return np.array((np.real(z), np.imag(z)))
-    return DeviceModel("coil", MODEL_COIL, 0, 3, 1, 2, 0, form, safe_sweep=True)
+    return _made(DeviceModel("coil", MODEL_COIL, 0, 3, 1, 2, 0, form, safe_sweep=True), "coil")
 
 
 def from_expression(expression, settings, parameters, constants=(), name=None):
@@ -207,8 +224,9 @@ def from_expression(expression, settings, parameters, constants=(), name=None):
         numpy_form.__name__ = name or f"expression[{digest}]"
         return numpy_form
     lib = build.build_plugin(header, digest)
-    return DeviceModel(name or f"expression[{digest}]", MODEL_PLUGIN, 0, len(parameters), len(settings),
-                       n_channels, len(constants), numpy_form, plugin_path=lib)
+    dm = DeviceModel(name or f"expression[{digest}]", MODEL_PLUGIN, 0, len(parameters), len(settings),
+                     n_channels, len(constants), numpy_form, plugin_path=lib)
+    return _made(dm, "expression", expression, tuple(settings), tuple(parameters), tuple(constants), name)
 
 
 def _beyond_device_limits(n_parameters, n_settings, n_channels, n_consts):
@@ -254,4 +272,24 @@ def from_function(model_function, name=None):
     dm = DeviceModel(label, MODEL_PLUGIN, 0, len(parameters), len(settings), len(exprs), len(constants),
                      model_function, plugin_path=lib)
     dm.expressions = exprs
-    return dm
+    return _made(dm, "function", model_function, name)
+
+
+# ------------------------------------------------------------------ recipes (pickling, save / load)
+_FACTORIES = {"lorentzian": lorentzian, "line_ab": line_ab, "line_mb": line_mb, "first_parameter": first_parameter,
+              "rabi": rabi, "coil": coil, "expression": from_expression, "function": from_function}
+
+
+def _made(model, factory, *args):
+    model._recipe = (factory, args)
+    return model
+
+
+def from_spec(spec):
+    """The model a ``DeviceModel.spec()`` describes, built by its factory: a hand-tuned model at once, an
+    expression model from its plugin library (the content-hash cache, or hipcc as on first use), a
+    ``from_function`` model by translating the function's source again."""
+    factory, args = spec
+    if factory not in _FACTORIES:
+        raise ValueError(f"unknown device model factory {factory!r}")
+    return _FACTORIES[factory](*args)

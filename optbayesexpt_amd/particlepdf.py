@@ -655,6 +655,25 @@ class ParticlePDF:
         else:
             _devrng.advance(self._rng, st, n + consumed)
 
+    # ------------------------------------------------------- copy, pickle, save
+    def __getstate__(self):
+        """The object's state as plain host data (_state.py): what ``pickle``, ``multiprocessing`` and
+        ``torch.save`` write.  Work in flight is settled first; the object itself goes on unchanged."""
+        from . import _state
+        return _state.snapshot(self)
+
+    def __setstate__(self, state):
+        """Rebuilds the object through its class's constructor on the current torch device, then restores
+        ``state`` (``ValueError`` for a state of another format version)."""
+        from . import _state
+        _state.restore(state, into=self)
+
+    def __deepcopy__(self, memo):
+        """An independent copy that continues bit for bit alongside the original: the device arrays are cloned
+        on the device, everything mutable is the copy's own.  ``TypeError`` for a settings-sharded object."""
+        from . import _state
+        return _state.deepcopy(self, memo)
+
     @staticmethod
     def _normalized_product(weight_array, likelihood_array):
         """Kept for API compatibility (particlepdf.py:347-360); the product path is
