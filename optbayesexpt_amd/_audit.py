@@ -23,13 +23,13 @@ import os
 
 import numpy as np
 
+# (_lib imports this module after it has defined these)
+from ._lib import HOST_SENTINEL, OBE_SWEEP_NOWAIT, OBE_SWEEP_SPECULATIVE, PROTOTYPES, MomentLayout
+
 try:
     _byte_bounds = np.lib.array_utils.byte_bounds          # numpy >= 2
 except AttributeError:                                      # pragma: no cover
     _byte_bounds = np.byte_bounds
-
-SENTINEL = 0x7ff8c0dec0dec0de          # csrc/obe_common.h: kHostSentinel
-OBE_SWEEP_SPECULATIVE, OBE_SWEEP_NOWAIT = 8, 16
 
 
 class DeliveryError(RuntimeError):
@@ -98,6 +98,10 @@ class _Audit(_NoAudit):
         self.zones = {}           # start -> _Zone
         self.violations = []
         self.counts = dict(zones=0, armed=0, waited=0, reads=0, syncs=0)
+        self.rules = {}           # entry point -> (rule, the argument positions of the parameters it reads)
+        for fn, (rule, *names) in _RULES.items():
+            params = [name for _, name in PROTOTYPES[fn][1]]
+            self.rules[fn] = (rule, tuple(params.index(name) for name in names))
 
     # ---- zones ---------------------------------------------------------------------------------------
     def wrap(self, a):
@@ -156,16 +160,17 @@ class _Audit(_NoAudit):
         if self.violations:
             v, self.violations = self.violations, []
             raise DeliveryError("; ".join(v))
-        rule = _RULES.get(name)
+        rule = self.rules.get(name)
         if rule is not None:
-            rule(self, args)
+            fn, positions = rule
+            fn(self, *[args[i] for i in positions])
 
     def waited(self, addr, n_words):
         if addr is None:
             return
         words = np.ctypeslib.as_array((np.ctypeslib.ctypes.c_uint64 * n_words).from_address(addr))
-        if np.any(words == SENTINEL):
-            raise DeliveryError(f"obe_host_words_wait returned with {int(np.sum(words == SENTINEL))} of {n_words} "
+        if np.any(words == HOST_SENTINEL):
+            raise DeliveryError(f"obe_host_words_wait returned with {int(np.sum(words == HOST_SENTINEL))} of {n_words} "
                                 f"word(s) at {addr:#x} still armed")
         self._mark(addr, n_words, False)
 
@@ -198,114 +203,78 @@ class _Audit(_NoAudit):
 
 
 # ---- which host words a call arms / delivers (include/obe_hip.h) -----------------------------------------
-def _rule_arm(a, args):
-    a._mark(_addr(args[0]), _int(args[1]) if len(args) > 1 else 1, True)
+# A rule gets the arguments of the parameters it names, in that order (resolved through _lib.PROTOTYPES).
+def _arm(a, h_words, n_words=1):
+    a._mark(_addr(h_words), _int(n_words), True)
 
 
-def _rule_arm1(a, args):
-    a._mark(_addr(args[0]), 1, True)
+def _wait(a, h_words, n_words=1):
+    a.waited(_addr(h_words), _int(n_words))
 
 
-def _rule_wait(a, args):
-    a.waited(_addr(args[0]), _int(args[1]))
+def _update_enqueue(a, m, h_pinned_out):
+    a._mark(_addr(h_pinned_out), MomentLayout(int(m.n_params)).update_len, True)
 
 
-def _rule_wait1(a, args):
-    a.waited(_addr(args[0]), 1)
+def _sweep(a, shifted, *h_results):
+    nowait = bool(_int(shifted) & (OBE_SWEEP_SPECULATIVE | OBE_SWEEP_NOWAIT))
+    for h in h_results:
+        a._mark(_addr(h), 1, nowait)                     # (the synchronous form has waited for each of them itself)
 
 
-def _rule_update_enqueue(a, args):
-    d = int(args[0].n_params)
-    a._mark(_addr(args[14]), 5 + 4 * d, True)
+def _resample_begin(a, n_dims, cdf_is_fresh, have_first_moments, h_f64, h_i64):
+    layout = MomentLayout(_int(n_dims))
+    lo = layout.first_len if _int(have_first_moments) else 0
+    f64 = _addr(h_f64)
+    a._mark(f64, 1, not _int(cdf_is_fresh))              # sum(w) of a CDF made by this call (a fresh one: the host's 1.0)
+    a._mark(f64 + 8 * (layout.resample_k3 + lo), layout.total_len - lo, True)
+    a._mark(_addr(h_i64), 2, True)
 
 
-def _rule_sweep(a, args):
-    nowait = _int(args[11]) & (OBE_SWEEP_SPECULATIVE | OBE_SWEEP_NOWAIT)
-    for k in (18, 19, 20):
-        a._mark(_addr(args[k]), 1, bool(nowait))         # (the synchronous form has waited for each of them itself)
+def _draw_indices(a, cdf_is_fresh, n_draws, d_idx, h_total_pinned):
+    if not _int(cdf_is_fresh):
+        a._mark(_addr(h_total_pinned), 1, True)          # sum(p): delivered by the call's kernels, never waited for by it
+    a._mark(_addr(d_idx), _int(n_draws), True)           # the indices, when d_idx is the device view of a landing zone
 
 
-def _rule_resample_begin(a, args):
-    d = _int(args[2])
-    mlen = 2 + 4 * d + d * d
-    lo = 2 + 4 * d if _int(args[8]) else 0
-    f64 = _addr(args[18])
-    if not _int(args[7]):
-        a._mark(f64, 1, True)                            # sum(w) of a CDF made by this call
-    else:
-        a._mark(f64, 1, False)                           # (written by the host: 1.0)
-    a._mark(f64 + 8 * (1 + lo), mlen - lo, True)
-    a._mark(_addr(args[19]), 2, True)
+def _mask_moments(a, n_dims, h_moments, h_changed):
+    a._mark(_addr(h_moments), MomentLayout(_int(n_dims)).first_len, True)
+    a._mark(_addr(h_changed), 1, True)
 
 
-def _rule_draw_indices(a, args):
-    if not _int(args[3]) and _addr(args[8]) is not None:
-        a._mark(_addr(args[8]), 1, True)                 # sum(p): delivered by the call's kernels, never waited for by it
-    a._mark(_addr(args[7]), _int(args[6]), True)         # the indices, when d_idx is the device view of a landing zone
+def _update_moments_delivered(a, m, h_out):
+    a._mark(_addr(h_out), MomentLayout(int(m.n_params)).update_decision, False)     # (the words before the decision)
 
 
-def _rule_mask_moments(h_mom, h_changed, n_dims):
-    def rule(a, args):
-        d = _int(args[n_dims])
-        a._mark(_addr(args[h_mom]), 2 + 4 * d, True)
-        a._mark(_addr(args[h_changed]), 1, True)
+def _delivered(words):
+    def rule(a, *h_results):
+        for h in h_results:
+            a._mark(_addr(h), words, False)
     return rule
 
 
-def _delivered(index, words):
-    def rule(a, args):
-        a._mark(_addr(args[index]), words(args) if callable(words) else words, False)
-    return rule
-
-
+# entry point -> (rule, the parameters it reads by their header names)
 _RULES = {
-    "obe_host_word_arm": _rule_arm1,
-    "obe_host_words_arm": _rule_arm,
-    "obe_host_word_wait": _rule_wait1,
-    "obe_host_words_wait": _rule_wait,
-    "obe_bayes_update_model_moments_enqueue": _rule_update_enqueue,
-    "obe_sweep_utility": _rule_sweep,
-    "obe_resample_begin": _rule_resample_begin,
-    "obe_draw_indices": _rule_draw_indices,
-    "obe_mask_nonpositive_moments": _rule_mask_moments(8, 9, 2),
-    "obe_mask_renorm_moments": _rule_mask_moments(7, 8, 2),
+    "obe_host_word_arm": (_arm, "h_pinned_word"),
+    "obe_host_words_arm": (_arm, "h_pinned_words", "n_words"),
+    "obe_host_word_wait": (_wait, "h_pinned_word"),
+    "obe_host_words_wait": (_wait, "h_pinned_words", "n_words"),
+    "obe_bayes_update_model_moments_enqueue": (_update_enqueue, "m", "h_pinned_out"),
+    "obe_sweep_utility": (_sweep, "shifted", "h_best", "h_best_idx", "h_kappa"),
+    "obe_resample_begin": (_resample_begin, "n_dims", "cdf_is_fresh", "have_first_moments", "h_f64", "h_i64"),
+    "obe_draw_indices": (_draw_indices, "cdf_is_fresh", "n_draws", "d_idx", "h_total_pinned"),
+    "obe_mask_nonpositive_moments": (_mask_moments, "n_dims", "h_moments", "h_changed"),
+    "obe_mask_renorm_moments": (_mask_moments, "n_dims", "h_moments", "h_changed"),
     # synchronous forms: they wait for their own words before they return
-    "obe_bayes_update_model": _delivered(13, 2),
-    "obe_bayes_update_model_moments": _delivered(14, lambda args: 4 + 4 * int(args[0].n_params)),
-    "obe_bayes_update_lik": _delivered(5, 2),
-    "obe_bayes_update_y": _delivered(14, 2),
-    "obe_mask_nonpositive": _delivered(6, 1),
-    "obe_weight_sums": _delivered(4, 2),
-    "obe_weight_cdf": _delivered(4, 1),
-    "obe_utility_argmax": lambda a, args: (a._mark(_addr(args[8]), 1, False), a._mark(_addr(args[9]), 1, False)),
-    "obe_argmax": lambda a, args: (a._mark(_addr(args[2]), 1, False), a._mark(_addr(args[3]), 1, False)),
-}
-
-
-# The argument positions the rules above rely on, by the parameter names of include/obe_hip.h
-# (tests/test_capi_symbols.py::test_audit_rules_address_the_parameters_they_name holds the two together: a changed
-# signature fails there instead of silently auditing the wrong argument).
-RULE_PARAMETERS = {
-    "obe_host_word_arm": {0: "h_pinned_word"},
-    "obe_host_words_arm": {0: "h_pinned_words", 1: "n_words"},
-    "obe_host_word_wait": {0: "h_pinned_word"},
-    "obe_host_words_wait": {0: "h_pinned_words", 1: "n_words"},
-    "obe_bayes_update_model_moments_enqueue": {0: "m", 14: "h_pinned_out"},
-    "obe_sweep_utility": {11: "shifted", 18: "h_best", 19: "h_best_idx", 20: "h_kappa"},
-    "obe_resample_begin": {2: "n_dims", 7: "cdf_is_fresh", 8: "have_first_moments", 18: "h_f64",
-                           19: "h_i64"},
-    "obe_draw_indices": {3: "cdf_is_fresh", 6: "n_draws", 7: "d_idx", 8: "h_total_pinned"},
-    "obe_mask_nonpositive_moments": {2: "n_dims", 8: "h_moments", 9: "h_changed"},
-    "obe_mask_renorm_moments": {2: "n_dims", 7: "h_moments", 8: "h_changed"},
-    "obe_bayes_update_model": {13: "h_out"},
-    "obe_bayes_update_model_moments": {0: "m", 14: "h_out"},
-    "obe_bayes_update_lik": {5: "h_out"},
-    "obe_bayes_update_y": {14: "h_out"},
-    "obe_mask_nonpositive": {6: "h_changed"},
-    "obe_weight_sums": {4: "h_out"},
-    "obe_weight_cdf": {4: "h_total"},
-    "obe_utility_argmax": {8: "h_best", 9: "h_best_idx"},
-    "obe_argmax": {2: "h_best", 3: "h_best_idx"},
+    "obe_bayes_update_model": (_delivered(words=2), "h_out"),
+    "obe_bayes_update_model_moments": (_update_moments_delivered, "m", "h_out"),
+    "obe_bayes_update_lik": (_delivered(words=2), "h_out"),
+    "obe_bayes_update_y": (_delivered(words=2), "h_out"),
+    "obe_mask_nonpositive": (_delivered(words=1), "h_changed"),
+    "obe_weight_sums": (_delivered(words=2), "h_out"),
+    "obe_weight_cdf": (_delivered(words=1), "h_total"),
+    "obe_utility_argmax": (_delivered(words=1), "h_best", "h_best_idx"),
+    "obe_argmax": (_delivered(words=1), "h_best", "h_best_idx"),
 }
 
 audit = _Audit() if os.environ.get("OBE_CHECK_DELIVERY") == "1" else _NoAudit()

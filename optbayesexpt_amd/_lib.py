@@ -31,12 +31,31 @@ OBE_MAX_SETDIMS = _H["OBE_MAX_SETDIMS"]
 OBE_MAX_DIMS = _H["OBE_MAX_DIMS"]
 OBE_FAST_DIMS = _H["OBE_FAST_DIMS"]                  # cloud kernels compiled for the exact row count up to here
 OBE_CLOUD_MAX_DIMS = _H["OBE_CLOUD_MAX_DIMS"]        # what the tiled cloud kernels take (ParticlePDF alone)
-OBE_WS_RESULT_OFFSET = 2      # doubles; include/obe_hip.h
+OBE_WS_RESULT_OFFSET = _H["OBE_WS_RESULT_OFFSET"]    # doubles
+# bits of obe_sweep_utility's `shifted` argument
+OBE_SWEEP_SHIFTED, OBE_SWEEP_SAFE = _H["OBE_SWEEP_SHIFTED"], _H["OBE_SWEEP_SAFE"]
+OBE_SWEEP_SPECULATIVE, OBE_SWEEP_NOWAIT = _H["OBE_SWEEP_SPECULATIVE"], _H["OBE_SWEEP_NOWAIT"]
 HOST_SENTINEL = 0x7ff8c0dec0dec0de     # the value of an armed host result word (csrc/obe_common.h: kHostSentinel)
-OBE_SWEEP_SHIFTED, OBE_SWEEP_SAFE, OBE_SWEEP_SPECULATIVE, OBE_SWEEP_NOWAIT = 1, 2, 8, 16      # bits of obe_sweep_utility's `shifted` argument
 
 c_void_p, c_int, c_int32, c_int64, c_double = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int32,
                                                ctypes.c_int64, ctypes.c_double)
+
+
+class MomentLayout:
+    """Where the K3 moment block of ``n_dims`` parameter rows (include/obe_hip.h: obe_moments) keeps what, and where
+    the host blocks that carry it put it."""
+
+    def __init__(self, n_dims):
+        d = n_dims
+        # [sum w, sum w^2, mean, m1, m2, std] (the first moments), then the D x D covariance
+        self.mean, self.std, self.cov = slice(2, 2 + d), slice(2 + 3 * d, 2 + 4 * d), slice(2 + 4 * d, 2 + 4 * d + d * d)
+        self.first_len = 2 + 4 * d
+        self.total_len = 2 + 4 * d + d * d            # obe_moments_len(n_dims)
+        # the fused update's host block: [sum t, sum w'^2, the first moments, the resample decision (enqueued form)]
+        self.update_decision = 4 + 4 * d
+        self.update_len = 5 + 4 * d
+        # obe_resample_begin's h_f64: [sum w, the K3 block]
+        self.resample_k3 = 1
 
 
 class ObeHipError(RuntimeError):
@@ -66,90 +85,38 @@ def declared_symbols(header_path=HEADER_PATH):
     return sorted(set(re.findall(r"\b(obe_[a-z0-9_]+)\s*\(", text)))
 
 
-_P = c_void_p   # any pointer (device or host) is passed as an integer address
+_SCALARS = {"int": c_int, "int32_t": c_int32, "int64_t": c_int64, "double": c_double}
+# (callers pass the structure itself: ctypes passes it by reference)
+_POINTERS = {"obe_model*": ctypes.POINTER(ObeModelStruct), "char*": ctypes.c_char_p}
 
-_SIGNATURES = {
-    "obe_abi_version": (c_int, []),
-    "obe_last_error": (ctypes.c_char_p, []),
-    "obe_defer_host_sync": (c_int, [c_int32]),
-    "obe_strict_sums": (c_int, [c_int32]),
-    "obe_source_fingerprint": (ctypes.c_char_p, []),
-    "obe_model_validate": (c_int, [ctypes.POINTER(ObeModelStruct)]),
-    "obe_device_info": (c_int, [ctypes.c_char_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int64)]),
-    "obe_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
-    "obe_bayes_update_model": (c_int, [ctypes.POINTER(ObeModelStruct), _P, c_int64, c_int64, _P, _P, _P, _P, _P,
-                                       c_int32, c_double, _P, c_int64, _P, _P]),
-    "obe_bayes_update_model_moments": (c_int, [ctypes.POINTER(ObeModelStruct), _P, c_int64, c_int64, _P, _P, _P, _P, _P,
-                                               c_int32, c_double, _P, _P, c_int64, _P, _P]),
-    "obe_bayes_update_model_moments_enqueue": (c_int, [ctypes.POINTER(ObeModelStruct), _P, c_int64, c_int64, _P, _P, _P,
-                                                       _P, _P, c_int32, c_double, _P, _P, c_int64, _P, c_int32,
-                                                       c_double, _P]),
-    "obe_bayes_update_sweep": (c_int, [ctypes.POINTER(ObeModelStruct), _P, c_int64, c_int64, _P, _P, _P, _P, _P,
-                                       c_int32, c_double, c_int64, c_int32, c_double, _P, c_int64, _P, _P]),
-    "obe_bayes_update_y": (c_int, [_P, c_int64, c_int32, _P, c_int64, c_int64, _P, _P, _P, _P, c_int32,
-                                   c_double, _P, c_int64, _P, _P]),
-    "obe_bayes_update_lik": (c_int, [_P, c_int64, _P, _P, c_int64, _P, _P]),
-    "obe_likelihood_y": (c_int, [_P, c_int64, c_int32, _P, c_int64, c_int64, _P, _P, _P, c_int32, c_double,
-                                 _P, _P]),
-    "obe_weight_sums": (c_int, [_P, c_int64, _P, c_int64, _P, _P]),
-    "obe_eval_over_particles": (c_int, [ctypes.POINTER(ObeModelStruct), _P, c_int64, c_int64, _P, _P, c_int64, _P]),
-    "obe_eval_over_settings": (c_int, [ctypes.POINTER(ObeModelStruct), _P, c_int64, c_int64, _P, _P, c_int64, _P]),
-    "obe_moments_len": (c_int64, [c_int32]),
-    "obe_moments": (c_int, [_P, c_int64, c_int32, c_int64, _P, c_int32, _P, _P, _P, c_int64, _P]),
-    "obe_weight_cdf": (c_int, [_P, c_int64, c_int32, _P, _P, _P, c_int64, _P]),
-    "obe_draw_indices": (c_int, [_P, c_int64, c_int32, c_int32, _P, _P, c_int32, _P, _P, _P, c_int64, _P]),
-    "obe_systematic_indices": (c_int, [_P, c_int64, c_double, c_int64, _P, _P]),
-    "obe_cdf_search": (c_int, [_P, c_int64, _P, c_int64, _P, _P, c_int64, _P]),
-    "obe_gather_columns": (c_int, [_P, c_int64, c_int32, c_int64, _P, c_int64, _P, c_int64, _P]),
-    "obe_resample_particles": (c_int, [_P, c_int64, c_int32, c_int64, _P, _P, _P, _P, c_double, c_int32,
-                                       _P, c_int64, _P, _P, c_int64, _P]),
-    "obe_mask_nonpositive": (c_int, [_P, c_int64, c_int64, _P, c_int32, _P, _P, _P, c_int64, _P]),
-    "obe_mask_nonpositive_moments": (c_int, [_P, c_int64, c_int32, c_int64, _P, c_int32, _P, _P, _P, _P, _P, c_int64,
-                                             _P]),
-    "obe_resample_begin": (c_int, [_P, c_int64, c_int32, c_int64, _P, _P, c_int32, c_int32, c_int32, c_int64,
-                                   _P, _P, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, _P]),
-    "obe_resample_particles_aos": (c_int, [_P, c_int32, c_int64, _P, _P, _P, _P, c_double, c_int32, _P, c_int64, _P, _P]),
-    "obe_resample_particles_aos_masked": (c_int, [_P, c_int32, c_int64, _P, _P, _P, _P, c_double, c_int32, _P, c_int64, _P,
-                                                  _P, c_int32, _P, _P]),
-    "obe_mask_renorm_moments": (c_int, [_P, c_int64, c_int32, c_int64, _P, _P, _P, _P, _P, _P, c_int64, _P]),
-    "obe_pcg64_uniforms_classify": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int64, _P]),
-    "obe_ziggurat_finish": (c_int, [c_int64, c_int64, _P, _P, _P, c_int64, _P]),
-    "obe_noise_var_from_moments": (c_int, [_P, c_int32, _P, c_int32, _P, _P]),
-    "obe_cumsum": (c_int, [_P, c_int64, c_int32, _P, _P, c_int64, _P]),
-    "obe_interval_utility": (c_int, [_P, c_int64, _P, c_int64, _P, c_double, _P, _P]),
-    "obe_power_normalize": (c_int, [_P, c_int64, c_double, _P, _P, c_int64, _P]),
-    "obe_sweep_utility": (c_int, [ctypes.POINTER(ObeModelStruct), _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                  _P, _P, c_int64, _P, c_int32, _P, c_int64, _P, c_double, _P, _P, _P, _P, _P,
-                                  _P, c_int64, _P]),
-    "obe_yspace_variance": (c_int, [_P, c_int64, c_int32, c_int64, _P, _P]),
-    "obe_utility_argmax": (c_int, [_P, c_int32, c_int64, _P, c_int64, _P, c_double, _P, _P, _P, _P, c_int64, _P]),
-    "obe_argmax": (c_int, [_P, c_int64, _P, _P, _P, c_int64, _P]),
-    "obe_eval_draws": (c_int, [ctypes.POINTER(ObeModelStruct), _P, c_int64, c_int64, _P, c_int64, c_int64, _P,
-                               c_int64, _P, _P]),
-    "obe_yspace_add_noise": (c_int, [_P, c_int64, c_int32, c_int64, _P, _P]),
-    "obe_yspace_maxmin": (c_int, [_P, c_int64, c_int64, _P, _P]),
-    "obe_yspace_entropy": (c_int, [_P, c_int64, c_int64, c_int32, _P, _P, _P]),
-    "obe_kld_utility": (c_int, [_P, c_int32, c_int64, _P, _P, _P]),
-    "obe_pcg64_raw": (c_int, [_P, c_int64, _P, _P]),
-    "obe_pcg64_uniform": (c_int, [_P, c_int64, _P, _P]),
-    "obe_ziggurat_workspace_bytes": (c_int64, [c_int64]),
-    "obe_ziggurat_normal": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, _P, _P, c_int64, _P]),
-    "obe_ziggurat_check": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int64]),
-    "obe_timer_create": (c_int, [ctypes.POINTER(c_void_p)]),
-    "obe_timer_start": (c_int, [_P, _P]),
-    "obe_timer_stop": (c_int, [_P, _P, ctypes.POINTER(ctypes.c_float)]),
-    "obe_timer_destroy": (c_int, [_P]),
-    "obe_sweep_settings_per_lane": (c_int, [c_int64]),
-    "obe_sweep_settings_per_lane_for": (c_int, [c_int64, c_int64]),
-    "obe_host_device_pointer": (c_int, [_P, ctypes.POINTER(c_void_p)]),
-    "obe_host_words_arm": (c_int, [_P, c_int64]),
-    "obe_host_words_wait": (c_int, [_P, c_int64, _P]),
-    "obe_host_word_arm": (c_int, [_P]),
-    "obe_host_word_wait": (c_int, [_P, _P]),
-    "obe_sweep_timing": (c_int, [c_int32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int64)]),
-    "obe_sweep_kernel_time": (c_int, [ctypes.POINTER(ObeModelStruct), _P, c_int64, c_int64, _P, c_int64, c_int64,
-                                      _P, _P, c_int32, _P, c_int64, c_int32, ctypes.POINTER(ctypes.c_float), _P]),
-}
+
+def _ctype(c_type):
+    """How a C type of the header is bound (``const`` aside): the scalars and the pointers named above as such, every
+    other pointer as an address.  A type outside this rule is refused, never guessed."""
+    m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)", c_type)
+    if m and m[2]:
+        return _POINTERS.get(m[1] + m[2], c_void_p)
+    if m and m[1] in _SCALARS:
+        return _SCALARS[m[1]]
+    raise TypeError(f"no ctypes binding for the C type {c_type!r} of include/obe_hip.h")
+
+
+def _prototypes(header_path=HEADER_PATH):
+    """name -> (restype, [(ctype, parameter name), ...]) of every OBE_API declaration of the header."""
+    text = re.sub(r"/\*.*?\*/", "", open(header_path).read(), flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"^OBE_API\s+([^(]+?)\s*\b(obe_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        args = []
+        for param in [] if params.strip() == "void" else params.split(","):
+            m = re.fullmatch(r"(.+?)\s*\b(\w+)", param.strip())
+            if m is None:
+                raise TypeError(f"{name}: cannot read the parameter {param.strip()!r} of include/obe_hip.h")
+            args.append((_ctype(m[1]), m[2]))
+        protos[name] = (_ctype(ret), args)
+    return protos
+
+
+PROTOTYPES = _prototypes()
 
 
 # entry points whose code depends on the model: a plugin library serves these
@@ -176,12 +143,12 @@ class HipLib:
         self.path = path
         self.cdll = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL if plugin else ctypes.RTLD_GLOBAL)
         names = MODEL_ENTRY_POINTS + ("obe_abi_version", "obe_last_error", "obe_source_fingerprint") if plugin \
-            else tuple(_SIGNATURES)
+            else tuple(PROTOTYPES)
         for name in names:
-            restype, argtypes = _SIGNATURES[name]
+            restype, params = PROTOTYPES[name]
             fn = getattr(self.cdll, name)
             fn.restype = restype
-            fn.argtypes = argtypes
+            fn.argtypes = [ctype for ctype, _ in params]
         abi = self.cdll.obe_abi_version()
         if abi != OBE_ABI_VERSION:
             raise ImportError(f"libobe_hip ABI {abi} does not match this package ({OBE_ABI_VERSION})")
@@ -255,7 +222,7 @@ class DeviceBound:
 
 
 import contextlib                         # noqa: E402
-from ._audit import audit                 # noqa: E402
+from ._audit import audit                 # noqa: E402  (here: _audit imports names defined above from this module)
 _AUDIT_ON = audit.on
 _NO_GUARD = contextlib.nullcontext()
 

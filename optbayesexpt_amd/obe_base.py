@@ -585,7 +585,6 @@ class OptBayesExpt(ParticlePDF):
     def _update_then_speculate(self, args):
         tp = self.tuning_parameters
         st = self._stream()
-        d = self.n_dims
         p_out = self._hargs.ptr_keep(self._upd_host)
         try:
             self._mlib.call("obe_bayes_update_model_moments_enqueue", *args, _ptr(self._moments_dev),
@@ -613,8 +612,8 @@ class OptBayesExpt(ParticlePDF):
                 if not exc.refused_before_launch:
                     raise
                 self._sweeps.library_refused()        # (nothing of the sweep was enqueued: refused before any launch)
-        self._lib.call("obe_host_words_wait", p_out, 5 + 4 * d, st)
-        self._sweeps.update_delivered(resampled=self._upd_host[4 + 4 * d] != 0.0)
+        self._lib.call("obe_host_words_wait", p_out, self._layout.update_len, st)
+        self._sweeps.update_delivered(resampled=self._upd_host[self._layout.update_decision] != 0.0)
         self._mom_host_key = key + (False,)
         self._sumsq, self._sumsq_key = float(self._upd_host[1]), self._weights.version
         if tp["auto_resample"]:

@@ -86,7 +86,7 @@ class OptBayesExptNoiseParameter(OptBayesExpt):
             self._weights.mark_device_written()
             self._mom_host_key = self._mom_dev_key = (self._particles.version, self._weights.version, False)
             # (the host copy is complete once every word of it — and the count — has arrived: armed by the call)
-            self._mom_host_wait = ((self._hargs.ptr_keep(self._moments_host), 2 + 4 * self.n_dims),
+            self._mom_host_wait = ((self._hargs.ptr_keep(self._moments_host), self._layout.first_len),
                                    (_lib.host_ptr(changed), 1))
         else:       # a stale `parameters` alias (set_pdf between updates): the mask alone, on those rows
             self._lib.call("obe_mask_nonpositive", _ptr(par), par.shape[1], self.n_particles,

@@ -130,6 +130,7 @@ class ParticlePDF:
         self._ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self._device)
         self._ws_bytes = self._ws.numel() * 8
         self._moments_dev = torch.zeros(self._lib.moments_len(d), dtype=torch.float64, device=self._device)
+        self._layout = _lib.MomentLayout(d)
         # page-locked landing zone of the fused update: [0] sum t, [1] sum w'^2, [2:] the K3 block —
         # the host copy of the moments is that tail, whichever call fills it
         self._upd_host = _lib.pinned_array(2 + self._lib.moments_len(d))
@@ -258,19 +259,16 @@ class ParticlePDF:
 
     def mean(self):
         """Weighted mean, shape ``(n_dims,)`` (particlepdf.py:173-183)."""
-        d = self.n_dims
-        return self._moments(False)[2:2 + d].copy()
+        return self._moments(False)[self._layout.mean].copy()
 
     def covariance(self):
         """Weighted covariance ``(n_dims, n_dims)`` (particlepdf.py:185-198)."""
         d = self.n_dims
-        m = self._moments(True)
-        return m[2 + 4 * d:2 + 4 * d + d * d].reshape((d, d)).copy()
+        return self._moments(True)[self._layout.cov].reshape((d, d)).copy()
 
     def std(self):
         """Per-parameter standard deviation (particlepdf.py:200-214)."""
-        d = self.n_dims
-        return self._moments(False)[2 + 3 * d:2 + 4 * d].copy()
+        return self._moments(False)[self._layout.std].copy()
 
     # ------------------------------------------------------------ Bayes update
     def bayesian_update(self, likelihood):
@@ -503,8 +501,8 @@ class ParticlePDF:
         validity test of the covariance only warns, so the pipelined resample runs it (``check()``) after
         the gather has been launched instead of before (25 of the 40-55 us this function takes)."""
         d = self.n_dims
-        mean = m[2:2 + d].copy()
-        cov = m[2 + 4 * d:2 + 4 * d + d * d].reshape((d, d))
+        mean = m[self._layout.mean].copy()
+        cov = m[self._layout.cov].reshape((d, d))
         a = self.tuning_parameters["a_param"]
         newcov = (1 - a ** 2) * cov
         u, s, vh = np.linalg.svd(newcov)
@@ -609,7 +607,8 @@ class ParticlePDF:
             self._cdf_dev = torch.empty(n, dtype=torch.float64, device=self._device)
             self._cdf_key = None
         b = self._resample_buffers(n, d)
-        mlen = self._lib.moments_len(d)
+        layout = self._layout
+        mlen, k3 = layout.total_len, layout.resample_k3
         b["flip"] ^= 1
         idx = b["idx"][b["flip"]]
         mkey = (self._particles.version, self._weights.version)
@@ -624,16 +623,15 @@ class ParticlePDF:
                        b["p_f"], b["p_i"], None if b["aos"] is None else _ptr(b["aos"]), _ptr(self._ws),
                        self._ws_bytes, stream)
         pin_f = b["pin_f"]
-        first = 2 + 4 * d                              # (a covariance-only pass delivers only the covariance)
-        lo = first if have_first else 0
+        lo = layout.first_len if have_first else 0    # (a covariance-only pass delivers only the covariance)
         # (the new cloud's storage, while the covariance is still on its way: off the host's critical path)
         new_cloud = torch.empty((d, n), dtype=torch.float64, device=self._device)
         # every word of the block is watched (the call armed them): the covariance is there, the normals still run
-        self._lib.call("obe_host_words_wait", _P(pin_f.ctypes.data + 8 * (1 + lo)), mlen - lo, stream)
+        self._lib.call("obe_host_words_wait", _P(pin_f.ctypes.data + 8 * (k3 + lo)), mlen - lo, stream)
         self._lib.call("obe_host_words_wait", b["p_f"], 1, stream)     # sum(w), from an earlier kernel
         self._validate_total(float(pin_f[0]))         # (raises before any generator state has moved)
         self._cdf_key = key
-        self._moments_host[lo:mlen] = pin_f[1 + lo:1 + mlen]
+        self._moments_host[lo:mlen] = pin_f[k3 + lo:k3 + mlen]
         self._mom_host_key = self._mom_dev_key = mkey + (True,)
         factor, mean, check_covariance = self._nudge_factor(self._moments_host, defer_check=True)
         self.last_draw_indices_device = idx

@@ -2,7 +2,6 @@
 functions include/obe_hip.h declares with the argument counts the ctypes binding uses,
 and its host-side argument validation reports errors without touching a GPU."""
 import ctypes
-import re
 
 import numpy as np
 import pytest
@@ -15,22 +14,14 @@ def lib():
     return _lib.load()
 
 
-def _header_prototypes():
-    text = open(_lib.HEADER_PATH).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {}
-    for m in re.finditer(r"\b(?:int|int64_t|const char\*)\s+(obe_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        args = m.group(2).strip()
-        protos[m.group(1)] = 0 if args in ("", "void") else len(args.split(","))
-    return protos
-
-
-def test_library_exports_every_declared_symbol(lib):
+def test_library_exports_and_binds_every_declared_symbol(lib):
     declared = _lib.declared_symbols()
     assert len(declared) >= 30
     for name in declared:
         assert hasattr(lib.cdll, name), f"{name} declared in obe_hip.h but not exported"
-    assert set(declared) == set(_lib._SIGNATURES), "ctypes table and header disagree"
+        restype, params = _lib.PROTOTYPES[name]
+        fn = getattr(lib.cdll, name)            # (the binding HipLib applied, not just the one it computed)
+        assert fn.restype is restype and len(fn.argtypes) == len(params), name
     assert lib.cdll.obe_abi_version() == _lib.OBE_ABI_VERSION == 3
 
 
@@ -73,25 +64,18 @@ def test_plugin_exports_nothing_but_the_declared_entry_points(lib):
     assert set(syms) <= set(_lib.declared_symbols()), sorted(set(syms) - set(_lib.declared_symbols()))
 
 
-def _header_parameter_names():
-    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
-    names = {}
-    for m in re.finditer(r"\b(?:int|int64_t|const char\*)\s+(obe_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        args = m.group(2).strip()
-        names[m.group(1)] = [] if args in ("", "void") else [a.strip().split()[-1].lstrip("*") for a in args.split(",")]
-    return names
+def _parameter_names():
+    return {fn: [name for _, name in params] for fn, (_, params) in _lib.PROTOTYPES.items()}
 
 
-def test_audit_rules_address_the_parameters_they_name():
-    """OBE_CHECK_DELIVERY's rules (optbayesexpt_amd/_audit.py) pick host-word pointers and counts out of a call's
-    argument tuple by POSITION; the positions are pinned here to the parameter names of include/obe_hip.h, and every
-    entry point that has a page-locked result parameter has a rule (or is listed as waiting for nothing new)."""
+def test_audit_rules_read_parameters_of_their_entry_points():
+    """OBE_CHECK_DELIVERY's rules (optbayesexpt_amd/_audit.py) read a call's arguments by the parameter names of
+    include/obe_hip.h: every name a rule reads is a parameter of its entry point, and every entry point that has a
+    page-locked result parameter has a rule (or is listed as waiting for nothing new)."""
     from optbayesexpt_amd import _audit
-    names = _header_parameter_names()
-    assert set(_audit._RULES) == set(_audit.RULE_PARAMETERS)
-    for fn, expect in _audit.RULE_PARAMETERS.items():
-        for index, name in expect.items():
-            assert names[fn][index] == name, (fn, index, names[fn][index], name)
+    names = _parameter_names()
+    for fn, (_, *reads) in _audit._RULES.items():
+        assert set(reads) <= set(names[fn]), (fn, sorted(set(reads) - set(names[fn])))
     # every entry point with a host result parameter is covered by a rule
     host_results = ("h_out", "h_pinned_out", "h_pinned_word", "h_pinned_words", "h_best", "h_best_idx", "h_kappa", "h_f64",
                     "h_i64", "h_total", "h_total_pinned", "h_moments", "h_changed")
@@ -100,11 +84,116 @@ def test_audit_rules_address_the_parameters_they_name():
     assert unruled <= {"obe_moments", "obe_bayes_update_sweep", "obe_likelihood_y"}, sorted(unruled)
 
 
-def test_ctypes_argument_counts_match_header():
-    protos = _header_prototypes()
-    assert set(protos) == set(_lib._SIGNATURES)
-    for name, n_args in protos.items():
-        assert len(_lib._SIGNATURES[name][1]) == n_args, name
+_ZONE = np.zeros(64)          # (zeros: no word holds the armed pattern, so every wait a rule records succeeds)
+
+
+def _w(k):
+    """Address of word k of _ZONE."""
+    return ctypes.c_void_p(_ZONE.ctypes.data + 8 * k)
+
+
+def _rule_effect(fn, **values):
+    """(armed, delivered, marks): the words of a landing zone over _ZONE that the OBE_CHECK_DELIVERY rule of entry
+    point `fn` arms and delivers after a call with these parameters (by header name; every other argument None), and
+    the audit's (armed, waited) counts of that call."""
+    from optbayesexpt_amd import _audit
+    names = _parameter_names()[fn]
+    assert set(values) <= set(names), sorted(set(values) - set(names))
+    args = tuple(values.get(name) for name in names)
+    base = _ZONE.ctypes.data
+    changed = []
+    for start in (False, True):          # all words delivered, then all armed: what the call changes
+        a = _audit._Audit()
+        a.zone_created(base, _ZONE.nbytes, None)
+        a.zones[base].armed[:] = start
+        a.after_call(fn, args)
+        changed.append(set(np.flatnonzero(a.zones[base].armed != start).tolist()))
+    return changed[0], changed[1], (a.counts["armed"], a.counts["waited"])
+
+
+def test_audit_rules_arm_and_deliver_the_words_of_their_calls():
+    """Each OBE_CHECK_DELIVERY rule (optbayesexpt_amd/_audit.py), driven on the CPU with a synthetic call: exactly
+    the host words include/obe_hip.h says the call arms (left for the caller to wait for) or delivers (waited for
+    before it returned), for each flag variant that changes which."""
+    from optbayesexpt_amd import _audit
+    d = 3                                # the K3 block of 3 rows: 2 + 4 d = 14 first-moment words, 23 in all
+    m = _lib.ObeModelStruct(n_params=d)
+    span = lambda k, n: set(range(k, k + n))     # noqa: E731
+    cases = [
+        ("obe_host_word_arm", dict(h_pinned_word=_w(5)), ({5}, set(), (1, 0))),
+        ("obe_host_words_arm", dict(h_pinned_words=_w(5), n_words=4), (span(5, 4), set(), (1, 0))),
+        ("obe_host_word_wait", dict(h_pinned_word=_w(5)), (set(), {5}, (0, 1))),
+        ("obe_host_words_wait", dict(h_pinned_words=_w(5), n_words=4), (set(), span(5, 4), (0, 1))),
+        # [sum t, sum w'^2, the 14 first moments, the resample decision]
+        ("obe_bayes_update_model_moments_enqueue", dict(m=m, h_pinned_out=_w(10)), (span(10, 17), set(), (1, 0))),
+        # the synchronous sweep waited for its results; the speculative and the unconditional enqueued form did not
+        ("obe_sweep_utility", dict(shifted=_lib.OBE_SWEEP_SHIFTED, h_best=_w(1), h_best_idx=_w(2), h_kappa=_w(3)),
+         (set(), {1, 2, 3}, (0, 3))),
+        ("obe_sweep_utility", dict(shifted=_lib.OBE_SWEEP_SAFE, h_best=_w(1), h_best_idx=_w(2)),
+         (set(), {1, 2}, (0, 2))),
+        ("obe_sweep_utility", dict(shifted=_lib.OBE_SWEEP_SHIFTED | _lib.OBE_SWEEP_SPECULATIVE, h_best=_w(1),
+                                   h_best_idx=_w(2), h_kappa=_w(3)), ({1, 2, 3}, set(), (3, 0))),
+        ("obe_sweep_utility", dict(shifted=_lib.OBE_SWEEP_NOWAIT, h_best=_w(1), h_best_idx=_w(2), h_kappa=_w(3)),
+         ({1, 2, 3}, set(), (3, 0))),
+        # h_f64 = [sum w, the K3 block]: sum w is armed unless the CDF was fresh (the host stores 1.0), the first
+        # moments unless the caller already has them; h_i64's two words always
+        ("obe_resample_begin", dict(n_dims=d, cdf_is_fresh=0, have_first_moments=0, h_f64=_w(20), h_i64=_w(50)),
+         ({20} | span(21, 23) | {50, 51}, set(), (3, 0))),
+        ("obe_resample_begin", dict(n_dims=d, cdf_is_fresh=1, have_first_moments=0, h_f64=_w(20), h_i64=_w(50)),
+         (span(21, 23) | {50, 51}, {20}, (2, 1))),
+        ("obe_resample_begin", dict(n_dims=d, cdf_is_fresh=0, have_first_moments=1, h_f64=_w(20), h_i64=_w(50)),
+         ({20} | span(35, 9) | {50, 51}, set(), (3, 0))),
+        ("obe_resample_begin", dict(n_dims=d, cdf_is_fresh=1, have_first_moments=1, h_f64=_w(20), h_i64=_w(50)),
+         (span(35, 9) | {50, 51}, {20}, (2, 1))),
+        # sum(p) only when the call rebuilds the CDF; the indices when d_idx is the device view of a landing zone
+        ("obe_draw_indices", dict(cdf_is_fresh=0, n_draws=4, d_idx=_w(30), h_total_pinned=_w(2)),
+         ({2} | span(30, 4), set(), (2, 0))),
+        ("obe_draw_indices", dict(cdf_is_fresh=1, n_draws=4, d_idx=_w(30), h_total_pinned=_w(2)),
+         (span(30, 4), set(), (1, 0))),
+        ("obe_draw_indices", dict(cdf_is_fresh=0, n_draws=4, d_idx=_w(30)), (span(30, 4), set(), (1, 0))),
+        ("obe_draw_indices", dict(cdf_is_fresh=0, n_draws=1, d_idx=None, h_total_pinned=_w(2)), ({2}, set(), (1, 0))),
+        ("obe_mask_nonpositive_moments", dict(n_dims=d, h_moments=_w(10), h_changed=_w(40)),
+         (span(10, 14) | {40}, set(), (2, 0))),
+        ("obe_mask_renorm_moments", dict(n_dims=d, h_moments=_w(10), h_changed=_w(40)),
+         (span(10, 14) | {40}, set(), (2, 0))),
+        ("obe_bayes_update_model", dict(h_out=_w(4)), (set(), {4, 5}, (0, 1))),
+        # [sum t, sum w'^2, the 14 first moments]
+        ("obe_bayes_update_model_moments", dict(m=m, h_out=_w(4)), (set(), span(4, 16), (0, 1))),
+        ("obe_bayes_update_lik", dict(h_out=_w(4)), (set(), {4, 5}, (0, 1))),
+        ("obe_bayes_update_y", dict(h_out=_w(4)), (set(), {4, 5}, (0, 1))),
+        ("obe_mask_nonpositive", dict(h_changed=_w(7)), (set(), {7}, (0, 1))),
+        ("obe_weight_sums", dict(h_out=_w(4)), (set(), {4, 5}, (0, 1))),
+        ("obe_weight_cdf", dict(h_total=_w(7)), (set(), {7}, (0, 1))),
+        ("obe_utility_argmax", dict(h_best=_w(1), h_best_idx=_w(2)), (set(), {1, 2}, (0, 2))),
+        ("obe_argmax", dict(h_best=_w(1), h_best_idx=_w(2)), (set(), {1, 2}, (0, 2))),
+    ]
+    assert {fn for fn, _, _ in cases} == set(_audit._RULES)
+    for fn, values, expect in cases:
+        assert _rule_effect(fn, **values) == expect, (fn, values)
+    # a wait that returns while a word still holds the armed pattern is a violation
+    armed = np.array([0, _lib.HOST_SENTINEL], dtype=np.uint64)
+    with pytest.raises(_audit.DeliveryError):
+        _audit._Audit().after_call("obe_host_words_wait", (ctypes.c_void_p(armed.ctypes.data), 2, None))
+
+
+def test_prototypes_cover_every_declaration():
+    """The strict parse of the OBE_API prototypes that the binding comes from skips no declaration that the loose
+    scan of the header finds."""
+    assert set(_lib.PROTOTYPES) == set(_lib.declared_symbols())
+
+
+def test_prototypes_refuse_a_c_type_outside_the_binding_rule(tmp_path):
+    header = tmp_path / "obe_hip.h"
+    header.write_text("OBE_API int obe_ok(const obe_model* m, void** out, char* name, int64_t n);\n")
+    assert [t for t, _ in _lib._prototypes(str(header))["obe_ok"][1]] == [
+        ctypes.POINTER(_lib.ObeModelStruct), ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]
+    for c_type in ("float", "uint64_t", "unsigned int", "void"):
+        header.write_text(f"OBE_API int obe_bad(const double* d_x, {c_type} v);\n")
+        with pytest.raises(TypeError):
+            _lib._prototypes(str(header))
+    header.write_text("OBE_API float obe_bad(void);\n")
+    with pytest.raises(TypeError):
+        _lib._prototypes(str(header))
 
 
 def test_model_struct_layout_and_validation(lib):
@@ -134,6 +223,8 @@ def test_model_struct_layout_and_validation(lib):
 
 def test_workspace_and_moment_sizes(lib):
     assert lib.moments_len(3) == 2 + 12 + 9
+    for d in list(range(1, 17)) + [40]:
+        assert _lib.MomentLayout(d).total_len == lib.moments_len(d), d
     small = lib.workspace_bytes(1000, 10, 1, 3)
     big = lib.workspace_bytes(1 << 20, 65536, 1, 3)
     assert 0 < small < big < 1 << 30
