@@ -41,6 +41,7 @@ from .models import DeviceModel
 from .particlepdf import ParticlePDF, _P, _ptr
 
 DEFAULT_N_DRAWS = 30            # obe_base.py:19
+MAX_ENTROPY_DRAWS = 2048        # csrc/obe_yspace.hip: kMaxDraws, the samples per column obe_yspace_entropy sorts
 rng = np.random.default_rng()   # module-level generator of the reference (random_setting)
 
 UTILITY_METHODS = ["variance_approx", "pseudo_utility", "full_kld_utility", "max_min",
@@ -1004,14 +1005,25 @@ class OptBayesExpt(ParticlePDF):
             self.utility_y_space[i] = self.eval_over_all_settings(oneparamset)
         return torch.from_numpy(np.ascontiguousarray(self.utility_y_space)).to(self._device)
 
-    def _column_entropy(self, ysp, as_variance):
-        """scipy.stats.differential_entropy(ysp, axis=0) per column, on the device."""
-        nd = ysp.shape[0]
-        cols = ysp[0].numel()
+    @staticmethod
+    def _check_entropy_draws(nd):
+        """The sample sizes obe_yspace_entropy takes, as a ValueError: scipy's own for a window
+        m = floor(sqrt(n) + 0.5) with 2 m >= n (n <= 4; scipy >= 1.12 returns NaN with a warning there instead,
+        which is deliberately not followed), and the sort kernel's limit.  Called BEFORE anything is drawn, so
+        that a refused N_DRAWS leaves self.rng where it was."""
         m = int(np.floor(np.sqrt(nd) + 0.5))
         if not 2 <= 2 * m < nd:
             raise ValueError(f"Window length ({m}) must be positive and less "
                              f"than half the sample size ({nd}).")
+        if nd > MAX_ENTROPY_DRAWS:
+            raise ValueError(f"the entropy utilities (pseudo_utility, full_kld_utility) take at most "
+                             f"{MAX_ENTROPY_DRAWS} draws per setting; N_DRAWS = {nd}")
+
+    def _column_entropy(self, ysp, as_variance):
+        """scipy.stats.differential_entropy(ysp, axis=0) per column, on the device."""
+        nd = ysp.shape[0]
+        cols = ysp[0].numel()
+        self._check_entropy_draws(nd)
         out = torch.empty(ysp.shape[1:], dtype=torch.float64, device=self._device)
         if cols:
             scratch = torch.empty(nd * cols, dtype=torch.float64, device=self._device)
@@ -1025,6 +1037,7 @@ class OptBayesExpt(ParticlePDF):
         return self._gather_settings(self._yvar_from_entropy_device())
 
     def _yvar_from_entropy_device(self):
+        self._check_entropy_draws(self.N_DRAWS)
         return self._column_entropy(self._yspace_device(), True)
 
     def yvar_max_min(self):
@@ -1054,6 +1067,7 @@ class OptBayesExpt(ParticlePDF):
         """exp(H(y + noise) - H(noise)) - 1, shape (C, N_s) (obe_base.py:688-720).  The
         N_DRAWS*C standard normals come from the module-level ``rng`` as in the reference."""
         nd, c = self.N_DRAWS, self.n_channels
+        self._check_entropy_draws(nd)
         ysp = self._yspace_device()
         nva = self._rank0_values(rng.normal(0, 1.0, nd * c))
         nvb = nva.reshape((c, nd))

@@ -21,6 +21,7 @@ __all__ = [
     "weighted_covariance", "weighted_std", "weight_cdf", "choice_indices",
     "systematic_indices", "nudge_factor", "gauss_likelihood", "yvar_from_draws", "yvar_full_sweep",
     "utility_from_yvar", "mean_noise_variance", "flatten_settings",
+    "spacing_entropy", "entropy_variance", "yspace_maxmin", "yspace_variance", "kld_utility",
     "OracleParticlePDF", "OracleOptBayesExpt", "OracleOptBayesExptNoiseParameter",
     "OracleOptBayesExptSweeper",
 ]
@@ -223,6 +224,91 @@ def mean_noise_variance(parameters, noise_index, weights):
     sig2 = np.asarray(parameters)[np.atleast_1d(noise_index)] ** 2
     out = np.sum(sig2 * weights, axis=1) / np.sum(weights)
     return out.reshape((-1, 1))
+
+
+# --------------------------------------------------------------------------
+# The y-space reductions of the non-default utilities (obe_base.py:491-535, 688-720)
+# --------------------------------------------------------------------------
+
+def spacing_entropy(ysp, axis=0, with_log_scale=False, with_sensitivity=False):
+    """scipy.stats.differential_entropy(ysp, axis=axis) with its defaults (method='auto', window
+    m = floor(sqrt(n) + 0.5)), written from the formulas (obe_base.py:7-10, 508-512, 713-718 call it).
+    With the samples of a column sorted, x_0 <= ... <= x_{n-1}, and edge-padded (x_j = x_0 for j < 0,
+    x_j = x_{n-1} for j >= n):
+
+      van Es (n <= 10)              1/(n-m) sum_{i=0}^{n-m-1} log((n+1)/m (x_{i+m} - x_i))
+                                    + sum_{k=m}^{n} 1/k + log m - log(n+1)
+      Ebrahimi et al. (n <= 1000)   1/n sum_{i=1}^{n} log(n (x_{i-1+m} - x_{i-1-m}) / (c_i m)),
+                                    c_i = 1 + (i-1)/m (i <= m), 1 + (n-i)/m (i >= n-m+1), 2 otherwise
+      Vasicek (n > 1000)            1/n sum_{i=1}^{n} log(n/(2m) (x_{i-1+m} - x_{i-1-m}))
+
+    The ARGUMENT of every logarithm is formed in float64 by the operations and in the order written above
+    (scipy's order, and the device's); the logarithms, their sum and the remaining terms are evaluated in
+    np.longdouble and rounded once at the end, so this is the more accurate side of a comparison with either.
+    A zero spacing gives -inf, a NaN in a column NaN, as in scipy.  No scipy import.
+
+    Returns H with ``axis`` removed.  On request also, per column:
+    ``with_log_scale``     mean |log term| — the scale of the rounding error of a float64 evaluation;
+    ``with_sensitivity``   mean 1 / (x_hi - x_lo) over the terms: samples that are each off by at most delta
+                           (an error of the model evaluation behind them) move H by at most 2 delta times this."""
+    y = np.moveaxis(np.asarray(ysp, dtype=np.float64), axis, 0)
+    n = y.shape[0]
+    m = int(np.floor(np.sqrt(n) + 0.5))
+    if not 2 <= 2 * m < n:
+        raise ValueError(f"Window length ({m}) must be positive and less "
+                         f"than half the sample size ({n}).")
+    x = np.sort(y.reshape(n, -1), axis=0)
+    ld = np.longdouble
+    dn, dm = np.float64(n), np.float64(m)
+    with np.errstate(all="ignore"):
+        if n <= 10:
+            hi, lo = x[m:], x[:-m]
+            arg = (dn + 1.0) / dm * (hi - lo)
+            logs = np.log(arg.astype(ld))
+            harm = ld(0)
+            for k in range(m, n + 1):
+                harm += ld(1) / ld(k)
+            h = np.sum(logs, axis=0) / ld(n - m) + harm + np.log(ld(m)) - np.log(ld(n + 1))
+        else:
+            i = np.arange(1, n + 1)
+            hi, lo = x[np.minimum(i - 1 + m, n - 1)], x[np.maximum(i - 1 - m, 0)]
+            if n <= 1000:
+                ci = np.full(n, 2.0)
+                ci[i <= m] = 1.0 + (i[i <= m] - 1) / dm
+                ci[i >= n - m + 1] = 1.0 + (n - i[i >= n - m + 1]) / dm
+                arg = dn * (hi - lo) / (ci * dm)[:, None]
+            else:
+                arg = dn / (2.0 * dm) * (hi - lo)
+            logs = np.log(arg.astype(ld))
+            h = np.sum(logs, axis=0) / ld(n)
+        out = [np.asarray(h, dtype=np.float64).reshape(y.shape[1:])]
+        if with_log_scale:
+            out.append(np.asarray(np.mean(np.abs(logs), axis=0), dtype=np.float64).reshape(y.shape[1:]))
+        if with_sensitivity:
+            out.append(np.mean(1.0 / (hi - lo), axis=0).reshape(y.shape[1:]))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def entropy_variance(h):
+    """obe_base.py:516-517 — the variance of the normal distribution whose entropy is h."""
+    with np.errstate(over="ignore"):
+        return np.exp(2 * np.asarray(h, dtype=np.float64)) / (2 * np.pi * np.e)
+
+
+def yspace_maxmin(ysp):
+    """obe_base.py:531-534 — (max - min)^2 over the draw axis."""
+    return (np.max(ysp, axis=0) - np.min(ysp, axis=0)) ** 2
+
+
+def yspace_variance(ysp):
+    """obe_base.py:487 — np.var over the draw axis (ddof = 0, two passes, draws added in order)."""
+    return np.var(ysp, axis=0)
+
+
+def kld_utility(h_y, h_n):
+    """obe_base.py:718-720 — exp(H(y + noise) - H(noise)) - 1; h_y (C, N_s), h_n (C,)."""
+    with np.errstate(over="ignore"):
+        return np.exp(np.asarray(h_y) - np.asarray(h_n).reshape(-1, 1)) - 1.0
 
 
 # --------------------------------------------------------------------------
@@ -435,19 +521,28 @@ class OracleOptBayesExpt(OracleParticlePDF):
         return np.array(ys)
 
     def utility(self):
-        from scipy.stats import differential_entropy as diffent        # as obe_base.py:7-10
+        """The differential entropies come from scipy, as in the reference (obe_base.py:7-10), not from
+        spacing_entropy: the two agree to a few eps in H, but exp(H_y - H_n) - 1 near zero amplifies that past the
+        1e-13 the golden full_kld trajectory is held to.  ``last_yspace`` keeps the (N_DRAWS, C, N_s) y-space (with
+        the noise added for full_kld; then ``last_noise`` the (N_DRAWS, C) noise values) for checkers that want
+        the high-precision entropies of exactly these draws."""
+        from scipy.stats import differential_entropy as diffent
         if self.utility_method == "max_min":                           # obe_base.py:520-535, 621-626
-            ysp = self._y_space()
-            var_p = (np.max(ysp, axis=0) - np.min(ysp, axis=0)) ** 2
+            self.last_yspace = self._y_space()
+            var_p = yspace_maxmin(self.last_yspace)
         elif self.utility_method == "pseudo_utility":                  # obe_base.py:508-518, 681-686
-            var_p = np.exp(2 * diffent(self._y_space(), axis=0)) / (2 * np.pi * np.e)
+            self.last_yspace = self._y_space()
+            var_p = entropy_variance(diffent(self.last_yspace, axis=0))
         elif self.utility_method == "full_kld_utility":                # obe_base.py:707-720
             draws = self.randdraw(self.N_DRAWS)
             nva = self.noise_rng.normal(0, 1.0, self.N_DRAWS * self.n_channels)
             noise = (nva.reshape((self.n_channels, self.N_DRAWS)) * np.sqrt(self.yvar_noise_model())).T
-            ysp = np.array([np.atleast_2d(self.model_function(self.allsettings, draws[:, i], self.cons))
-                            + noise[i] for i in range(self.N_DRAWS)])
-            return np.exp(diffent(ysp, axis=0) - diffent(noise, axis=0)) - 1.0
+            # (obe_base.py:714-715 adds noisevalues[i], shape (C,), to a (C, N_s) array: that broadcasts for one
+            # channel only.  With more channels the noise of draw i, channel c goes to every setting of that channel.)
+            self.last_noise = noise
+            self.last_yspace = np.array([np.atleast_2d(self.model_function(self.allsettings, draws[:, i], self.cons))
+                                         + noise[i][:, None] for i in range(self.N_DRAWS)])
+            return kld_utility(diffent(self.last_yspace, axis=0), diffent(noise, axis=0))
         else:
             var_p = self.yvar_from_parameter_draws()
         return utility_from_yvar(var_p, self.yvar_noise_model(), self.cost_estimate())

@@ -367,3 +367,72 @@ def conditioning_rtol(ref_var, ref_mean, n_eff, floor=1e-10, eps_y=2.3e-16):
     with np.errstate(divide="ignore", invalid="ignore"):
         cond = np.where(ref_var > 0.0, np.abs(ref_mean) / np.sqrt(ref_var), 0.0)
     return np.maximum(floor, 4.0 * 2.0 * eps_y * cond / np.sqrt(max(float(n_eff), 1.0)))
+
+
+EPS = 2.0 ** -52
+
+
+def entropy_tolerance(n, h_ref, log_scale):
+    """Absolute tolerance of a float64 evaluation of the spacing entropy H (oracle.spacing_entropy's formulas) of
+    n samples per column against the high-precision value ``h_ref`` — derived, not measured.  The argument of every
+    logarithm is formed by the same IEEE operations in the same order on both sides ((n+1)/m * d; n * d / (c_i m);
+    n/(2m) * d), so the arguments are bit-equal and what differs is the logarithm (<= 1 ulp in the device's
+    maths library, 2 allowed) and a serial float64 sum of up to n terms of mean size ``log_scale`` = mean |log
+    term| (<= eps n / 4 of that scale after the division by n):
+
+        |H - H_ref| <= eps [ (n + 2) log_scale + 8 (|H_ref| + A) ],     eps = 2^-52
+
+    with A = 0 for Ebrahimi / Vasicek and, for van Es (n <= 10), the terms added after the sum:
+    sum_{k=m}^{n} 1/k + |log m| + |log(n+1)|.  At n = 2048 this is 4.6e-13 log_scale — orders of magnitude below
+    what a wrong c_i, window or estimator produces (1e-3 ... 1).  Columns whose reference is -inf or NaN have no
+    tolerance (compared exactly by the callers): the value returned for them is unused."""
+    m = int(np.floor(np.sqrt(n) + 0.5))
+    a = sum(1.0 / k for k in range(m, n + 1)) + abs(np.log(m)) + abs(np.log(n + 1)) if n <= 10 else 0.0
+    with np.errstate(invalid="ignore"):
+        return EPS * ((n + 2) * np.asarray(log_scale) + 8.0 * (np.abs(h_ref) + a))
+
+
+def assert_entropy(got, h_ref, tol, what):
+    """H against the reference: -inf, +inf and NaN exactly where the reference has them, every other column within
+    its own ``tol`` (absolute).  The message names the worst column; returns the worst error / tolerance."""
+    got, h_ref = np.asarray(got, dtype=np.float64), np.asarray(h_ref, dtype=np.float64)
+    tol = np.broadcast_to(np.asarray(tol, dtype=np.float64), h_ref.shape)
+    assert got.shape == h_ref.shape, (what, got.shape, h_ref.shape)
+    fin = np.isfinite(h_ref)
+    assert_array_equal(got[~fin], h_ref[~fin], err_msg=f"{what}: columns whose reference is not finite")
+    assert np.all(np.isfinite(got[fin])), f"{what}: {int(np.sum(~np.isfinite(got[fin])))} non-finite value(s) " \
+                                          f"where the reference is finite"
+    if not fin.any():
+        return 0.0
+    ratio = np.zeros(h_ref.shape)
+    ratio[fin] = np.abs(got[fin] - h_ref[fin]) / tol[fin]
+    k = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    assert ratio[k] <= 1.0, (f"{what}: column {k}: got {got[k]!r}, reference {h_ref[k]!r}, error "
+                             f"{abs(got[k] - h_ref[k]):.3g} > tolerance {tol[k]:.3g}")
+    return float(ratio[k])
+
+
+def assert_entropy_variance(got, h_ref, tol, what):
+    """exp(2 H) / (2 pi e) against the same from the reference entropy: relative tolerance 2 tol_H + 8 eps (the
+    exponential turns an absolute error of H into twice that relative error; exp and the division add a few ulp).
+    Exactly 0.0 where H_ref = -inf, and inf / 0 where exp(2 H_ref) overflows / underflows on both sides."""
+    got, h_ref = np.asarray(got, dtype=np.float64), np.asarray(h_ref, dtype=np.float64)
+    with np.errstate(over="ignore", under="ignore"):
+        want = np.exp(2.0 * h_ref) / (2.0 * np.pi * np.e)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    rtol = np.broadcast_to(2.0 * np.asarray(tol, dtype=np.float64) + 8.0 * EPS, want.shape)
+    plain = np.isfinite(want) & (want >= 2.3e-308)          # (a subnormal result has fewer than 53 bits)
+    sub = np.isfinite(want) & ~plain
+    assert_array_equal(got[~np.isfinite(want)], want[~np.isfinite(want)], err_msg=f"{what}: non-finite columns")
+    with np.errstate(invalid="ignore"):
+        allowed = np.where(want[sub] > 0.0, rtol[sub] * want[sub], 0.0) + 4 * 4.95e-324
+    assert np.all(np.abs(got[sub] - want[sub]) <= allowed), f"{what}: subnormal results"
+    assert np.all(got[np.isneginf(h_ref)] == 0.0), f"{what}: H = -inf must give exactly 0.0"
+    if not plain.any():
+        return 0.0
+    ratio = np.zeros(want.shape)
+    ratio[plain] = np.abs(got[plain] - want[plain]) / (rtol[plain] * want[plain])
+    k = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+    assert ratio[k] <= 1.0, (f"{what}: column {k}: got {got[k]!r}, reference {want[k]!r}, relative error "
+                             f"{abs(got[k] / want[k] - 1):.3g} > {rtol[k]:.3g}")
+    return float(ratio[k])

@@ -42,7 +42,7 @@ def _script(body, **extra):
 @pytest.mark.parametrize("files", [
     ["tests/test_gpu_units.py"],
     ["tests/test_gpu_speculative.py", "tests/test_gpu_sweeper.py"],
-    ["tests/test_gpu_trajectories.py", "tests/test_gpu_c_abi.py", "tests/test_gpu_examples.py"],
+    ["tests/test_gpu_trajectories.py", "tests/test_gpu_c_abi.py", "tests/test_gpu_examples.py", "tests/test_gpu_yspace.py"],
     ["tests/test_gpu_two_ranks.py"],
     ["tests/test_gpu_scale.py", "-k", "not whole_grid and not large_cloud"],
 ])

@@ -292,3 +292,105 @@ def test_numpy_pairwise_sum_restatement_is_np_sum_bit_for_bit():
     # the reference's own literal (tests/test_optbayesexpt.py:58-69): lkl / np.sum(lkl)
     lkl = np.exp(-(np.array((1, 4, 4, 7)) - 5.0) ** 2 / 2)
     assert oracle.numpy_pairwise_sum(0.25 * lkl).tobytes() == np.float64(np.sum(0.25 * lkl)).tobytes()
+
+
+# ---- the y-space reductions: oracle.spacing_entropy and its one-line companions ----
+
+ENTROPY_SIZES = list(range(5, 65)) + [99, 100, 101, 999, 1000, 1001, 1024, 2047, 2048, 5000]
+
+
+def _entropy_columns(g, n):
+    """Three columns of n samples: a wide and a narrow normal on an offset, and a heavy-tailed one."""
+    return np.stack([g.normal(3.0, 10.0, n), g.normal(-812.5, 1e-4, n), g.standard_cauchy(n) * 1e3], axis=1)
+
+
+def test_spacing_entropy_matches_scipy_at_every_estimator_and_switch():
+    """oracle.spacing_entropy against scipy.stats.differential_entropy(axis=0) — the function the reference calls
+    (obe_base.py:7-10) — for every sample size 5 ... 64 (van Es up to 10, Ebrahimi from 11, windows m = 2 ... 8) and
+    around the switches and limits further up (99 ... 101, 999 | 1000 | 1001 Ebrahimi -> Vasicek, 1024, 2047, 2048,
+    5000): three columns each plus one with ties (-inf on both sides) and one with a NaN (NaN on both sides).
+    scipy is the LESS accurate side (float64 logs, np.mean): it is held to the tolerance that _replay states for a
+    float64 evaluation against the oracle."""
+    diffent = pytest.importorskip("scipy.stats").differential_entropy
+    g = np.random.default_rng(1507)
+    worst = 0.0
+    for n in ENTROPY_SIZES:
+        cols = _entropy_columns(g, n)
+        tied = g.integers(0, 3, n).astype(np.float64)                  # {0, 1, 2}, and one window is all one value
+        tied[:2 * int(np.floor(np.sqrt(n) + 0.5)) + 1] = 1.0
+        holed = g.normal(size=n)
+        holed[g.integers(n)] = np.nan
+        y = np.concatenate([cols, tied[:, None], holed[:, None]], axis=1)
+        h, scale = oracle.spacing_entropy(y, axis=0, with_log_scale=True)
+        with np.errstate(all="ignore"):
+            ref = diffent(y, axis=0)
+        assert h.shape == ref.shape == (5,)
+        assert np.all(np.isfinite(ref[:3])) and ref[3] == -np.inf and np.isnan(ref[4]), (n, ref)
+        worst = max(worst, _replay.assert_entropy(ref, h, _replay.entropy_tolerance(n, h, scale), f"n = {n}"))
+        # along another axis, and a (n, C, N_s)-shaped y-space
+        assert_array_equal(oracle.spacing_entropy(y.T.copy(), axis=1), h)
+        assert_array_equal(oracle.spacing_entropy(y.reshape(n, 5, 1), axis=0), h.reshape(5, 1))
+    print(f"scipy against the oracle: worst error / tolerance {worst:.3f}")
+    for n in (1, 2, 3, 4):                                              # scipy < 1.12 raises the same for these
+        with pytest.raises(ValueError, match="Window length"):
+            oracle.spacing_entropy(np.arange(float(n)))
+
+
+def test_spacing_entropy_estimators_differ_where_they_switch():
+    """The pins above can tell the estimators apart: at n = 10 | 11 and 1000 | 1001 evaluating the neighbouring
+    estimator's formula instead moves H by far more than the tolerance."""
+    diffent = pytest.importorskip("scipy.stats").differential_entropy
+    g = np.random.default_rng(3)
+    for n, other in ((10, "ebrahimi"), (11, "van es"), (1000, "vasicek"), (1001, "ebrahimi")):
+        y = g.normal(size=(n, 4))
+        h, scale = oracle.spacing_entropy(y, with_log_scale=True)
+        assert np.all(np.abs(diffent(y, axis=0, method=other) - h) > 1e6 * _replay.entropy_tolerance(n, h, scale))
+
+
+@pytest.mark.parametrize("n", [9, 30, 1001])
+def test_spacing_entropy_matches_a_50_digit_evaluation(n):
+    """One column per estimator (van Es n = 9, Ebrahimi n = 30, Vasicek n = 1001) against the same formula evaluated
+    with mpmath at 50 digits from the sorted float64 samples.  What separates the two is the float64 rounding of the
+    logarithms' ARGUMENTS — at most three roundings each (the spacing, the factor, their product or quotient), i.e.
+    a relative error <= 2 eps of the argument = an absolute error <= 2 eps of each log term and of their mean — and
+    the final rounding of H to float64: |H - H_50| <= eps (2 + |H|); x2 margin."""
+    mp = pytest.importorskip("mpmath")
+    g = np.random.default_rng(n)
+    col = g.normal(40.0, 0.37, n)
+    with mp.workdps(50):
+        x = [mp.mpf(float(v)) for v in np.sort(col)]
+        m = int(np.floor(np.sqrt(n) + 0.5))
+        if n <= 10:
+            h = sum(mp.log(mp.mpf(n + 1) / m * (x[i + m] - x[i])) for i in range(n - m)) / (n - m)
+            h += sum(mp.mpf(1) / k for k in range(m, n + 1)) + mp.log(m) - mp.log(n + 1)
+        else:
+            h = mp.mpf(0)
+            for i in range(1, n + 1):
+                d = x[min(i - 1 + m, n - 1)] - x[max(i - 1 - m, 0)]
+                if n <= 1000:
+                    ci = 1 + mp.mpf(i - 1) / m if i <= m else 1 + mp.mpf(n - i) / m if i >= n - m + 1 else mp.mpf(2)
+                    h += mp.log(n * d / (ci * m))
+                else:
+                    h += mp.log(mp.mpf(n) / (2 * m) * d)
+            h /= n
+        got = oracle.spacing_entropy(col)
+        err = float(abs(mp.mpf(float(got)) - h))
+    assert err <= 2 * _replay.EPS * (2 + abs(float(h))), (n, float(got), float(h), err)
+
+
+def test_yspace_one_liners():
+    """yspace_maxmin, yspace_variance, entropy_variance, kld_utility: the reference's expressions
+    (obe_base.py:487, 516-517, 531-534, 720) on a (N_d, C, N_s) array."""
+    g = np.random.default_rng(12)
+    y = g.normal(5.0, 2.0, (7, 2, 9))
+    assert_array_equal(oracle.yspace_maxmin(y), (y.max(axis=0) - y.min(axis=0)) ** 2)
+    assert_array_equal(oracle.yspace_maxmin(y[:1]), np.zeros((2, 9)))
+    assert_array_equal(oracle.yspace_variance(y), np.var(y, axis=0))
+    assert_allclose(oracle.yspace_variance(y), np.mean((y - y.mean(axis=0)) ** 2, axis=0), rtol=1e-14)
+    h = g.normal(size=(2, 9))
+    assert_array_equal(oracle.entropy_variance(h), np.exp(2 * h) / (2 * np.pi * np.e))
+    assert oracle.entropy_variance(-np.inf) == 0.0
+    assert_allclose(oracle.entropy_variance(0.5 * np.log(2 * np.pi * np.e * 4.0)), 4.0, rtol=1e-15)   # N(., 2^2)
+    hn = np.array([0.3, -1.1])
+    assert_array_equal(oracle.kld_utility(h, hn), np.exp(h - hn[:, None]) - 1.0)
+    assert_array_equal(oracle.kld_utility(np.full((2, 1), -np.inf), hn), [[-1.0], [-1.0]])
