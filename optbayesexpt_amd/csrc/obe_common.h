@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/obe_hip.h"
 
@@ -24,6 +26,21 @@ void set_error(const std::string& msg);
 bool defer_host_sync();    // obe_defer_host_sync: host results are copied asynchronously, the caller synchronises
 int fail(hipError_t e, const char* what);
 int bad_arg(const char* what);
+
+// Host-side dispatch on the width of the cloud: f(std::integral_constant<int, D>{}) for D == n_dims in
+// [LO, kFastDims], the widths the cloud kernels are instantiated for; any other width is refused with `refusal`.
+static_assert(OBE_FAST_DIMS == 16, "edit with OBE_FAST_DIMS the four refusals that say \"1..16\": obe_bayes_update_model_moments, "
+                                   "obe_mask_renorm_moments, obe_resample_begin, obe_resample_particles");
+template <int LO, class F, int... I>
+int dispatch_dims_from(int n_dims, const char* refusal, F&& f, std::integer_sequence<int, I...>) {
+    int rc = 0;
+    const bool found = ((n_dims == LO + I && ((rc = f(std::integral_constant<int, LO + I>{})), true)) || ...);
+    return found ? rc : bad_arg(refusal);
+}
+template <int LO = 1, class F>
+int dispatch_dims(int n_dims, const char* refusal, F&& f) {
+    return dispatch_dims_from<LO>(n_dims, refusal, f, std::make_integer_sequence<int, kFastDims - LO + 1>{});
+}
 
 #define OBE_HIP_TRY(expr)                                   \
     do {                                                    \
@@ -77,6 +94,40 @@ inline void arm_host_words(void* h_words, int64_t n) {
     for (int64_t i = 0; i < n; ++i) p[i] = kHostSentinel;
 }
 int wait_host_words(const void* h_words, int64_t n, hipStream_t st);      // obe_capi.hip
+
+// n result words of the caller's (h_words NULL: the caller wants none), and the one statement of how they reach the
+// host.  The call hands view() — the device view, NULL for pageable memory — to the kernel that delivers, arm()s the
+// words once nothing can refuse it any more and BEFORE its first launch, and after its last launch wait()s: by
+// watching the armed words, or — pageable memory, or a call that may not arm (obe_moments) — by the stream's own wait.
+// A call that does not wait by design (the update's enqueue form, OBE_SWEEP_NOWAIT, ...) stops after arm(): the
+// caller watches.  copy() is the pageable route, from the device copy of the results; a no-op where kernels deliver.
+class HostWords {
+  public:
+    HostWords(void* h_words, int64_t n) : host_(h_words), dev_(device_view_of_host(h_words)), n_(n) {}
+    template <class T> T* host() const { return static_cast<T*>(host_); }
+    template <class T> T* view() const { return static_cast<T*>(dev_); }
+    void arm() {
+        if (dev_) arm_host_words(host_, n_);
+        armed_ = dev_ != nullptr;
+    }
+    int copy(int64_t first, int64_t count, const void* d_src, hipStream_t st) const {
+        if (!host_ || dev_) return 0;
+        OBE_HIP_TRY(hipMemcpyAsync(host<uint64_t>() + first, d_src, count * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+    int wait(hipStream_t st) const {
+        if (!host_) return 0;
+        if (armed_) return wait_host_words(host_, n_, st);
+        OBE_HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    }
+
+  private:
+    void* host_;
+    void* dev_;
+    int64_t n_;
+    bool armed_ = false;
+};
 // device side: everything stored to the host before this call is visible there before what follows
 // (the explicit wait restates the one that belongs behind the fence's L2 write-back: ROCm 7.2's compiler drops
 // it when its scoreboard says this wave has nothing outstanding, and the flag store that follows can then
@@ -163,6 +214,20 @@ inline int stream_blocks(int64_t n, int per_block) {
     if (b < 1) b = 1;
     if (b > kMaxBlocks) b = kMaxBlocks;
     return static_cast<int>(b);
+}
+
+// ---- what the calls of obe_resample.hip need of the caller's workspace (they check against these; so does
+// obe_workspace_bytes, next to moments_ws_bytes of obe_moments.h, update_ws_bytes of obe_update.h and the sweep's own)
+constexpr int kScanItems = 8;                         // contiguous weights per thread
+constexpr int kScanTile = kBlock * kScanItems;        // 2048 weights per block
+// obe_weight_cdf / obe_cumsum / obe_draw_indices: 8 scalars, the block sums and (a CDF of weights) the block minima
+inline int64_t scan_ws_bytes(int64_t n) {
+    const int64_t nb = (n + kScanTile - 1) / kScanTile;
+    return (2 * nb + 8) * (int64_t)sizeof(double);
+}
+// obe_resample_particles beyond OBE_FAST_DIMS: the D x D factor and the mean travel through the workspace
+inline int64_t resample_wide_ws_bytes(int n_dims) {
+    return ((int64_t)n_dims * n_dims + n_dims) * (int64_t)sizeof(double);
 }
 
 // np.nan_to_num defaults: NaN -> 0, +inf -> DBL_MAX, -inf -> -DBL_MAX

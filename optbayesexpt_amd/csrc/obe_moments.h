@@ -241,18 +241,11 @@ __device__ __forceinline__ void derive_first_moments(const double* raw, int d, d
     }
 }
 
-// obe_moments() without the final synchronisation (the caller arms and watches the host words it expects,
-// or synchronises); *host_written tells whether h_out was page-locked, i.e. written by the kernels themselves
-int moments_call(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles, const double* d_weights,
-                 int32_t want_cov, double* d_out, double* h_out, void* d_ws, int64_t ws_bytes, hipStream_t st,
-                 bool* host_written);
-
 // Grid of the moment passes (and of the update's normalisation pass that shares them): one workgroup per CU
 // up to 2 M particles; beyond that a wave per SIMD with only D + 1 loads in flight no longer fills HBM
 // (tools/measure_update.py, D = 3, 16.8 M particles: 4.0 TB/s with 256 workgroups, 4.8 with 768; D = 10 is
 // as fast with 256), so narrow clouds get up to three per CU.  kMomGridCap bounds it for the workspace.
 constexpr int kMomGridCap = 3 * kMomBlocks;
-static_assert(kMomGridCap <= 1024, "obe_workspace_bytes sizes the moment partials for at most 1024 workgroups");
 inline int moment_blocks(int64_t n, int d) {
     const int per_cu = n < ((int64_t)1 << 21) ? 1 : (d <= 4 ? 3 : (d <= 7 ? 2 : 1));
     return static_cast<int>(std::min<int64_t>((int64_t)per_cu * kMomBlocks, (n + kBlock - 1) / kBlock));
@@ -264,5 +257,19 @@ inline int moment_blocks(int64_t n, int d) {
 inline int first_moment_blocks(int64_t n, int d) {      // (the same count of workgroups, of more threads each)
     return static_cast<int>(std::min<int64_t>(moment_blocks(n, d), (n + kMomThreads - 1) / kMomThreads));
 }
+
+// What obe_moments needs of the caller's workspace: a row of partial sums per workgroup (and one row to fold into)
+// of the widest pass — first moments or covariance triangle; a kTile x kTile block for the tiled wide clouds.
+constexpr int kTile = 8;
+inline int64_t moments_ws_bytes(int n_dims) {
+    const int64_t nv_max = n_dims > kFastDims ? kTile * kTile
+                                              : std::max<int64_t>(2 + 2 * n_dims, (int64_t)n_dims * (n_dims + 1) / 2);
+    return ((int64_t)kMomGridCap * nv_max + nv_max) * (int64_t)sizeof(double);
+}
+
+// obe_moments() without delivery to the host: `host` is the device view of the caller's page-locked copy (the
+// kernels write it; the caller arms and watches the words it expects, or synchronises) or NULL
+int moments_call(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles, const double* d_weights,
+                 int32_t want_cov, double* d_out, double* host, void* d_ws, int64_t ws_bytes, hipStream_t st);
 
 }  // namespace obe

@@ -114,8 +114,7 @@ __global__ __launch_bounds__(kFoldThreads) void fold_derive_pass2(const double* 
 // launches for the first moments, T (T + 1) launches for the covariance, T = ceil(D/8) — slower than one
 // pass with everything in registers, and any D.  Per-particle arithmetic, block reductions and folds are the ones
 // above (accumulate_first_moments, store_block_partials, fold_values_block): a fixed order, run-to-run identical.
-constexpr int kTile = 8;
-
+// (kTile = 8: obe_moments.h)
 // first moments of rows [d0, d0 + kTile): v[0] = sum w, v[1] = sum w^2 (every tile; tile 0's are used),
 // v[2 + i] = sum x w, v[2 + kTile + i] = sum x^2 w   (rows past the end: zeros)
 __global__ __launch_bounds__(kBlock) void moments_pass1_tile(const double* __restrict__ x, int64_t ld, int64_t n,
@@ -269,31 +268,19 @@ static int launch_moments(const double* x, int64_t ld, int64_t n, const double* 
     return 0;
 }
 
-// obe_moments without the final synchronisation (obe_resample_begin arms and watches the host words)
+// obe_moments without delivery to the host (obe_resample_begin arms and watches the host words)
 int moments_call(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles, const double* d_weights,
-                 int32_t want_cov, double* d_out, double* h_out, void* d_ws, int64_t ws_bytes, hipStream_t st,
-                 bool* host_written) {
+                 int32_t want_cov, double* d_out, double* host, void* d_ws, int64_t ws_bytes, hipStream_t st) {
     if (!d_particles || !d_weights || !d_out || n_particles <= 0) return bad_arg("obe_moments: bad pointer/size");
     if (n_dims < 1 || n_dims > OBE_CLOUD_MAX_DIMS) return bad_arg("obe_moments: n_dims must be 1..1024");
-    const bool tiled = n_dims > kFastDims;
-    const int64_t nv_max = tiled ? kTile * kTile : std::max<int64_t>(2 + 2 * n_dims, (int64_t)n_dims * (n_dims + 1) / 2);
-    const int64_t need = ((int64_t)kMomGridCap * nv_max + nv_max) * sizeof(double);
-    if (!d_ws || ws_bytes < need) return bad_arg("obe_moments: workspace too small");
+    if (!d_ws || ws_bytes < moments_ws_bytes(n_dims)) return bad_arg("obe_moments: workspace too small");
     double* partials = static_cast<double*>(d_ws);
-    double* hv = static_cast<double*>(device_view_of_host(h_out));     // page-locked h_out: the kernels write it
-    const MomentsOut mo{d_out, hv};
-    if (host_written) *host_written = hv != nullptr;
-    if (tiled) return launch_moments_tiled(d_particles, ld_p, n_dims, n_particles, d_weights, want_cov, partials, mo, st);
-    int rc = -1;
-#define OBE_MOM_CASE(DD) \
-    case DD: rc = launch_moments<DD>(d_particles, ld_p, n_particles, d_weights, want_cov, partials, mo, st); break;
-    switch (n_dims) {
-        OBE_MOM_CASE(1) OBE_MOM_CASE(2) OBE_MOM_CASE(3) OBE_MOM_CASE(4) OBE_MOM_CASE(5) OBE_MOM_CASE(6)
-        OBE_MOM_CASE(7) OBE_MOM_CASE(8) OBE_MOM_CASE(9) OBE_MOM_CASE(10) OBE_MOM_CASE(11) OBE_MOM_CASE(12)
-        OBE_MOM_CASE(13) OBE_MOM_CASE(14) OBE_MOM_CASE(15) OBE_MOM_CASE(16)
-    }
-#undef OBE_MOM_CASE
-    return rc;
+    const MomentsOut mo{d_out, host};
+    if (n_dims > kFastDims)
+        return launch_moments_tiled(d_particles, ld_p, n_dims, n_particles, d_weights, want_cov, partials, mo, st);
+    return dispatch_dims(n_dims, "obe_moments: no kernel for this n_dims", [&](auto D) -> int {
+        return launch_moments<decltype(D)::value>(d_particles, ld_p, n_particles, d_weights, want_cov, partials, mo, st);
+    });
 }
 
 }  // namespace obe
@@ -308,16 +295,15 @@ int obe_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t
                 const double* d_weights, int32_t want_cov, double* d_out, double* h_out, void* d_ws,
                 int64_t ws_bytes, void* stream) {
     hipStream_t st = as_stream(stream);
-    bool host_written = false;
-    if (int rc = moments_call(d_particles, ld_p, n_dims, n_particles, d_weights, want_cov, d_out, h_out, d_ws, ws_bytes,
-                              st, &host_written))
+    const int64_t len = want_cov ? obe_moments_len(n_dims) : 2 + 4 * (int64_t)n_dims;
+    // (page-locked h_out: the kernels write it.  Never armed — want_cov == 2 leaves the words of the first moments
+    // alone —, so the wait is the stream's own)
+    const HostWords out(h_out, len);
+    if (int rc = moments_call(d_particles, ld_p, n_dims, n_particles, d_weights, want_cov, d_out, out.view<double>(),
+                              d_ws, ws_bytes, st))
         return rc;
-    if (h_out) {
-        const int64_t len = want_cov ? obe_moments_len(n_dims) : 2 + 4 * (int64_t)n_dims;
-        if (!host_written) OBE_HIP_TRY(hipMemcpyAsync(h_out, d_out, len * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (!defer_host_sync()) OBE_HIP_TRY(hipStreamSynchronize(st));
-    }
-    return 0;
+    if (int rc = out.copy(0, len, d_out, st)) return rc;
+    return defer_host_sync() ? 0 : out.wait(st);
 }
 
 }  // extern "C"

@@ -16,9 +16,6 @@
 
 namespace obe {
 
-constexpr int kScanItems = 8;                         // contiguous weights per thread
-constexpr int kScanTile = kBlock * kScanItems;        // 2048 weights per block
-
 // Inclusive scan of one 2048-element tile held as 8 contiguous items per thread.
 // Returns the tile total in every thread.  The same routine is used by the block-sum
 // pass and by the final pass, so both see bit-identical values.
@@ -496,13 +493,6 @@ __global__ __launch_bounds__(kBlock) void resample_wide_kernel(const double* __r
     }
 }
 
-template <int D>
-static int launch_soa_to_aos(const double* d_old, int64_t ld_old, int64_t n, double* aos, hipStream_t st) {
-    soa_to_aos_kernel<D><<<stream_blocks(n, kBlock), kBlock, 0, st>>>(d_old, ld_old, n, aos);
-    OBE_CHECK_LAUNCH("soa_to_aos_kernel");
-    return 0;
-}
-
 // d_old == nullptr: d_ws already IS the (N, D) copy of the old cloud (obe_resample_particles_aos)
 template <int D>
 static int launch_resample(const NudgeArgs& na, const double* d_old, int64_t ld_old, int64_t n, const int64_t* d_idx,
@@ -539,8 +529,7 @@ static int scan_common(const char* who, const double* d_x, int64_t n, int32_t st
                        double* d_out, double* h_total, void* d_ws, int64_t ws_bytes, void* stream) {
     if (!d_x || !d_out || n <= 0) return bad_arg(who);
     const int64_t nb = (n + kScanTile - 1) / kScanTile;
-    const int64_t need = (2 * nb + 8) * (int64_t)sizeof(double);
-    if (!d_ws || ws_bytes < need) return bad_arg("scan: workspace too small");
+    if (!d_ws || ws_bytes < scan_ws_bytes(n)) return bad_arg("scan: workspace too small");
     double* scalars = static_cast<double*>(d_ws);
     double* block_sums = scalars + 8;
     double* block_mins = normalize ? block_sums + nb : nullptr;       // a CDF of weights: validated like numpy's p
@@ -741,8 +730,7 @@ static int resample_particles(const double* d_old, int64_t ld_old, int32_t n_dim
     if (n_dims > kFastDims) {
         // wide cloud: only the plain form (the (D, N) cloud, no mask); F and the mean travel through the workspace
         if (!d_old || mask_bits) return bad_arg("obe_resample_particles_aos: more than OBE_FAST_DIMS parameters (use obe_resample_particles)");
-        const int64_t fm_doubles = (int64_t)n_dims * n_dims + n_dims;
-        if (!d_ws || ws_bytes < fm_doubles * (int64_t)sizeof(double)) return bad_arg("obe_resample_particles: workspace too small");
+        if (!d_ws || ws_bytes < resample_wide_ws_bytes(n_dims)) return bad_arg("obe_resample_particles: workspace too small");
         hipStream_t ws_st = as_stream(stream);
         double* fm = static_cast<double*>(d_ws);
         OBE_HIP_TRY(hipMemcpyAsync(fm, h_factor, sizeof(double) * n_dims * n_dims, hipMemcpyHostToDevice, ws_st));
@@ -762,16 +750,10 @@ static int resample_particles(const double* d_old, int64_t ld_old, int32_t n_dim
     for (int i = 0; i < n_dims * n_dims; ++i) na.factor[i] = h_factor[i];
     for (int i = 0; i < n_dims; ++i) na.mean[i] = h_mean[i];
     hipStream_t st = as_stream(stream);
-#define OBE_RS_CASE(DD) \
-    case DD: return launch_resample<DD>(na, d_old, ld_old, n_particles, d_idx, d_normals, d_new, ld_new, d_weights, \
-                                        d_ws, ws_bytes, st, mask_bits, d_mask_partials);
-    switch (n_dims) {
-        OBE_RS_CASE(1) OBE_RS_CASE(2) OBE_RS_CASE(3) OBE_RS_CASE(4) OBE_RS_CASE(5) OBE_RS_CASE(6) OBE_RS_CASE(7)
-        OBE_RS_CASE(8) OBE_RS_CASE(9) OBE_RS_CASE(10) OBE_RS_CASE(11) OBE_RS_CASE(12) OBE_RS_CASE(13)
-        OBE_RS_CASE(14) OBE_RS_CASE(15) OBE_RS_CASE(16)
-    }
-#undef OBE_RS_CASE
-    return bad_arg("obe_resample_particles: n_dims must be 1..16");
+    return dispatch_dims(n_dims, "obe_resample_particles: n_dims must be 1..16", [&](auto D) -> int {
+        return launch_resample<decltype(D)::value>(na, d_old, ld_old, n_particles, d_idx, d_normals, d_new, ld_new,
+                                                   d_weights, d_ws, ws_bytes, st, mask_bits, d_mask_partials);
+    });
 }
 
 // The device side of ParticlePDF.resample() up to the point where the host must factorise the covariance
@@ -800,11 +782,11 @@ int obe_resample_begin(const double* d_particles, int64_t ld_p, int32_t n_dims, 
     if (n_dims < 1 || n_dims > kFastDims) return bad_arg("obe_resample_begin: n_dims must be 1..16 (OBE_FAST_DIMS)");
     const int64_t n = n_particles, n_normal = n * n_dims;
     if (n_raw < n + n_normal + 4096) return bad_arg("obe_resample_begin: fewer raw values than the draws need");
-    if (!device_view_of_host(h_f64) || !device_view_of_host(h_i64))
+    double* hv_f64 = static_cast<double*>(device_view_of_host(h_f64));
+    if (!hv_f64 || !device_view_of_host(h_i64))
         return bad_arg("obe_resample_begin: the host result buffers must be page-locked");
     hipStream_t st = as_stream(stream);
     const int prev = obe_defer_host_sync(1);
-    int rc = 0;
     // Two chains that share nothing but the uniforms: the generator's (raw values -> uniforms, ziggurat normals
     // and their bookkeeping: touches d_uniforms, d_normals, d_zig_ws, h_i64) and the cloud's (CDF, search,
     // covariance: d_ws, d_cdf, d_idx, d_moments, h_f64).  They run side by side on two streams — the random
@@ -828,100 +810,93 @@ int obe_resample_begin(const double* d_particles, int64_t ld_p, int32_t n_dims, 
     // written only afterwards — the caller's workspace belongs to the scan and the search, which now run beside
     // it) and the copy.  The host then has the covariance ~20 us earlier, and the caller's stream is scan ->
     // guide -> search only: the random chain (~85 us at that size) is what the gather waits for.
-    const int64_t nv_max = std::max<int64_t>(2 + 2 * n_dims, (int64_t)n_dims * (n_dims + 1) / 2);
-    const bool third = split && d_aos && n_dims >= 2 && side.stream2 &&
-                       (int64_t)n_dims * n >= (int64_t)kMomGridCap * nv_max + nv_max;
+    const int64_t aos_bytes = (int64_t)sizeof(double) * n_dims * n;
+    const bool third = split && d_aos && n_dims >= 2 && side.stream2 && aos_bytes >= moments_ws_bytes(n_dims);
     const bool copy_here = d_aos && n_dims >= 2;
-    auto make_aos = [&](hipStream_t on) -> int {
-#define OBE_AOS_CASE(DD) \
-    case DD: return launch_soa_to_aos<DD>(d_particles, ld_p, n, d_aos, on);
-        switch (n_dims) {
-            OBE_AOS_CASE(2) OBE_AOS_CASE(3) OBE_AOS_CASE(4) OBE_AOS_CASE(5) OBE_AOS_CASE(6) OBE_AOS_CASE(7) OBE_AOS_CASE(8)
-            OBE_AOS_CASE(9) OBE_AOS_CASE(10) OBE_AOS_CASE(11) OBE_AOS_CASE(12) OBE_AOS_CASE(13) OBE_AOS_CASE(14)
-            OBE_AOS_CASE(15) OBE_AOS_CASE(16)
-        }
-#undef OBE_AOS_CASE
-        return 0;
+
+    // The pieces, each stated once; the three layouts below only order them.  Random numbers: uniforms + the
+    // classification of every raw position behind them, straight from the generator state; then the normals (h_i64)
+    auto uniforms = [&]() -> int {
+        return obe_pcg64_uniforms_classify(h_pcg_state4, n, n_raw - n, d_uniforms, d_zig_tables, d_zig_ws, zig_ws_bytes, rs);
     };
-    do {
+    auto normals = [&]() -> int {
+        return obe_ziggurat_finish(n_raw - n, n_normal, d_normals, h_i64, d_zig_ws, zig_ws_bytes, rs);
+    };
+    // ... as a chain of its own on the side stream: `mid` = the uniforms are there, `done` = the normals are
+    auto random_chain = [&]() -> int {
+        if (int e = ev(hipStreamWaitEvent(side.stream, side.entry, 0))) return e;
+        if (int e = uniforms()) return e;
+        if (int e = ev(hipEventRecord(side.mid, side.stream))) return e;
+        if (int e = normals()) return e;
+        return ev(hipEventRecord(side.done, side.stream));
+    };
+    // the weight CDF on the caller's stream, unless the caller's is fresh
+    auto cdf = [&]() -> int {
+        if (cdf_is_fresh) {
+            h_f64[0] = 1.0;
+            return 0;
+        }
+        arm_host_word(h_f64);
+        return obe_weight_cdf(d_weights, n, strict_cdf, d_cdf, h_f64, d_ws, ws_bytes, stream);
+    };
+    auto search = [&]() -> int { return obe_cdf_search(d_cdf, n, d_uniforms, n, d_idx, d_ws, ws_bytes, stream); };
+    // the covariance (and, unless have_first_moments, the first moments) of the pre-resample cloud, its partial sums
+    // in `ws`; the words it delivers are armed here and watched by the caller
+    auto covariance = [&](void* ws, int64_t bytes, hipStream_t on) -> int {
+        arm_host_words(h_f64 + 1 + lo, obe_moments_len(n_dims) - lo);
+        return moments_call(d_particles, ld_p, n_dims, n, d_weights, have_first_moments ? 2 : 1, d_moments, hv_f64 + 1,
+                            ws, bytes, on);
+    };
+    auto make_aos = [&](hipStream_t on) -> int {
+        if (!copy_here) return 0;
+        return dispatch_dims<2>(n_dims, "soa_to_aos_kernel: no kernel for this n_dims", [&](auto D) -> int {
+            soa_to_aos_kernel<decltype(D)::value><<<stream_blocks(n, kBlock), kBlock, 0, on>>>(d_particles, ld_p, n, d_aos);
+            OBE_CHECK_LAUNCH("soa_to_aos_kernel");
+            return 0;
+        });
+    };
+
+    auto enqueue = [&]() -> int {
         if (third) {
             // Three chains.  The host enqueues the LONGEST first — the random numbers (uniforms + classification,
             // then four ziggurat kernels: ~90 us at 524 288 x 10, what the gather ends up waiting for) —, then the
             // covariance + (N, D) copy (the host's factorisation waits for the covariance), then CDF -> guide ->
             // search on the caller's stream: every launch costs the host 2-4 us, and with the cloud's chains first
             // the random chain used to start 20-45 us after the others.
-            if ((rc = ev(hipEventRecord(side.entry, st)))) break;
-            if ((rc = ev(hipStreamWaitEvent(side.stream, side.entry, 0)))) break;
-            if ((rc = obe_pcg64_uniforms_classify(h_pcg_state4, n, n_raw - n, d_uniforms, d_zig_tables, d_zig_ws,
-                                                  zig_ws_bytes, rs)))
-                break;
-            if ((rc = ev(hipEventRecord(side.mid, side.stream)))) break;
-            if ((rc = obe_ziggurat_finish(n_raw - n, n_normal, d_normals, h_i64, d_zig_ws, zig_ws_bytes, rs))) break;
-            if ((rc = ev(hipEventRecord(side.done, side.stream)))) break;
-            if ((rc = ev(hipStreamWaitEvent(side.stream2, side.entry, 0)))) break;
-            arm_host_words(h_f64 + 1 + lo, obe_moments_len(n_dims) - lo);
-            bool host_written = false;
-            if ((rc = moments_call(d_particles, ld_p, n_dims, n, d_weights, have_first_moments ? 2 : 1, d_moments,
-                                   h_f64 + 1, d_aos, (int64_t)sizeof(double) * n_dims * n, side.stream2, &host_written)))
-                break;
-            if ((rc = make_aos(side.stream2))) break;
-            if ((rc = ev(hipEventRecord(side.done2, side.stream2)))) break;
-            if (!cdf_is_fresh) {
-                arm_host_word(h_f64);
-                if ((rc = obe_weight_cdf(d_weights, n, strict_cdf, d_cdf, h_f64, d_ws, ws_bytes, stream))) break;
-            } else {
-                h_f64[0] = 1.0;
-            }
-            if ((rc = ev(hipStreamWaitEvent(st, side.mid, 0)))) break;
-            if ((rc = obe_cdf_search(d_cdf, n, d_uniforms, n, d_idx, d_ws, ws_bytes, stream))) break;
-            if ((rc = ev(hipStreamWaitEvent(st, side.done, 0)))) break;
-            if ((rc = ev(hipStreamWaitEvent(st, side.done2, 0)))) break;
-            break;
+            if (int e = ev(hipEventRecord(side.entry, st))) return e;
+            if (int e = random_chain()) return e;
+            if (int e = ev(hipStreamWaitEvent(side.stream2, side.entry, 0))) return e;
+            if (int e = covariance(d_aos, aos_bytes, side.stream2)) return e;
+            if (int e = make_aos(side.stream2)) return e;
+            if (int e = ev(hipEventRecord(side.done2, side.stream2))) return e;
+            if (int e = cdf()) return e;
+            if (int e = ev(hipStreamWaitEvent(st, side.mid, 0))) return e;
+            if (int e = search()) return e;
+            if (int e = ev(hipStreamWaitEvent(st, side.done, 0))) return e;
+            return ev(hipStreamWaitEvent(st, side.done2, 0));
         }
-        // (split: the cloud's chain is enqueued first — the host waits for the covariance, and every launch costs
-        // it a few microseconds; the kernels of the random chain arrive while the scan is already running)
-        if (split && (rc = ev(hipEventRecord(side.entry, st)))) break;
-        auto cdf_and_covariance = [&]() -> int {
-            if (!cdf_is_fresh) {
-                arm_host_word(h_f64);
-                if (int e = obe_weight_cdf(d_weights, n, strict_cdf, d_cdf, h_f64, d_ws, ws_bytes, stream)) return e;
-            } else {
-                h_f64[0] = 1.0;
-            }
-            if (!split) return 0;       // (one stream: the round-3 order, covariance after the search)
-            arm_host_words(h_f64 + 1 + lo, obe_moments_len(n_dims) - lo);
-            bool host_written = false;
-            return moments_call(d_particles, ld_p, n_dims, n, d_weights, have_first_moments ? 2 : 1, d_moments, h_f64 + 1,
-                                d_ws, ws_bytes, st, &host_written);
-        };
-        if (split && (rc = cdf_and_covariance())) break;
-        // the buffers of the random chain may still be read by earlier work of the caller's stream
-        if (split && (rc = ev(hipStreamWaitEvent(side.stream, side.entry, 0)))) break;
-        // uniforms + the classification of every raw position behind them, straight from the generator state
-        if ((rc = obe_pcg64_uniforms_classify(h_pcg_state4, n, n_raw - n, d_uniforms, d_zig_tables, d_zig_ws,
-                                              zig_ws_bytes, rs)))
-            break;
         if (split) {
-            if ((rc = ev(hipEventRecord(side.mid, side.stream)))) break;
-            if ((rc = obe_ziggurat_finish(n_raw - n, n_normal, d_normals, h_i64, d_zig_ws, zig_ws_bytes, rs))) break;
-            if ((rc = ev(hipEventRecord(side.done, side.stream)))) break;
-            if ((rc = ev(hipStreamWaitEvent(st, side.mid, 0)))) break;
-        } else if ((rc = cdf_and_covariance())) {
-            break;
+            // (the cloud's chain is enqueued first — the host waits for the covariance, and every launch costs
+            // it a few microseconds; the kernels of the random chain arrive while the scan is already running)
+            if (int e = ev(hipEventRecord(side.entry, st))) return e;
+            if (int e = cdf()) return e;
+            if (int e = covariance(d_ws, ws_bytes, st)) return e;
+            // the buffers of the random chain may still be read by earlier work of the caller's stream
+            if (int e = random_chain()) return e;
+            if (int e = ev(hipStreamWaitEvent(st, side.mid, 0))) return e;
+            if (int e = search()) return e;
+            if (int e = make_aos(st)) return e;
+            return ev(hipStreamWaitEvent(st, side.done, 0));
         }
-        if ((rc = obe_cdf_search(d_cdf, n, d_uniforms, n, d_idx, d_ws, ws_bytes, stream))) break;
-        if (copy_here && (rc = make_aos(st))) break;
-        if (split) {
-            if ((rc = ev(hipStreamWaitEvent(st, side.done, 0)))) break;
-        } else {
-            arm_host_words(h_f64 + 1 + lo, obe_moments_len(n_dims) - lo);
-            bool host_written = false;
-            if ((rc = moments_call(d_particles, ld_p, n_dims, n, d_weights, have_first_moments ? 2 : 1, d_moments,
-                                   h_f64 + 1, d_ws, ws_bytes, st, &host_written)))
-                break;
-            if ((rc = obe_ziggurat_finish(n_raw - n, n_normal, d_normals, h_i64, d_zig_ws, zig_ws_bytes, stream))) break;
-        }
-    } while (false);
+        // one stream: the round-3 order, covariance after the search
+        if (int e = uniforms()) return e;
+        if (int e = cdf()) return e;
+        if (int e = search()) return e;
+        if (int e = make_aos(st)) return e;
+        if (int e = covariance(d_ws, ws_bytes, st)) return e;
+        return normals();
+    };
+    const int rc = enqueue();
     obe_defer_host_sync(prev);
     return rc;
 }

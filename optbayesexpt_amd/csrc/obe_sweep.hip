@@ -32,6 +32,7 @@
 
 #include "obe_common.h"
 #include "obe_models.h"
+#include "obe_update.h"
 
 namespace obe {
 
@@ -97,16 +98,6 @@ static SweepPlan plan_sweep(int64_t ns, int64_t nd, int cost = 1, int max_spt = 
     p.chunk = (p.chunk + 63) / 64 * 64;
     p.nchunks = static_cast<int>((nd + p.chunk - 1) / p.chunk);
     return p;
-}
-
-static int64_t sweep_ws_doubles(int64_t ns, int64_t nd, int nc, int packed_w) {
-    const SweepPlan p = plan_sweep(ns, nd, 1 << 20);       // (the grid of the costliest model: the most chunks)
-    // (sized by the monotone bound: the chunk count itself is not monotone in nd after the rounding
-    // of the chunk length, and a sweep of N_DRAWS < n_particles draws runs in the same workspace)
-    return 2 * (int64_t)p.nchunks_bound * nc * ns  // partial S1, S2
-           + (int64_t)nc * ns                      // per-setting shift
-           + 3 * argmax_slots(ns) + 16             // argmax / kappa partials + scalars
-           + nd * packed_w + 8;                    // packed draws
 }
 
 struct SweepArgs {
@@ -454,7 +445,7 @@ __device__ __forceinline__ double kappa_worst(double a, double b) {
 }
 
 // Where the result goes on the host, as device-visible addresses (page-locked host memory), or all
-// NULL: then read_best() copies it.
+// NULL: then BestWords::read() copies it.
 struct HostResult {
     double* best;
     int64_t* idx;
@@ -858,6 +849,13 @@ struct SweepWs {
 static int64_t sweep_ws_bytes(int64_t part_doubles, int64_t cs_doubles, int64_t slots, int64_t packed_doubles) {
     return (2 * part_doubles + cs_doubles + 3 * slots + 16 + packed_doubles + 2) * (int64_t)sizeof(double);
 }
+// ... of any sweep of ns settings, nc channels and AT MOST nd draws (obe_workspace_bytes)
+static int64_t sweep_ws_bytes_bound(int64_t ns, int64_t nd, int nc, int packed_w) {
+    const SweepPlan p = plan_sweep(ns, nd, 1 << 20);       // (the grid of the costliest model: the most chunks)
+    // (sized by the monotone bound: the chunk count itself is not monotone in nd after the rounding
+    // of the chunk length, and a sweep of N_DRAWS < n_particles draws runs in the same workspace)
+    return sweep_ws_bytes((int64_t)p.nchunks_bound * nc * ns, (int64_t)nc * ns, argmax_slots(ns), nd * packed_w);
+}
 static int carve_sweep_ws(void* d_ws, int64_t ws_bytes, int64_t part_doubles, int64_t cs_doubles, SweepWs& w,
                           int64_t slots = kMaxBlocks, int64_t packed_doubles = 0) {
     const int64_t need = sweep_ws_bytes(part_doubles, cs_doubles, slots, packed_doubles);
@@ -883,34 +881,43 @@ static double* result_tail(void* d_ws, int64_t ws_bytes, int64_t need_bytes) {
     return reinterpret_cast<double*>(static_cast<char*>(d_ws) + (ws_bytes & ~(int64_t)7) - 48);
 }
 
-// the device views of the caller's host outputs if every one that is asked for is page-locked; each such
-// word is armed (before any launch) and read_best() waits for each of them
-static HostResult host_result(double* h_best, int64_t* h_best_idx, double* h_kappa) {
-    HostResult r{static_cast<double*>(device_view_of_host(h_best)), static_cast<int64_t*>(device_view_of_host(h_best_idx)),
-                 static_cast<double*>(device_view_of_host(h_kappa))};
-    if ((h_best && !r.best) || (h_best_idx && !r.idx) || (h_kappa && !r.kappa)) r = HostResult{nullptr, nullptr, nullptr};
-    if (r.best) arm_host_word(h_best);
-    if (r.idx) arm_host_word(h_best_idx);
-    if (r.kappa) arm_host_word(h_kappa);
-    return r;
-}
-
-static int read_best(const SweepWs& w, double* h_best, int64_t* h_best_idx, hipStream_t st,
-                     double* h_kappa = nullptr, const HostResult& delivered = HostResult{nullptr, nullptr, nullptr}) {
-    if (!h_best && !h_best_idx && !h_kappa) return 0;
-    if (delivered.best || delivered.idx || delivered.kappa) {       // the kernel writes them: watch every word
-        if (h_best_idx) if (int rc = wait_host_word(h_best_idx, st)) return rc;
-        if (h_kappa) if (int rc = wait_host_word(h_kappa, st)) return rc;
-        if (h_best) if (int rc = wait_host_word(h_best, st)) return rc;
+// The caller's three result words.  The kernels deliver them only if every one that is asked for is page-locked:
+// then each is armed (before any launch) and read() waits for each of them; otherwise read() copies the record.
+struct BestWords {
+    HostWords best, idx, kappa;
+    bool by_kernel;
+    BestWords(double* hb, int64_t* hi, double* hk) : best(hb, 1), idx(hi, 1), kappa(hk, 1) {
+        by_kernel = !((hb && !best.view<void>()) || (hi && !idx.view<void>()) || (hk && !kappa.view<void>()));
+    }
+    // what the delivering kernel is given (tail: OBE_WS_RESULT_TAIL, or NULL)
+    HostResult arm(double* tail) {
+        if (!by_kernel) return HostResult{nullptr, nullptr, nullptr, tail};
+        best.arm();
+        idx.arm();
+        kappa.arm();
+        return HostResult{best.view<double>(), idx.view<int64_t>(), kappa.view<double>(), tail};
+    }
+    int read(const SweepWs& w, hipStream_t st) const {
+        if (by_kernel) {       // the kernel writes them: watch every word (none asked for: nothing to wait for)
+            if (int rc = idx.wait(st)) return rc;
+            if (int rc = kappa.wait(st)) return rc;
+            return best.wait(st);
+        }
+        double tmp[9];
+        OBE_HIP_TRY(hipMemcpyAsync(tmp, w.out_v, 9 * sizeof(double), hipMemcpyDeviceToHost, st));
+        OBE_HIP_TRY(hipStreamSynchronize(st));
+        if (best.host<void>()) *best.host<double>() = tmp[0];
+        if (kappa.host<void>()) *kappa.host<double>() = tmp[1];
+        if (idx.host<void>()) memcpy(idx.host<void>(), &tmp[8], sizeof(int64_t));
         return 0;
     }
-    double tmp[9];
-    OBE_HIP_TRY(hipMemcpyAsync(tmp, w.out_v, 9 * sizeof(double), hipMemcpyDeviceToHost, st));
-    OBE_HIP_TRY(hipStreamSynchronize(st));
-    if (h_best) *h_best = tmp[0];
-    if (h_kappa) *h_kappa = tmp[1];
-    if (h_best_idx) memcpy(h_best_idx, &tmp[8], sizeof(int64_t));
-    return 0;
+};
+
+// the last launch of obe_utility_argmax / obe_argmax and the delivery of its result
+static int fold_best(const SweepWs& w, int nb, const HostResult& hr, const BestWords& out, hipStream_t st) {
+    argmax_fold<<<1, kBlock, 0, st>>>(w.bv, w.bi, nb, nullptr, w.out_v, w.out_i, hr);
+    OBE_CHECK_LAUNCH("argmax_fold");
+    return out.read(w, st);
 }
 
 template <class M, bool SHIFT, bool SAFE>
@@ -1023,13 +1030,13 @@ int64_t obe_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_c
 #else
     const int packed_w = max_packed_width(n_dims);
 #endif
-    int64_t d = sweep_ws_doubles(n_settings, n_particles, n_channels, packed_w);
-    const int64_t nv = std::max<int64_t>(2 + 2 * n_dims, (int64_t)n_dims * (n_dims + 1) / 2);
-    d = std::max<int64_t>(d, 1024 * nv + nv);                       // moments (grid cap <= 1024)
-    d = std::max<int64_t>(d, 2 * kMaxBlocks + 8 + 1024 * (2 + 2 * (int64_t)n_dims));   // update + fused first moments
-    d = std::max<int64_t>(d, 2 * ((n_particles + 2047) / 2048) + 8);      // cdf block sums and minima
-    d = std::max<int64_t>(d, 2 * (int64_t)kMaxBlocks + 8);          // update partials
-    return (d + 64) * (int64_t)sizeof(double);
+    // the largest of what each consumer checks against, plus room for the tails (OBE_WS_RESULT_TAIL, OBE_WS_ABORT_WORD)
+    int64_t b = sweep_ws_bytes_bound(n_settings, n_particles, n_channels, packed_w);
+    b = std::max(b, moments_ws_bytes(n_dims));
+    b = std::max(b, update_ws_bytes(n_dims));          // (with the fused first moments; without them it is less)
+    b = std::max(b, scan_ws_bytes(n_particles));
+    b = std::max(b, resample_wide_ws_bytes(n_dims));
+    return b + 64 * (int64_t)sizeof(double);
 }
 
 int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
@@ -1059,12 +1066,11 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
                 return bad_arg("obe_sweep_utility: OBE_SWEEP_SPECULATIVE needs 16 spare bytes at the end of the workspace (OBE_WS_ABORT_WORD)");
             a.abort = ws_abort_word(d_ws, ws_bytes);
         }
-        if ((h_best && !device_view_of_host(h_best)) || (h_best_idx && !device_view_of_host(h_best_idx)) ||
-            (h_kappa && !device_view_of_host(h_kappa)))
-            return bad_arg("obe_sweep_utility: OBE_SWEEP_SPECULATIVE / OBE_SWEEP_NOWAIT need page-locked host outputs");
     }
-    HostResult hr = host_result(h_best, h_best_idx, h_kappa);
-    hr.tail = result_tail(d_ws, ws_bytes, sweep_ws_need);
+    BestWords out(h_best, h_best_idx, h_kappa);
+    if (nowait && !out.by_kernel)
+        return bad_arg("obe_sweep_utility: OBE_SWEEP_SPECULATIVE / OBE_SWEEP_NOWAIT need page-locked host outputs");
+    const HostResult hr = out.arm(result_tail(d_ws, ws_bytes, sweep_ws_need));
     if (d_draw_idx && n_draws <= kSmallSweepDraws && n_settings * n_draws <= kSmallSweepEvals) {
         int rc = dispatch_model(mm, [&](auto M) -> int {
             using Model = decltype(M);
@@ -1082,7 +1088,7 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
             return 0;
         });
         if (rc) return rc;
-        return read_best(w, h_best, h_best_idx, st, h_kappa, hr);
+        return out.read(w, st);
     }
     // (a call without host outputs — a sharded rank reads the record itself — is timed too: it waits for the
     // sweep kernel's end event instead of for the result)
@@ -1109,19 +1115,20 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     if (rc) return rc;
     int nb = static_cast<int>((n_settings + kFinSettings - 1) / kFinSettings);
     if (nb > kFinMaxBlocks) return bad_arg("obe_sweep_utility: more than 4 194 304 settings per call");
+    // (FG chunk groups x WS settings per workgroup: see sweep_finalize)
+    auto finalize = [&](auto FG, auto WS) {
+        sweep_finalize<decltype(FG)::value, decltype(WS)::value><<<nb, decltype(FG)::value * decltype(WS)::value, 0, st>>>(
+            w.part1, w.part2, plan.nchunks, mm.n_channels, n_settings, d_moments, d_draw_idx == nullptr, ua, w.cs,
+            d_yvar, d_utility, w.bv, w.bi, w.bk, a.abort);
+    };
+    using std::integral_constant;
     if (plan.nchunks >= kFinManyChunks && nb < kFinNarrowBelow) {
         nb = static_cast<int>((n_settings + kFinNarrow - 1) / kFinNarrow);       // (< 512: within the argmax slots)
-        sweep_finalize<kFinGroupsMany, kFinNarrow><<<nb, kFinGroupsMany * kFinNarrow, 0, st>>>(
-            w.part1, w.part2, plan.nchunks, mm.n_channels, n_settings, d_moments, d_draw_idx == nullptr, ua, w.cs,
-            d_yvar, d_utility, w.bv, w.bi, w.bk, a.abort);
+        finalize(integral_constant<int, kFinGroupsMany>{}, integral_constant<int, kFinNarrow>{});
     } else if (plan.nchunks >= kFinManyChunks)
-        sweep_finalize<kFinGroupsMany><<<nb, kFinGroupsMany * kWave, 0, st>>>(
-            w.part1, w.part2, plan.nchunks, mm.n_channels, n_settings, d_moments, d_draw_idx == nullptr, ua, w.cs,
-            d_yvar, d_utility, w.bv, w.bi, w.bk, a.abort);
+        finalize(integral_constant<int, kFinGroupsMany>{}, integral_constant<int, kFinSettings>{});
     else
-        sweep_finalize<kFinGroupsFew><<<nb, kFinGroupsFew * kWave, 0, st>>>(
-            w.part1, w.part2, plan.nchunks, mm.n_channels, n_settings, d_moments, d_draw_idx == nullptr, ua, w.cs,
-            d_yvar, d_utility, w.bv, w.bi, w.bk, a.abort);
+        finalize(integral_constant<int, kFinGroupsFew>{}, integral_constant<int, kFinSettings>{});
     OBE_CHECK_LAUNCH("sweep_finalize");
     argmax_fold<<<1, kBlock, 0, st>>>(w.bv, w.bi, nb, w.bk, w.out_v, w.out_i, hr, a.abort);
     OBE_CHECK_LAUNCH("argmax_fold");
@@ -1132,7 +1139,7 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
         }
         return 0;
     }
-    rc = read_best(w, h_best, h_best_idx, st, h_kappa, hr);
+    rc = out.read(w, st);
     if (timed && !rc && !(h_best || h_best_idx || h_kappa)) rc = (int)hipEventSynchronize(g_timing.e1);
     if (timed && !rc) {                       // the stream is drained: both events have completed
         float ms = 0.f;
@@ -1172,7 +1179,9 @@ int obe_sweep_kernel_time(const obe_model* m, const double* d_settings, int64_t 
     hipEvent_t e0, e1;
     OBE_HIP_TRY(hipEventCreate(&e0));
     OBE_HIP_TRY(hipEventCreate(&e1));
-    const int sh = shifted;
+    auto sweep_once = [&]() -> int {
+        return dispatch_model(mm, [&](auto M) -> int { return launch_sweep<decltype(M)>(plan, a, shifted, st); });
+    };
     int rc = dispatch_model(mm, [&](auto M) -> int { return launch_pack<decltype(M)>(a, st); });
     if (rc) {
         (void)hipEventDestroy(e0);
@@ -1186,7 +1195,7 @@ int obe_sweep_kernel_time(const obe_model* m, const double* d_settings, int64_t 
         for (int i = 0; i < -iters && !rc; ++i) {
             hipError_t e = hipStreamSynchronize(st);
             (void)hipEventRecord(e0, st);
-            rc = dispatch_model(mm, [&](auto M) -> int { return launch_sweep<decltype(M)>(plan, a, sh, st); });
+            rc = sweep_once();
             (void)hipEventRecord(e1, st);
             if (e == hipSuccess) e = hipEventSynchronize(e1);
             float ms = 0.f;
@@ -1196,11 +1205,11 @@ int obe_sweep_kernel_time(const obe_model* m, const double* d_settings, int64_t 
         }
         *h_ms_avg = (float)(total / (double)(-iters));
     } else {
-        rc = dispatch_model(mm, [&](auto M) -> int { return launch_sweep<decltype(M)>(plan, a, sh, st); });   // warm
+        rc = sweep_once();   // warm
         if (!rc) {
             (void)hipEventRecord(e0, st);
             for (int i = 0; i < iters && !rc; ++i)
-                rc = dispatch_model(mm, [&](auto M) -> int { return launch_sweep<decltype(M)>(plan, a, sh, st); });
+                rc = sweep_once();
             (void)hipEventRecord(e1, st);
             hipError_t e = hipEventSynchronize(e1);
             float ms = 0.f;
@@ -1236,13 +1245,11 @@ int obe_utility_argmax(const double* d_yvar, int32_t n_channels, int64_t n_setti
     UtilArgs ua;
     if (int rc = make_util_args(ua, d_noise_var, noise_ld, d_cost, cost_scalar, 0, 0)) return rc;
     const int nb = stream_blocks(n_settings, kBlock);
+    BestWords out(h_best, h_best_idx, nullptr);
+    const HostResult hr = out.arm(result_tail(d_ws, ws_bytes, sweep_ws_bytes(0, 0, kMaxBlocks, 0)));
     utility_kernel<<<nb, kBlock, 0, st>>>(d_yvar, n_channels, n_settings, ua, d_utility, w.bv, w.bi);
     OBE_CHECK_LAUNCH("utility_kernel");
-    HostResult hr = host_result(h_best, h_best_idx, nullptr);
-    hr.tail = result_tail(d_ws, ws_bytes, sweep_ws_bytes(0, 0, kMaxBlocks, 0));
-    argmax_fold<<<1, kBlock, 0, st>>>(w.bv, w.bi, nb, nullptr, w.out_v, w.out_i, hr);
-    OBE_CHECK_LAUNCH("argmax_fold");
-    return read_best(w, h_best, h_best_idx, st, nullptr, hr);
+    return fold_best(w, nb, hr, out, st);
 }
 
 int obe_argmax(const double* d_v, int64_t n, double* h_best, int64_t* h_best_idx, void* d_ws, int64_t ws_bytes,
@@ -1252,13 +1259,11 @@ int obe_argmax(const double* d_v, int64_t n, double* h_best, int64_t* h_best_idx
     if (int rc = carve_sweep_ws(d_ws, ws_bytes, 0, 0, w)) return rc;
     hipStream_t st = as_stream(stream);
     const int nb = stream_blocks(n, kBlock);
+    BestWords out(h_best, h_best_idx, nullptr);
+    const HostResult hr = out.arm(result_tail(d_ws, ws_bytes, sweep_ws_bytes(0, 0, kMaxBlocks, 0)));
     argmax_kernel<<<nb, kBlock, 0, st>>>(d_v, n, w.bv, w.bi);
     OBE_CHECK_LAUNCH("argmax_kernel");
-    HostResult hr = host_result(h_best, h_best_idx, nullptr);
-    hr.tail = result_tail(d_ws, ws_bytes, sweep_ws_bytes(0, 0, kMaxBlocks, 0));
-    argmax_fold<<<1, kBlock, 0, st>>>(w.bv, w.bi, nb, nullptr, w.out_v, w.out_i, hr);
-    OBE_CHECK_LAUNCH("argmax_fold");
-    return read_best(w, h_best, h_best_idx, st, nullptr, hr);
+    return fold_best(w, nb, hr, out, st);
 }
 
 }  // extern "C"

@@ -166,9 +166,8 @@ bool strict_sums_on();           // obe_strict_sums: the calling thread's unfuse
 int finish_update(const UpdateWs& w, int nb, int64_t n, double* d_weights, double* h_out, hipStream_t st);
 // pass B fused with the first moments (normalize_moments_kernel<d, FOLD>) and, without an arrival counter, the
 // separate fold launch: everything of obe_bayes_update_model_moments behind pass A
-int launch_normalize_moments(int d, const UpdateWs& w, int nb, int nm, const double* d_particles, int64_t ld_p,
-                             int64_t n_particles, double* d_weights, const UpdateFold& fold, double* d_moments, double* hv,
-                             hipStream_t st);
+int launch_normalize_moments(int d, const UpdateWs& w, int nb, const double* d_particles, int64_t ld_p,
+                             int64_t n_particles, double* d_weights, const UpdateFold& fold, hipStream_t st);
 // the model-independent launches of a sweep batch (obe_bayes_update_sweep): before the first point, behind every
 // point's pass A, behind the last point
 int launch_sweep_reset(const UpdateWs& w, hipStream_t st);

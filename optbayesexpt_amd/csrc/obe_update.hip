@@ -75,6 +75,42 @@ __global__ __launch_bounds__(kBlock) void eval_settings_kernel(obe_model m, Para
     }
 }
 
+// What the three model-update entry points share: prepare() = everything that can refuse the call, then pass A.
+// Pass A multiplies the weights by the likelihood in place: a refusal after it would leave them half updated, and a
+// caller that then falls back to another form would apply the likelihood twice — so prepare() comes before any launch.
+struct ModelUpdate {
+    obe_model mm;
+    LikArgs la;
+    UpdateWs w;
+    int nb;
+    // (with_moments: the partials of the fused first moments are carved too — mm.n_params of them, 1..OBE_FAST_DIMS)
+    int prepare(const obe_model* m, const double* h_y_meas, const double* h_sigma, const int32_t* h_noise_rows,
+                int32_t n_lik_channels, double choke, int64_t n_particles, void* d_ws, int64_t ws_bytes, bool with_moments) {
+        mm = *m;
+        if (int rc = obe_model_validate(&mm)) return rc;
+        if (n_lik_channels > mm.n_channels) return bad_arg("n_lik_channels exceeds model channels");
+        if (with_moments && (mm.n_params < 1 || mm.n_params > kFastDims))
+            return bad_arg("obe_bayes_update_model_moments: n_params must be 1..16 (OBE_FAST_DIMS)");
+        if (int rc = fill_lik_args(la, h_y_meas, h_sigma, h_noise_rows, n_lik_channels, choke, mm.n_params)) return rc;
+        if (int rc = carve_update_ws(d_ws, ws_bytes, w, with_moments ? mm.n_params : 0)) return rc;
+        nb = update_blocks(n_particles);
+        return 0;
+    }
+    // h_setting: this point's setting, mm.n_setdims values (NULL: zeros)
+    int pass_a(const double* h_setting, const double* d_particles, int64_t ld_p, int64_t n_particles, double* d_weights,
+               const SweepCtl& ctl, hipStream_t st) const {
+        SettingArg sa{};
+        for (int k = 0; k < mm.n_setdims; ++k) sa.x[k] = h_setting ? h_setting[k] : 0.0;
+        return dispatch_model(mm, [&](auto M) -> int {
+            using Model = decltype(M);
+            update_model_kernel<Model><<<nb, kBlock, 0, st>>>(mm, sa, la, d_particles, ld_p, n_particles, d_weights, w.pa,
+                                                              ctl);
+            OBE_CHECK_LAUNCH("update_model_kernel");
+            return 0;
+        });
+    }
+};
+
 }  // namespace obe
 
 using namespace obe;
@@ -86,26 +122,12 @@ int obe_bayes_update_model(const obe_model* m, const double* d_particles, int64_
                            const double* h_sigma, const int32_t* h_noise_rows, int32_t n_lik_channels,
                            double choke, void* d_ws, int64_t ws_bytes, double* h_out, void* stream) {
     if (!m || !d_particles || !d_weights || n_particles <= 0) return bad_arg("obe_bayes_update_model: bad pointer/size");
-    obe_model mm = *m;
-    if (int rc = obe_model_validate(&mm)) return rc;
-    if (n_lik_channels > mm.n_channels) return bad_arg("n_lik_channels exceeds model channels");
-    LikArgs la;
-    if (int rc = fill_lik_args(la, h_y_meas, h_sigma, h_noise_rows, n_lik_channels, choke, mm.n_params)) return rc;
-    UpdateWs w;
-    if (int rc = carve_update_ws(d_ws, ws_bytes, w)) return rc;
-    SettingArg sa{};
-    for (int k = 0; k < mm.n_setdims; ++k) sa.x[k] = h_setting ? h_setting[k] : 0.0;
+    ModelUpdate u;
+    if (int rc = u.prepare(m, h_y_meas, h_sigma, h_noise_rows, n_lik_channels, choke, n_particles, d_ws, ws_bytes, false))
+        return rc;
     hipStream_t st = as_stream(stream);
-    const int nb = update_blocks(n_particles);
-    int rc = dispatch_model(mm, [&](auto M) -> int {
-        using Model = decltype(M);
-        update_model_kernel<Model><<<nb, kBlock, 0, st>>>(mm, sa, la, d_particles, ld_p, n_particles, d_weights, w.pa,
-                                                          SweepCtl{});
-        OBE_CHECK_LAUNCH("update_model_kernel");
-        return 0;
-    });
-    if (rc) return rc;
-    return finish_update(w, nb, n_particles, d_weights, h_out, st);
+    if (int rc = u.pass_a(h_setting, d_particles, ld_p, n_particles, d_weights, SweepCtl{}, st)) return rc;
+    return finish_update(u.w, u.nb, n_particles, d_weights, h_out, st);
 }
 
 static int update_model_moments(const obe_model* m, const double* d_particles, int64_t ld_p, int64_t n_particles,
@@ -115,52 +137,29 @@ static int update_model_moments(const obe_model* m, const double* d_particles, i
                                 void* stream, bool enqueue_only, int32_t auto_resample, double resample_threshold) {
     if (!m || !d_particles || !d_weights || !d_moments || n_particles <= 0)
         return bad_arg("obe_bayes_update_model_moments: bad pointer/size");
-    obe_model mm = *m;
-    if (int rc = obe_model_validate(&mm)) return rc;
-    if (n_lik_channels > mm.n_channels) return bad_arg("n_lik_channels exceeds model channels");
-    const int d = mm.n_params;
-    if (d < 1 || d > kFastDims) return bad_arg("obe_bayes_update_model_moments: n_params must be 1..16 (OBE_FAST_DIMS)");
-    LikArgs la;
-    if (int rc = fill_lik_args(la, h_y_meas, h_sigma, h_noise_rows, n_lik_channels, choke, mm.n_params)) return rc;
-    UpdateWs w;
-    if (int rc = carve_update_ws(d_ws, ws_bytes, w, d)) return rc;
-    SettingArg sa{};
-    for (int k = 0; k < mm.n_setdims; ++k) sa.x[k] = h_setting ? h_setting[k] : 0.0;
+    ModelUpdate u;
+    if (int rc = u.prepare(m, h_y_meas, h_sigma, h_noise_rows, n_lik_channels, choke, n_particles, d_ws, ws_bytes, true))
+        return rc;
+    const int d = u.mm.n_params;
     hipStream_t st = as_stream(stream);
-    const int nb = update_blocks(n_particles);
-    // Everything that can refuse the call is checked BEFORE the first launch (pass A multiplies the weights by
-    // the likelihood in place: a refusal after it would leave them half updated, and a caller that then falls
-    // back to the synchronous form would apply the likelihood twice).
-    double* hv = static_cast<double*>(device_view_of_host(h_out));
-    const int64_t n_words = 2 + 2 + 4 * (int64_t)d + (enqueue_only ? 1 : 0);
+    // [0] sum t, [1] sum w'^2, [2..) the K3 block's first moments, (enqueue form) the resample decision
+    HostWords out(h_out, 2 + 2 + 4 * (int64_t)d + (enqueue_only ? 1 : 0));
+    double* hv = out.view<double>();
     if (enqueue_only && !hv) return bad_arg("obe_bayes_update_model_moments_enqueue: h_out must be page-locked");
     // the fold rides in the normalisation launch (its last workgroup to arrive) unless there is no counter for this stream
     unsigned* counter = stream_control_words(st);
     if (enqueue_only && !counter) return bad_arg("obe_bayes_update_model_moments_enqueue: no control words for this stream");
     if (enqueue_only && ws_bytes < update_ws_bytes(d) + 16)
         return bad_arg("obe_bayes_update_model_moments_enqueue: the workspace needs 16 spare bytes at its end (OBE_WS_ABORT_WORD)");
-    const int nm = first_moment_blocks(n_particles, d);
-    if (hv) arm_host_words(h_out, n_words);      // every word of the result block is watched
-    const UpdateFold fold{counter, w.scalars, d_moments, hv, enqueue_only ? ws_abort_word(d_ws, ws_bytes) : nullptr,
+    out.arm();      // every word of the result block is watched
+    const UpdateFold fold{counter, u.w.scalars, d_moments, hv, enqueue_only ? ws_abort_word(d_ws, ws_bytes) : nullptr,
                           (double)n_particles, resample_threshold, auto_resample};
-    int rc = dispatch_model(mm, [&](auto M) -> int {
-        using Model = decltype(M);
-        update_model_kernel<Model><<<nb, kBlock, 0, st>>>(mm, sa, la, d_particles, ld_p, n_particles, d_weights, w.pa,
-                                                          SweepCtl{});
-        OBE_CHECK_LAUNCH("update_model_kernel");
-        return 0;
-    });
-    if (rc) return rc;
-    if (int rc2 = launch_normalize_moments(d, w, nb, nm, d_particles, ld_p, n_particles, d_weights, fold, d_moments, hv, st))
-        return rc2;
-    if (enqueue_only) return 0;
-    if (h_out) {
-        if (hv) return wait_host_words(h_out, n_words, st);
-        OBE_HIP_TRY(hipMemcpyAsync(h_out, w.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-        OBE_HIP_TRY(hipMemcpyAsync(h_out + 2, d_moments, (2 + 4 * (int64_t)d) * sizeof(double), hipMemcpyDeviceToHost, st));
-        OBE_HIP_TRY(hipStreamSynchronize(st));
-    }
-    return 0;
+    if (int rc = u.pass_a(h_setting, d_particles, ld_p, n_particles, d_weights, SweepCtl{}, st)) return rc;
+    if (int rc = launch_normalize_moments(d, u.w, u.nb, d_particles, ld_p, n_particles, d_weights, fold, st)) return rc;
+    if (enqueue_only) return 0;      // armed, not waited for: the caller watches
+    if (int rc = out.copy(0, 2, u.w.scalars, st)) return rc;
+    if (int rc = out.copy(2, 2 + 4 * (int64_t)d, d_moments, st)) return rc;
+    return out.wait(st);
 }
 
 int obe_bayes_update_model_moments(const obe_model* m, const double* d_particles, int64_t ld_p, int64_t n_particles,
@@ -192,37 +191,25 @@ int obe_bayes_update_sweep(const obe_model* m, const double* d_particles, int64_
                            void* d_ws, int64_t ws_bytes, double* h_out, void* stream) {
     if (!m || !d_particles || !d_weights || n_particles <= 0 || n_points <= 0 || !h_y_meas || !h_out)
         return bad_arg("obe_bayes_update_sweep: bad pointer/size");
-    obe_model mm = *m;
-    if (int rc = obe_model_validate(&mm)) return rc;
-    if (n_lik_channels > mm.n_channels) return bad_arg("n_lik_channels exceeds model channels");
-    UpdateWs w;
-    if (int rc = carve_update_ws(d_ws, ws_bytes, w)) return rc;
+    ModelUpdate u;
+    if (int rc = u.prepare(m, h_y_meas, h_sigma, h_noise_rows, n_lik_channels, choke, n_particles, d_ws, ws_bytes, false))
+        return rc;
     hipStream_t st = as_stream(stream);
-    const int nb = update_blocks(n_particles);
-    if (int rc = launch_sweep_reset(w, st)) return rc;
+    if (int rc = launch_sweep_reset(u.w, st)) return rc;
     // (obe_strict_sums: every point's sum t and sum w'^2 in np.sum's order, as the point-by-point calls form them)
     const bool strict = strict_sums_on();
-    const int nfold = strict ? 1 : nb;
+    const int nfold = strict ? 1 : u.nb;
     for (int64_t k = 0; k < n_points; ++k) {
-        LikArgs la;
-        if (int rc = fill_lik_args(la, h_y_meas + k * OBE_MAX_CHANNELS, h_sigma, h_noise_rows, n_lik_channels, choke,
-                                   mm.n_params))
+        // (the points differ in their measurement and setting only: what could refuse was checked with point 0's)
+        for (int c = 0; c < u.la.n_ch; ++c) u.la.y_meas[c] = h_y_meas[k * OBE_MAX_CHANNELS + c];
+        const SweepCtl ctl{u.w.scalars, u.w.pa, u.w.pb, nfold, (int)k, auto_resample, resample_threshold, (double)n_particles};
+        if (int rc = u.pass_a(h_settings ? h_settings + k * OBE_MAX_SETDIMS : nullptr, d_particles, ld_p, n_particles,
+                              d_weights, ctl, st))
             return rc;
-        SettingArg sa{};
-        for (int j = 0; j < mm.n_setdims; ++j) sa.x[j] = h_settings ? h_settings[k * OBE_MAX_SETDIMS + j] : 0.0;
-        const SweepCtl ctl{w.scalars, w.pa, w.pb, nfold, (int)k, auto_resample, resample_threshold, (double)n_particles};
-        int rc = dispatch_model(mm, [&](auto M) -> int {
-            using Model = decltype(M);
-            update_model_kernel<Model><<<nb, kBlock, 0, st>>>(mm, sa, la, d_particles, ld_p, n_particles, d_weights,
-                                                              w.pa, ctl);
-            OBE_CHECK_LAUNCH("update_model_kernel");
-            return 0;
-        });
-        if (rc) return rc;
-        if (int rc2 = launch_sweep_point_tail(w, nb, nfold, n_particles, d_weights, strict, st)) return rc2;
+        if (int rc = launch_sweep_point_tail(u.w, u.nb, nfold, n_particles, d_weights, strict, st)) return rc;
     }
-    if (int rc = launch_sweep_end(w, nfold, n_particles, auto_resample, resample_threshold, (int)n_points, st)) return rc;
-    OBE_HIP_TRY(hipMemcpyAsync(h_out, w.scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (int rc = launch_sweep_end(u.w, nfold, n_particles, auto_resample, resample_threshold, (int)n_points, st)) return rc;
+    OBE_HIP_TRY(hipMemcpyAsync(h_out, u.w.scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
     OBE_HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }

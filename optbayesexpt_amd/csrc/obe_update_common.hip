@@ -156,16 +156,12 @@ __global__ __launch_bounds__(kBlock) void fold2_kernel(const double* __restrict_
 
 // fold + delivery of {sum t, sum w'^2} to h_out: written by the kernel itself when h_out is page-locked
 static int fold2_to_host(const double* pa, const double* pb, int nb, double* scalars, double* h_out, hipStream_t st) {
-    double* hv = static_cast<double*>(device_view_of_host(h_out));
-    if (hv) arm_host_words(h_out, 2);
-    fold2_kernel<<<1, kBlock, 0, st>>>(pa, pb, nb, scalars, hv);
+    HostWords out(h_out, 2);
+    out.arm();
+    fold2_kernel<<<1, kBlock, 0, st>>>(pa, pb, nb, scalars, out.view<double>());
     OBE_CHECK_LAUNCH("fold2_kernel");
-    if (h_out) {
-        if (hv) return wait_host_words(h_out, 2, st);
-        OBE_HIP_TRY(hipMemcpyAsync(h_out, scalars, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-        OBE_HIP_TRY(hipStreamSynchronize(st));
-    }
-    return 0;
+    if (int rc = out.copy(0, 2, scalars, st)) return rc;
+    return out.wait(st);
 }
 
 // last launch of a sweep batch: fold the final point's partials and test it (unless an earlier
@@ -236,6 +232,16 @@ struct RowsArg {
     int n;
     int rows[OBE_MAX_DIMS];
 };
+// false: a row index outside [0, n_dims_limit) — the kernels index the cloud with these
+static bool make_rows_arg(RowsArg& ra, const int32_t* h_rows, int n_rows, int n_dims_limit) {
+    ra = RowsArg{};
+    ra.n = n_rows;
+    for (int k = 0; k < n_rows; ++k) {
+        if (h_rows[k] < 0 || h_rows[k] >= n_dims_limit) return false;
+        ra.rows[k] = h_rows[k];
+    }
+    return true;
+}
 
 __global__ __launch_bounds__(kBlock) void mask_kernel(RowsArg ra, const double* __restrict__ particles, int64_t ld,
                                                       int64_t n, double* __restrict__ weights,
@@ -559,29 +565,25 @@ int finish_update(const UpdateWs& w, int nb, int64_t n, double* d_weights, doubl
 }
 
 
-int launch_normalize_moments(int d, const UpdateWs& w, int nb, int nm, const double* d_particles, int64_t ld_p,
-                             int64_t n_particles, double* d_weights, const UpdateFold& fold, double* d_moments, double* hv,
-                             hipStream_t st) {
+int launch_normalize_moments(int d, const UpdateWs& w, int nb, const double* d_particles, int64_t ld_p,
+                             int64_t n_particles, double* d_weights, const UpdateFold& fold, hipStream_t st) {
     const bool counter = fold.counter != nullptr;
-#define OBE_UPD_MOM_CASE(DD)                                                                                           \
-    case DD:                                                                                                           \
-        if (counter)                                                                                                   \
-            normalize_moments_kernel<DD, true><<<nm, kMomThreads, 0, st>>>(w.pa, nb, d_particles, ld_p, n_particles,       \
-                                                                      d_weights, w.pb, w.mom, fold);                   \
-        else                                                                                                           \
-            normalize_moments_kernel<DD, false><<<nm, kMomThreads, 0, st>>>(w.pa, nb, d_particles, ld_p, n_particles,      \
-                                                                       d_weights, w.pb, w.mom, fold);                  \
-        break;
-    switch (d) {
-        OBE_UPD_MOM_CASE(1) OBE_UPD_MOM_CASE(2) OBE_UPD_MOM_CASE(3) OBE_UPD_MOM_CASE(4) OBE_UPD_MOM_CASE(5)
-        OBE_UPD_MOM_CASE(6) OBE_UPD_MOM_CASE(7) OBE_UPD_MOM_CASE(8) OBE_UPD_MOM_CASE(9) OBE_UPD_MOM_CASE(10)
-        OBE_UPD_MOM_CASE(11) OBE_UPD_MOM_CASE(12) OBE_UPD_MOM_CASE(13) OBE_UPD_MOM_CASE(14) OBE_UPD_MOM_CASE(15)
-        OBE_UPD_MOM_CASE(16)
-    }
-#undef OBE_UPD_MOM_CASE
-    OBE_CHECK_LAUNCH("normalize_moments_kernel");
+    const int nm = first_moment_blocks(n_particles, d);
+    if (int rc = dispatch_dims(d, "normalize_moments_kernel: no kernel for this n_dims", [&](auto D) -> int {
+            constexpr int DD = decltype(D)::value;
+            if (counter)
+                normalize_moments_kernel<DD, true><<<nm, kMomThreads, 0, st>>>(w.pa, nb, d_particles, ld_p, n_particles,
+                                                                               d_weights, w.pb, w.mom, fold);
+            else
+                normalize_moments_kernel<DD, false><<<nm, kMomThreads, 0, st>>>(w.pa, nb, d_particles, ld_p, n_particles,
+                                                                                d_weights, w.pb, w.mom, fold);
+            OBE_CHECK_LAUNCH("normalize_moments_kernel");
+            return 0;
+        }))
+        return rc;
     if (!counter) {
-        fold_update_moments_kernel<<<1, kFoldThreads, 0, st>>>(w.pa, nb, w.pb, nm, w.mom, d, w.scalars, d_moments, hv);
+        fold_update_moments_kernel<<<1, kFoldThreads, 0, st>>>(w.pa, nb, w.pb, nm, w.mom, d, w.scalars, fold.mom_out,
+                                                               fold.host_out);
         OBE_CHECK_LAUNCH("fold_update_moments_kernel");
     }
     return 0;
@@ -713,38 +715,46 @@ int obe_mask_nonpositive(const double* d_particles, int64_t ld_p, int64_t n_part
         return bad_arg("obe_mask_nonpositive: bad pointer/size");
     UpdateWs w;
     if (int rc = carve_update_ws(d_ws, ws_bytes, w)) return rc;
-    RowsArg ra{};
-    ra.n = n_rows;
-    for (int k = 0; k < n_rows; ++k) ra.rows[k] = h_rows[k];
+    RowsArg ra;
+    if (!make_rows_arg(ra, h_rows, n_rows, OBE_CLOUD_MAX_DIMS)) return bad_arg("obe_mask_nonpositive: row index out of range");
     hipStream_t st = as_stream(stream);
     const int nb = stream_blocks(n_particles, kBlock);
+    HostWords changed(h_changed, 1);
+    changed.arm();
     mask_kernel<<<nb, kBlock, 0, st>>>(ra, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
     OBE_CHECK_LAUNCH("mask_kernel");
     fold2_kernel<<<1, kBlock, 0, st>>>(w.pa, w.pb, nb, w.scalars, nullptr);
     OBE_CHECK_LAUNCH("fold2_kernel");
-    int64_t* hv = static_cast<int64_t*>(device_view_of_host(h_changed));
-    if (hv) arm_host_word(h_changed);
-    mask_renorm_kernel<<<nb, kBlock, 0, st>>>(w.scalars, n_particles, d_weights, hv);
+    mask_renorm_kernel<<<nb, kBlock, 0, st>>>(w.scalars, n_particles, d_weights, changed.view<int64_t>());
     OBE_CHECK_LAUNCH("mask_renorm_kernel");
-    if (h_changed) {
-        if (hv) {
-            // (the count is the kernel's first store; the renormalisation that may still be running is ordered
-            // before everything the caller enqueues next)
-            if (int rc = wait_host_word(h_changed, st)) return rc;
-        } else {
-            double sc[2];
-            OBE_HIP_TRY(hipMemcpyAsync(sc, w.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-            OBE_HIP_TRY(hipStreamSynchronize(st));
-            *h_changed = (int64_t)sc[1];
-        }
-    }
+    // (the count is the kernel's first store; the renormalisation that may still be running is ordered
+    // before everything the caller enqueues next)
+    if (!h_changed || changed.view<int64_t>()) return changed.wait(st);
+    double sc[2];       // (pageable: the count is a double on the device, converted here)
+    OBE_HIP_TRY(hipMemcpyAsync(sc, w.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    OBE_HIP_TRY(hipStreamSynchronize(st));
+    *h_changed = (int64_t)sc[1];
     return 0;
 }
 
+// the second half: renormalise if anything was zeroed + the first moments of the constrained cloud, from the partial
+// sums {sum w, count} that mask_kernel — or the masked gather of a resample (obe_resample_particles_aos_masked) — left
 static int mask_renorm_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
                                const double* psum, const double* pcount, int nb, double* d_weights, double* d_moments,
-                               double* h_moments, double* hm, int64_t* h_changed, int64_t* hc, unsigned* counter,
-                               double* partials_mom, hipStream_t st);
+                               HostWords& moments, HostWords& changed, unsigned* counter, double* partials_mom,
+                               hipStream_t st) {
+    // armed, not waited for: the caller watches the count and the K3 block
+    changed.arm();
+    moments.arm();
+    const MaskFold mf{counter, d_moments, moments.view<double>(), changed.view<int64_t>()};
+    const int nm = first_moment_blocks(n_particles, n_dims);
+    return dispatch_dims(n_dims, "mask_renorm_moments_kernel: no kernel for this n_dims", [&](auto D) -> int {
+        mask_renorm_moments_kernel<decltype(D)::value><<<nm, kMomThreads, 0, st>>>(psum, pcount, nb, d_particles, ld_p,
+                                                                                   n_particles, d_weights, partials_mom, mf);
+        OBE_CHECK_LAUNCH("mask_renorm_moments_kernel");
+        return 0;
+    });
+}
 
 int obe_mask_renorm_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
                             const double* d_mask_partials, double* d_weights, double* d_moments, double* h_moments,
@@ -754,17 +764,16 @@ int obe_mask_renorm_moments(const double* d_particles, int64_t ld_p, int32_t n_d
     if (n_dims < 1 || n_dims > kFastDims) return bad_arg("obe_mask_renorm_moments: n_dims must be 1..16 (OBE_FAST_DIMS)");
     hipStream_t st = as_stream(stream);
     unsigned* counter = stream_control_words(st);
-    int64_t* hc = static_cast<int64_t*>(device_view_of_host(h_changed));
-    double* hm = static_cast<double*>(device_view_of_host(h_moments));
+    HostWords changed(h_changed, 1), moments(h_moments, 2 + 4 * (int64_t)n_dims);
     // (refused before any launch: the caller then runs obe_mask_nonpositive_moments(), which on weights the gather
     // has already masked finds the same particles and leaves the same bits)
-    if (!counter || (h_changed && !hc) || (h_moments && !hm))
+    if (!counter || (h_changed && !changed.view<void>()) || (h_moments && !moments.view<void>()))
         return bad_arg("obe_mask_renorm_moments: needs an arrival counter for the stream and page-locked host outputs");
     UpdateWs w;
     if (int rc = carve_update_ws(d_ws, ws_bytes, w, n_dims)) return rc;
     return mask_renorm_moments(d_particles, ld_p, n_dims, n_particles, d_mask_partials, d_mask_partials + kMaxBlocks,
-                               stream_blocks(n_particles, kBlock), d_weights, d_moments, h_moments, hm, h_changed, hc,
-                               counter, w.mom, st);
+                               stream_blocks(n_particles, kBlock), d_weights, d_moments, moments, changed, counter, w.mom,
+                               st);
 }
 
 int obe_mask_nonpositive_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
@@ -775,9 +784,8 @@ int obe_mask_nonpositive_moments(const double* d_particles, int64_t ld_p, int32_
     if (n_dims < 1 || n_dims > OBE_CLOUD_MAX_DIMS) return bad_arg("obe_mask_nonpositive_moments: n_dims must be 1..1024");
     hipStream_t st = as_stream(stream);
     unsigned* counter = stream_control_words(st);
-    int64_t* hc = static_cast<int64_t*>(device_view_of_host(h_changed));
-    double* hm = static_cast<double*>(device_view_of_host(h_moments));
-    if (!counter || (h_changed && !hc) || (h_moments && !hm) || n_dims > kFastDims) {
+    HostWords changed(h_changed, 1), moments(h_moments, 2 + 4 * (int64_t)n_dims);
+    if (!counter || (h_changed && !changed.view<void>()) || (h_moments && !moments.view<void>()) || n_dims > kFastDims) {
         // no arrival counter for this stream / pageable host buffers / a cloud wider than the fused kernels are
         // compiled for: the two separate calls (synchronous)
         if (int rc = obe_mask_nonpositive(d_particles, ld_p, n_particles, h_rows, n_rows, d_weights, h_changed, d_ws,
@@ -788,43 +796,13 @@ int obe_mask_nonpositive_moments(const double* d_particles, int64_t ld_p, int32_
     }
     UpdateWs w;
     if (int rc = carve_update_ws(d_ws, ws_bytes, w, n_dims)) return rc;
-    RowsArg ra{};
-    ra.n = n_rows;
-    for (int k = 0; k < n_rows; ++k) {
-        if (h_rows[k] < 0 || h_rows[k] >= n_dims) return bad_arg("obe_mask_nonpositive_moments: row index out of range");
-        ra.rows[k] = h_rows[k];
-    }
+    RowsArg ra;
+    if (!make_rows_arg(ra, h_rows, n_rows, n_dims)) return bad_arg("obe_mask_nonpositive_moments: row index out of range");
     const int nb = stream_blocks(n_particles, kBlock);
     mask_kernel<<<nb, kBlock, 0, st>>>(ra, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
     OBE_CHECK_LAUNCH("mask_kernel");
-    return mask_renorm_moments(d_particles, ld_p, n_dims, n_particles, w.pa, w.pb, nb, d_weights, d_moments, h_moments,
-                               hm, h_changed, hc, counter, w.mom, st);
-}
-
-// the second half: renormalise if anything was zeroed + the first moments of the constrained cloud, from the partial
-// sums {sum w, count} that mask_kernel — or the masked gather of a resample (obe_resample_particles_aos_masked) — left
-static int mask_renorm_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
-                               const double* psum, const double* pcount, int nb, double* d_weights, double* d_moments,
-                               double* h_moments, double* hm, int64_t* h_changed, int64_t* hc, unsigned* counter,
-                               double* partials_mom, hipStream_t st) {
-    if (hc) arm_host_word(h_changed);
-    if (hm) arm_host_words(h_moments, 2 + 4 * (int64_t)n_dims);
-    const MaskFold mf{counter, d_moments, hm, hc};
-    const int nm = first_moment_blocks(n_particles, n_dims);
-#define OBE_MASK_MOM_CASE(DD)                                                                                       \
-    case DD:                                                                                                        \
-        mask_renorm_moments_kernel<DD><<<nm, kMomThreads, 0, st>>>(psum, pcount, nb, d_particles, ld_p, n_particles,    \
-                                                              d_weights, partials_mom, mf);                         \
-        break;
-    switch (n_dims) {
-        OBE_MASK_MOM_CASE(1) OBE_MASK_MOM_CASE(2) OBE_MASK_MOM_CASE(3) OBE_MASK_MOM_CASE(4) OBE_MASK_MOM_CASE(5)
-        OBE_MASK_MOM_CASE(6) OBE_MASK_MOM_CASE(7) OBE_MASK_MOM_CASE(8) OBE_MASK_MOM_CASE(9) OBE_MASK_MOM_CASE(10)
-        OBE_MASK_MOM_CASE(11) OBE_MASK_MOM_CASE(12) OBE_MASK_MOM_CASE(13) OBE_MASK_MOM_CASE(14)
-        OBE_MASK_MOM_CASE(15) OBE_MASK_MOM_CASE(16)
-    }
-#undef OBE_MASK_MOM_CASE
-    OBE_CHECK_LAUNCH("mask_renorm_moments_kernel");
-    return 0;
+    return mask_renorm_moments(d_particles, ld_p, n_dims, n_particles, w.pa, w.pb, nb, d_weights, d_moments, moments,
+                               changed, counter, w.mom, st);
 }
 
 int obe_power_normalize(const double* d_u, int64_t n, double exponent, double* d_p_out, void* d_ws,
@@ -845,12 +823,8 @@ int obe_noise_var_from_moments(const double* d_moments, int32_t n_dims, const in
                                double* d_out, void* stream) {
     if (!d_moments || !h_rows || !d_out || n_rows < 1 || n_rows > OBE_MAX_DIMS)
         return bad_arg("obe_noise_var_from_moments: bad pointer/size");
-    RowsArg ra{};
-    ra.n = n_rows;
-    for (int k = 0; k < n_rows; ++k) {
-        if (h_rows[k] < 0 || h_rows[k] >= n_dims) return bad_arg("noise row index out of range");
-        ra.rows[k] = h_rows[k];
-    }
+    RowsArg ra;
+    if (!make_rows_arg(ra, h_rows, n_rows, n_dims)) return bad_arg("noise row index out of range");
     noise_var_kernel<<<1, kWave, 0, as_stream(stream)>>>(d_moments, n_dims, ra, d_out);
     OBE_CHECK_LAUNCH("noise_var_kernel");
     return 0;
