@@ -562,6 +562,48 @@ OBE_API int obe_ziggurat_normal(const uint64_t* d_raw, int64_t n_raw, int64_t of
                         void* d_ws, int64_t ws_bytes, void* stream);
 OBE_API int obe_ziggurat_check(int64_t consumed, int64_t found, int64_t n, int64_t n_raw, int64_t offset);
 
+/* ---- posterior summaries: marginals, joint histograms, quantiles (extension) ----
+ * What the reference's users read from the whole cloud after a cycle — the weighted scatter plots of
+ * demos/pipulse/pipulse.py:159 and demos/find_peak/seqLor_pdfevolve.py:156-163, the histograms quoted in
+ * docs/manual_demos.rst, the 95 % credible intervals tests/test_gpu_trajectories.py:186 argues with —, next to the
+ * mean / covariance / std of particlepdf.py:173-214, without copying the cloud to the host.
+ * Fixed point: every weight enters as the integer Q_i = rint(w_i 2^k), NaN and negative weights as 0, with
+ * k = 62 - e for the smallest e with sum(w) <= 2^e (1 + 2^-20) (k = 62 for normalised weights; sum(Q) < 2^63).  Bins
+ * and cumulative sums are unsigned 64-bit integers, so every result is the same bits from run to run and under any
+ * permutation of the cloud; a mass is Q_bin 2^-k, within 4 eps mass + n_bin 2^-62 sum(w) of the exact sum.  Weights
+ * must be finite.  All results land in the caller's DEVICE buffers, nothing is waited for.  h_rows: the n_rows
+ * parameter rows (each in [0, n_dims)) the call serves; d_ws: obe_posterior_workspace_bytes(n_particles, n_rows,
+ * bins per row — bins_x * bins_y with n_rows = 1 for the joint form —, n_q) bytes, a buffer of its own (the calls
+ * use its head, where obe_workspace_bytes()'s workspace keeps other calls' results). */
+OBE_API int64_t obe_posterior_workspace_bytes(int64_t n_particles, int32_t n_rows, int64_t n_bins, int32_t n_q);
+/* d_minmax[2 r], d_minmax[2 r + 1] = np.min / np.max of row h_rows[r] over ALL particles (both NaN if the row holds
+ * one; -0.0 reported as 0.0): the automatic range of np.histogram_bin_edges. */
+OBE_API int obe_minmax_rows(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                    const int32_t* h_rows, int32_t n_rows, double* d_minmax, void* d_ws, int64_t ws_bytes,
+                    void* stream);
+/* d_mass (n_rows, n_bins) = np.histogram(particles[h_rows[r]], weights = w) over the caller's edges d_edges
+ * (n_rows, n_bins + 1), ascending.  Membership is decided by the edge array alone: bin k holds
+ * edges[k] <= x < edges[k + 1], the last bin also x == edges[n_bins]; values outside and NaN are not counted.  Up to
+ * 4096 bins per row the bins of as many rows as fit are kept in 32 KiB of LDS per workgroup (one pass over the cloud
+ * per group of rows); beyond, up to 2^24 bins per row, the adds go to global memory.  More is refused (-1). */
+OBE_API int obe_weighted_histogram(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                           const double* d_weights, const int32_t* h_rows, int32_t n_rows, const double* d_edges,
+                           int64_t n_bins, double* d_mass, void* d_ws, int64_t ws_bytes, void* stream);
+/* d_mass (n_bins_x, n_bins_y) row-major = np.histogram2d(particles[row_x], particles[row_y], weights = w) over the
+ * caller's edges, same membership rule per axis.  n_bins_x * n_bins_y <= 4096 in LDS, <= 2^24 at all. */
+OBE_API int obe_weighted_histogram2d(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                             const double* d_weights, int32_t row_x, int32_t row_y, const double* d_xedges,
+                             int64_t n_bins_x, const double* d_yedges, int64_t n_bins_y, double* d_mass,
+                             void* d_ws, int64_t ws_bytes, void* stream);
+/* d_quantiles (n_rows, n_q) = np.quantile(particles[h_rows[r]], h_q, weights = w, method = "inverted_cdf"): the
+ * smallest particle value x with sum_{x_i <= x} Q_i >= max(1, ceil(q sum Q)), in np.sort's order (-0.0 == 0.0, NaN
+ * last; NaN if every weight is zero).  A radix select on the 64-bit order-preserving key: 8 passes of 8 bits, each a
+ * weighted digit histogram of the keys that carry the digits chosen so far, the digit chosen by a small kernel in
+ * between; one call serves every row and up to 16 values of q (each in [0, 1]) with the same 8 passes. */
+OBE_API int obe_weighted_quantiles(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                           const double* d_weights, const int32_t* h_rows, int32_t n_rows, const double* h_q,
+                           int32_t n_q, double* d_quantiles, void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _devrng, _lib
+from . import _devrng, _lib, _posterior
 from ._mirror import Mirror
 
 _P = ctypes.c_void_p
@@ -269,6 +269,41 @@ class ParticlePDF:
     def std(self):
         """Per-parameter standard deviation (particlepdf.py:200-214)."""
         return self._moments(False)[self._layout.std].copy()
+
+    # ------------------------------------------------ marginals, quantiles, intervals
+    # (extension: the reference reads these from the whole cloud on the host — demos/pipulse/pipulse.py:159,
+    # demos/find_peak/seqLor_pdfevolve.py:156-163.  They describe the cloud as it stands, run on the device
+    # (_posterior.py, csrc/obe_posterior.hip) and change nothing: no random number, no version, no cache, and the
+    # host mirrors of the cloud and the weights are not materialised.  Weights enter in fixed point, so every result
+    # is the same bits from run to run and under any permutation of the cloud.  NaN weights count as zero (the rule
+    # of bayesian_update's nan_to_num); negative or infinite weights are not supported.)
+    def marginal_histogram(self, dims=None, bins=64, range=None, density=False):
+        """Weighted histogram of each parameter row in ``dims`` (``None``: every row): ``(mass, edges)`` of shapes
+        ``(n_rows, bins)`` and ``(n_rows, bins + 1)``, per row what ``np.histogram(particles[r], bins, range_r,
+        weights=particle_weights, density=density)`` returns.  ``range``: ``None`` (each row's min and max over all
+        particles), one ``(min, max)`` for every row, or one per row.  Negative weights are not supported."""
+        return _posterior.marginal_histogram(self, dims, bins, range, density)
+
+    def joint_histogram(self, dim_x, dim_y, bins=64, range=None, density=False):
+        """Weighted two-dimensional histogram of rows ``dim_x`` and ``dim_y``: ``(mass, xedges, yedges)`` as
+        ``np.histogram2d(particles[dim_x], particles[dim_y], bins, range, weights=particle_weights,
+        density=density)``; ``bins`` an integer or a pair.  Negative weights are not supported."""
+        return _posterior.joint_histogram(self, dim_x, dim_y, bins, range, density)
+
+    def quantile(self, q, dims=None):
+        """Weighted quantiles per parameter row, shape ``(n_rows, n_q)`` (``(n_rows,)`` for a scalar ``q``):
+        ``np.quantile(particles[r], q, weights=particle_weights, method="inverted_cdf")`` — always a value some
+        particle holds; order as ``np.sort`` (-0.0 equals 0.0, NaN last).  Negative weights are not supported."""
+        return _posterior.quantile(self, q, dims)
+
+    def median(self, dims=None):
+        """``quantile(0.5, dims)``."""
+        return _posterior.quantile(self, 0.5, dims)
+
+    def credible_interval(self, level=0.95, dims=None):
+        """Equal-tailed credible interval per parameter row, shape ``(n_rows, 2)``:
+        ``quantile(((1 - level) / 2, 1 - (1 - level) / 2), dims)``."""
+        return _posterior.quantile(self, _posterior.interval_quantiles(level), dims)
 
     # ------------------------------------------------------------ Bayes update
     def bayesian_update(self, likelihood):
