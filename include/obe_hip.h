@@ -604,6 +604,35 @@ OBE_API int obe_weighted_quantiles(const double* d_particles, int64_t ld_p, int3
                            const double* d_weights, const int32_t* h_rows, int32_t n_rows, const double* h_q,
                            int32_t n_q, double* d_quantiles, void* d_ws, int64_t ws_bytes, void* stream);
 
+/* ---- posterior predictive summaries: mean, variance and quantiles of the model output (extension) ----
+ * The fitted curve with its uncertainty.  The reference's demos draw the model at the mean parameters as the "Est."
+ * curve (demos/line_plus_noise/line_plus_noise.py:138,181), a plug-in estimate without a band; the summaries of
+ * y_i = model(x_s; theta_i)[c] over the whole weighted cloud need n_settings x n_particles evaluations, which stay on
+ * the chip here.  y_i is what obe_eval_over_particles writes for the setting x_s (obe_base.py:298-320), bit for bit;
+ * d_settings (n_setdims, n_settings) with row stride ld_s holds POINTS, one per column.  NaN and negative weights
+ * count as zero, and a particle of zero weight contributes nothing whatever its y is.  All results land in the
+ * caller's DEVICE buffers, nothing is waited for.
+ * d_ws: obe_predictive_workspace_bytes(n_particles, n_settings, the model's channels, n_q —
+ * 0 for the moments —) bytes, a buffer of its own, as for the posterior summaries; the size does not shrink when an
+ * argument grows. */
+OBE_API int64_t obe_predictive_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels, int32_t n_q);
+/* d_mean, d_var (C, n_settings): mean = sum w y / sum w and var = sum w (y - mean)^2 / sum w, the weighted form of the
+ * np.average / variance the reference takes of its parameters (particlepdf.py:173-214), in two passes over the
+ * cloud (the second about the mean the first one found).  Partial sums are folded in a fixed order: the same bits
+ * from run to run.  sum w == 0 gives NaN. */
+OBE_API int obe_predictive_moments(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                           const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                           double* d_mean, double* d_var, void* d_ws, int64_t ws_bytes, void* stream);
+/* d_quantiles (n_q, C, n_settings) = np.quantile(y, h_q, weights = w, method = "inverted_cdf") per setting and channel,
+ * by obe_weighted_quantiles' rule and radix select (fixed-point weights, np.sort's order, the same bits under any
+ * permutation of the cloud): the model values of up to 64 (setting, channel) rows at a time are written to the
+ * workspace (64 x n_particles doubles of it) and selected from as from a cloud of rows.  1..16 values of q, each in
+ * [0, 1]. */
+OBE_API int obe_predictive_quantiles(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                             const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                             const double* h_q, int32_t n_q, double* d_quantiles, void* d_ws, int64_t ws_bytes,
+                             void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

@@ -1,0 +1,280 @@
+// K10 — posterior predictive summaries on the device: for every setting x_s and channel c the weighted mean, variance
+// and quantiles of y_i = model(x_s; theta_i)[c] over the whole cloud.  The settings x particles evaluations never leave
+// the chip: only the (C, n_settings) results are written.
+//
+// The model is evaluated with M::eval, the exact NumPy-order form, so every y is the bits obe_eval_over_particles
+// writes.  NaN and negative weights count as zero, and a particle of zero weight contributes nothing whatever its y is
+// (NaN and inf included).
+//   moments    lane <-> setting, the particle axis streamed (the same particle for all lanes: scalar loads), grid =
+//              setting tiles x particle chunks.  Two passes: sum w y, then sum w (y - mean)^2 about that mean; the
+//              chunk partials are folded in chunk order.  No atomics: the same bits from run to run.
+//   quantiles  the model values of a tile of (setting, channel) rows are written to the workspace once (lane <->
+//              particle), then obe_posterior.hip's radix select runs on that tile as on a cloud of rows: eight
+//              passes of select_pass_kernel / select_choose_kernel.  Integer sums: the same bits under any grid and
+//              any permutation of the cloud.  (A fused select that recomputed the key in every pass instead of
+//              loading it was built and measured: slower at both benchmark clouds)
+#include <algorithm>
+
+#include "obe_models.h"
+#include "obe_select.h"
+
+namespace obe {
+namespace {
+
+constexpr int kPredHeader = 8;                     // words: [0] sum w, [1] k (scale_kernel)
+constexpr int kPredHeadWords = kPredHeader + kPostPartials + kMaxQ;
+constexpr int kMomentWaves = 8192;                 // waves a moments pass aims at (32 per CU): chunks = this / setting tiles
+constexpr int kMomentMinChunk = 256;               // particles per chunk at least
+constexpr int kTileRows = 64;                      // (setting, channel) rows whose values are kept at a time: 64 x N_p doubles
+
+inline int64_t setting_tiles(int64_t n_settings) { return (n_settings + kWave - 1) / kWave; }
+inline int moment_chunks(int64_t n_particles, int64_t n_settings) {
+    const int64_t by_size = (n_particles + kMomentMinChunk - 1) / kMomentMinChunk;
+    const int64_t by_grid = std::max<int64_t>(1, kMomentWaves / setting_tiles(n_settings));
+    return (int)std::max<int64_t>(1, std::min(by_size, by_grid));
+}
+// chunks x padded settings <= kMomentWaves x 64 + the padded settings, whatever the cloud
+inline int64_t moment_words(int64_t n_settings, int n_channels) {
+    return ((int64_t)kMomentWaves + setting_tiles(n_settings)) * kWave * n_channels;
+}
+inline int64_t tile_rows_bound(int64_t n_settings, int n_channels) { return std::min<int64_t>(n_settings * n_channels, kTileRows); }
+// the tile's values, its digit histograms, prefixes, targets and results, its row list
+inline int64_t select_words(int64_t n_particles, int64_t n_settings, int n_channels, int n_q) {
+    const int64_t rows = tile_rows_bound(n_settings, n_channels);
+    return rows * n_particles + rows * n_q * (int64_t)(kDigits + 3) + (rows + 1) / 2;
+}
+
+struct PredWs {
+    u64* hdr;
+    double* partials;
+    double* q;
+    u64* body;
+};
+inline PredWs carve(void* d_ws) {
+    u64* base = static_cast<u64*>(d_ws);
+    return PredWs{base, reinterpret_cast<double*>(base + kPredHeader),
+                  reinterpret_cast<double*>(base + kPredHeader + kPostPartials), base + kPredHeadWords};
+}
+
+// ---- moments.  One wave per workgroup; lane = one setting, the chunk's particles one after the other.
+// CENTRED: sum w (y - centre)^2 about centre (C, n_settings); else sum w y.
+template <class M, bool CENTRED>
+__global__ __launch_bounds__(kWave) void predict_moment_kernel(obe_model m, const double* __restrict__ settings,
+                                                               int64_t ld_s, int64_t n_s,
+                                                               const double* __restrict__ particles, int64_t ld_p,
+                                                               int64_t n, const double* __restrict__ w,
+                                                               int64_t chunk_len, const double* __restrict__ centre,
+                                                               double* __restrict__ partials) {
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_s ? s : n_s - 1;                    // (the padding lanes repeat the last setting)
+    double x[M::NS], c0[M::NC], acc[M::NC];
+#pragma unroll
+    for (int k = 0; k < M::NS; ++k) x[k] = settings[(int64_t)k * ld_s + sc];
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        c0[c] = CENTRED ? centre[(int64_t)c * n_s + sc] : 0.0;
+        acc[c] = 0.0;
+    }
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p] and the particle are the same for all lanes)
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        double y[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            if (CENTRED) {
+                const double d = y[c] - c0[c];
+                acc[c] += wp * (d * d);
+            } else {
+                acc[c] += wp * y[c];
+            }
+        }
+    }
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) partials[((int64_t)blockIdx.y * M::NC + c) * n_pad + s] = acc[c];
+}
+
+// out (C, n_settings) = (the chunk partials, added in chunk order) / sum w
+__global__ __launch_bounds__(kBlock) void predict_fold_kernel(const double* __restrict__ partials, int chunks, int n_channels,
+                                                              int64_t n_pad, int64_t n_s, const u64* __restrict__ hdr,
+                                                              double* __restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_s) return;
+    const double sw = __longlong_as_double((long long)hdr[0]);
+    for (int c = 0; c < n_channels; ++c) {
+        double acc = 0.0;
+        for (int j = 0; j < chunks; ++j) acc += partials[((int64_t)j * n_channels + c) * n_pad + s];
+        out[(int64_t)c * n_s + s] = acc / sw;
+    }
+}
+
+// ---- quantiles.  Row r = setting * NC + channel.  values (rows of the tile, n): the model at the tile's settings, grid
+// (particle blocks, settings of the tile).
+template <class M>
+__global__ __launch_bounds__(kBlock) void predict_rows_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                              int64_t s0, const double* __restrict__ particles,
+                                                              int64_t ld_p, int64_t n, double* __restrict__ values) {
+    double x[M::NS];
+#pragma unroll
+    for (int d = 0; d < M::NS; ++d) x[d] = settings[(int64_t)d * ld_s + s0 + blockIdx.y];
+    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kBlock) {
+        double y[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) values[((int64_t)blockIdx.y * M::NC + c) * n + p] = y[c];
+    }
+}
+
+__global__ void predict_row_list_kernel(int32_t* __restrict__ rows, int n) {
+    if ((int)threadIdx.x < n) rows[threadIdx.x] = threadIdx.x;
+}
+
+// out (n_q, C, n_settings): the tile's results, which select_choose_kernel left row by row (rows of the tile, n_q)
+__global__ __launch_bounds__(kBlock) void predict_deliver_kernel(const double* __restrict__ found, int64_t s0, int tile_settings,
+                                                                 int64_t n_s, int n_channels, int n_q,
+                                                                 double* __restrict__ out) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= tile_settings * n_channels * n_q) return;
+    const int s = i % tile_settings, jc = i / tile_settings;
+    const int c = jc % n_channels, j = jc / n_channels;
+    out[((int64_t)j * n_channels + c) * n_s + s0 + s] = found[(s * n_channels + c) * n_q + j];
+}
+
+int check_inputs(const char* who, const obe_model* m, const void* d_settings, int64_t ld_s, int64_t n_settings,
+                 const void* d_particles, int64_t ld_p, int64_t n_particles, const void* d_weights, const void* d_ws) {
+    static thread_local std::string msg;
+    const char* what = nullptr;
+    if (!m || !d_settings || !d_particles || !d_weights || !d_ws) what = "null pointer";
+    else if (n_settings < 1 || ld_s < n_settings) what = "n_settings < 1 or a row of settings shorter than that";
+    else if (n_particles < 1 || ld_p < n_particles) what = "bad cloud size";
+    if (!what) return 0;
+    msg = std::string(who) + ": " + what;
+    return bad_arg(msg.c_str());
+}
+
+int enqueue_scale(const double* d_weights, int64_t n, const PredWs& ws, hipStream_t st) {
+    const int nb = std::min(stream_blocks(n, kBlock * 8), kPostPartials);
+    wsum_partial_kernel<<<nb, kBlock, 0, st>>>(d_weights, n, ws.partials);
+    OBE_CHECK_LAUNCH("wsum_partial_kernel");
+    scale_kernel<<<1, kBlock, 0, st>>>(ws.partials, nb, ws.hdr);
+    OBE_CHECK_LAUNCH("scale_kernel");
+    return 0;
+}
+
+}  // namespace
+}  // namespace obe
+
+using namespace obe;
+
+extern "C" {
+
+int64_t obe_predictive_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels, int32_t n_q) {
+    if (n_settings < 1) n_settings = 1;
+    if (n_channels < 1) n_channels = 1;
+    if (n_q < 0) n_q = 0;
+    if (n_q > kMaxQ) n_q = kMaxQ;
+    if (n_particles < 1) n_particles = 1;
+    const int64_t body = std::max(moment_words(n_settings, n_channels),
+                                  n_q ? select_words(n_particles, n_settings, n_channels, n_q) : 0);
+    return (kPredHeadWords + body) * (int64_t)sizeof(u64);
+}
+
+int obe_predictive_moments(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                           const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                           double* d_mean, double* d_var, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_mean || !d_var) return bad_arg("obe_predictive_moments: null pointer");
+    if (int rc = check_inputs("obe_predictive_moments", m, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles,
+                              d_weights, d_ws))
+        return rc;
+    obe_model mm = *m;
+    if (int rc = obe_model_validate(&mm)) return rc;
+    if (ws_bytes < obe_predictive_workspace_bytes(n_particles, n_settings, mm.n_channels, 0))
+        return bad_arg("obe_predictive_moments: workspace too small");
+    hipStream_t st = as_stream(stream);
+    const PredWs ws = carve(d_ws);
+    const int64_t tiles = setting_tiles(n_settings);
+    if (tiles > 0x7fffffff) return bad_arg("obe_predictive_moments: too many settings for one call");
+    const int chunks = moment_chunks(n_particles, n_settings);
+    // whole waves of particles per chunk (the count of chunks that are not empty may then be smaller)
+    const int64_t chunk_len = ((n_particles + chunks - 1) / chunks + kWave - 1) / kWave * kWave;
+    const int used = (int)((n_particles + chunk_len - 1) / chunk_len);
+    double* partials = reinterpret_cast<double*>(ws.body);
+    if (int rc = enqueue_scale(d_weights, n_particles, ws, st)) return rc;
+    return dispatch_model(mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        const dim3 grid((unsigned)tiles, (unsigned)used);
+        const int fold_blocks = (int)((n_settings + kBlock - 1) / kBlock);
+        predict_moment_kernel<Model, false><<<grid, kWave, 0, st>>>(mm, d_settings, ld_s, n_settings, d_particles, ld_p,
+                                                                    n_particles, d_weights, chunk_len, nullptr, partials);
+        OBE_CHECK_LAUNCH("predict_moment_kernel");
+        predict_fold_kernel<<<fold_blocks, kBlock, 0, st>>>(partials, used, Model::NC, tiles * kWave, n_settings, ws.hdr,
+                                                            d_mean);
+        OBE_CHECK_LAUNCH("predict_fold_kernel");
+        predict_moment_kernel<Model, true><<<grid, kWave, 0, st>>>(mm, d_settings, ld_s, n_settings, d_particles, ld_p,
+                                                                   n_particles, d_weights, chunk_len, d_mean, partials);
+        OBE_CHECK_LAUNCH("predict_moment_kernel");
+        predict_fold_kernel<<<fold_blocks, kBlock, 0, st>>>(partials, used, Model::NC, tiles * kWave, n_settings, ws.hdr,
+                                                            d_var);
+        OBE_CHECK_LAUNCH("predict_fold_kernel");
+        return 0;
+    });
+}
+
+int obe_predictive_quantiles(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                             const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                             const double* h_q, int32_t n_q, double* d_quantiles, void* d_ws, int64_t ws_bytes,
+                             void* stream) {
+    if (!h_q || !d_quantiles) return bad_arg("obe_predictive_quantiles: null pointer");
+    if (n_q < 1 || n_q > kMaxQ) return bad_arg("obe_predictive_quantiles: 1..16 quantiles per call");
+    for (int j = 0; j < n_q; ++j)
+        if (!(h_q[j] >= 0.0 && h_q[j] <= 1.0)) return bad_arg("obe_predictive_quantiles: q outside [0, 1]");
+    if (int rc = check_inputs("obe_predictive_quantiles", m, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles,
+                              d_weights, d_ws))
+        return rc;
+    obe_model mm = *m;
+    if (int rc = obe_model_validate(&mm)) return rc;
+    if (ws_bytes < obe_predictive_workspace_bytes(n_particles, n_settings, mm.n_channels, n_q))
+        return bad_arg("obe_predictive_quantiles: workspace too small");
+    const int n_c = mm.n_channels;
+    const int tile_settings = (int)std::min<int64_t>(n_settings, std::max(1, kTileRows / n_c));
+    const int tile_rows = tile_settings * n_c;                 // whole settings: <= tile_rows_bound()
+    hipStream_t st = as_stream(stream);
+    const PredWs ws = carve(d_ws);
+    double* values = reinterpret_cast<double*>(ws.body);
+    u64* hist = ws.body + (int64_t)tile_rows * n_particles;
+    u64* prefix = hist + (int64_t)tile_rows * n_q * kDigits;
+    u64* remaining = prefix + tile_rows * n_q;
+    double* found = reinterpret_cast<double*>(remaining + tile_rows * n_q);
+    int32_t* d_rows = reinterpret_cast<int32_t*>(found + tile_rows * n_q);
+    predict_row_list_kernel<<<1, kTileRows, 0, st>>>(d_rows, tile_rows);          // the tile's rows are 0, 1, 2, ...
+    OBE_CHECK_LAUNCH("predict_row_list_kernel");
+    OBE_HIP_TRY(hipMemcpyAsync(ws.q, h_q, sizeof(double) * n_q, hipMemcpyHostToDevice, st));
+    OBE_HIP_TRY(hipMemsetAsync(hist, 0, (size_t)tile_rows * n_q * kDigits * sizeof(u64), st));      // (handed back zeroed)
+    if (int rc = enqueue_scale(d_weights, n_particles, ws, st)) return rc;
+    return dispatch_model(mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        for (int64_t s0 = 0; s0 < n_settings; s0 += tile_settings) {
+            const int ns = (int)std::min<int64_t>(tile_settings, n_settings - s0);
+            const int rows = ns * n_c, slots = rows * n_q;
+            predict_rows_kernel<Model><<<dim3(stream_blocks(n_particles, kBlock), ns), kBlock, 0, st>>>(
+                mm, d_settings, ld_s, s0, d_particles, ld_p, n_particles, values);
+            OBE_CHECK_LAUNCH("predict_rows_kernel");
+            for (int pass = 0; pass < kPasses; ++pass) {
+                select_pass_kernel<<<dim3(cloud_blocks(n_particles), rows), kBlock, (size_t)n_q * kDigits * sizeof(u64), st>>>(
+                    values, n_particles, n_particles, d_weights, d_rows, n_q, pass, ws.hdr, prefix, hist);
+                OBE_CHECK_LAUNCH("select_pass_kernel");
+                select_choose_kernel<<<slots, kWave, 0, st>>>(hist, n_q, ws.q, pass, prefix, remaining, found);
+                OBE_CHECK_LAUNCH("select_choose_kernel");
+            }
+            predict_deliver_kernel<<<(slots + kBlock - 1) / kBlock, kBlock, 0, st>>>(found, s0, ns, n_settings, n_c, n_q,
+                                                                                    d_quantiles);
+            OBE_CHECK_LAUNCH("predict_deliver_kernel");
+        }
+        return 0;
+    });
+}
+
+}  // extern "C"

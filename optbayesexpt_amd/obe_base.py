@@ -33,7 +33,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _devrng, _lib
+from . import _devrng, _lib, _predictive
 from ._sweepstate import Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
@@ -394,6 +394,28 @@ class OptBayesExpt(ParticlePDF):
                        self._n_settings, self._n_settings, _lib.host_ptr(thp), _ptr(y), self._n_settings,
                        self._stream())
         return y.cpu().numpy()
+
+    # ------------------------------------------------ the model curve with its uncertainty
+    # (extension: the reference's demos draw the model at the mean parameters — demos/line_plus_noise/
+    # line_plus_noise.py:138,181 —, a plug-in estimate without a band.  These summarise y_i = model(x; theta_i), the
+    # values of eval_over_all_parameters((x,)), over the whole weighted cloud on the device (_predictive.py,
+    # csrc/obe_predict.hip) and change nothing of the object.  ``settings``: None = every point of the design grid
+    # (``allsettings``), else a tuple of n_setdims scalars or 1-D arrays broadcast to n_x POINTS (not meshgrid axes),
+    # or an (n_setdims, n_x) array.  Device models only; NaN and negative weights count as zero.)
+    def predict(self, settings=None):
+        """``(mean, std)`` of the model output over the cloud, each ``(n_channels, n_x)``: ``mean = sum w y / sum w``,
+        ``std = sqrt(sum w (y - mean)^2 / sum w)``."""
+        return _predictive.predict(self, settings)
+
+    def predictive_quantile(self, q, settings=None):
+        """Weighted quantiles of the model output, ``(n_q, n_channels, n_x)`` (``(n_channels, n_x)`` for a scalar
+        ``q``): ``np.quantile(y, q, weights=particle_weights, method="inverted_cdf")`` by ``quantile()``'s rule."""
+        return _predictive.predictive_quantile(self, q, settings)
+
+    def predictive_interval(self, level=0.95, settings=None):
+        """Equal-tailed credible band ``(lo, hi)`` of the model output, each ``(n_channels, n_x)``: the quantiles at
+        ``(1 - level) / 2`` and ``(1 + level) / 2``."""
+        return _predictive.predictive_interval(self, level, settings)
 
     def _setting_array(self, onesettingset):
         """The setting of a record, zero-padded to OBE_MAX_SETDIMS — in this object's record buffer:

@@ -34,7 +34,7 @@ def main():
             dt = time.perf_counter() - t0
             total += dt
             print(f"  {src:18s} {dt:6.2f} s" + ("" if r.returncode == 0 else "   FAILED: " + r.stderr[-300:]))
-        print(f"  sum of the four, one after the other: {total:.2f} s")
+        print(f"  sum of the sources, one after the other: {total:.2f} s")
         os.environ["OBE_PLUGIN_DIR"] = os.path.join(tmp, "plugins")
         build.PLUGIN_DIR = os.environ["OBE_PLUGIN_DIR"]
         t0 = time.perf_counter()
