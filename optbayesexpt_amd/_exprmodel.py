@@ -94,7 +94,7 @@ class _ToC(ast.NodeVisitor):
 #   * products are distributed / re-associated when that moves work out of the SP level
 #     ((x - x0)/d -> x/d - x0/d;  sw*(b + a*r) -> (sw*a)*r + sw*b);
 #   * divisions by SP-level denominators are batched over the SPT settings a lane owns
-#     (batch_rcp_guarded: one v_rcp_f64 per batch); a*b + c is emitted as fma.
+#     (batch_div_poisoned / batch_rcp_poisoned: one v_rcp_f64 per batch); a*b + c is emitted as fma.
 # Only the sweep uses this form (utilities agree with the exact form to ~1e-13 relative);
 # the Bayes update and eval_over_* use the exact one-operation-per-node `formula`.
 _LC, _LS, _LP, _LSP = 0, 1, 2, 3

@@ -47,85 +47,6 @@ __device__ __forceinline__ double exact_rcp(double q) {
     return fma(r, fma(e, e, e), r);
 }
 
-// Batch inversion: r[j] = 1/q[j] for N values from one reciprocal of their product
-// (3(N-1) multiplies + 1 rcp instead of N rcp + 4N Newton FMAs).  q >= 1 on every
-// direct caller, so the product cannot underflow; it overflows only beyond q ~ 1e77.
-// Returns the reciprocal of the whole product (batch_rcp_guarded's range check).
-template <int N>
-__device__ __forceinline__ double batch_rcp(const double (&q)[N], double (&r)[N]) {
-    if constexpr (N == 1) {
-        r[0] = exact_rcp(q[0]);
-        return r[0];
-    } else if constexpr (N == 2) {
-        const double inv = fast_rcp(q[0] * q[1]);
-        r[0] = inv * q[1];
-        r[1] = inv * q[0];
-        return inv;
-    } else if constexpr (N == 4) {
-        const double p01 = q[0] * q[1], p23 = q[2] * q[3];
-        const double inv = fast_rcp(p01 * p23);
-        const double i01 = inv * p23, i23 = inv * p01;
-        r[0] = i01 * q[1];
-        r[1] = i01 * q[0];
-        r[2] = i23 * q[3];
-        r[3] = i23 * q[2];
-        return inv;
-    } else {
-        static_assert(N == 8, "batch_rcp: N must be 1, 2, 4 or 8");
-        const double p01 = q[0] * q[1], p23 = q[2] * q[3], p45 = q[4] * q[5], p67 = q[6] * q[7];
-        const double p03 = p01 * p23, p47 = p45 * p67;
-        const double inv = fast_rcp(p03 * p47);
-        const double i03 = inv * p47, i47 = inv * p03;
-        const double i01 = i03 * p23, i23 = i03 * p01, i45 = i47 * p67, i67 = i47 * p45;
-        r[0] = i01 * q[1];
-        r[1] = i01 * q[0];
-        r[2] = i23 * q[3];
-        r[3] = i23 * q[2];
-        r[4] = i45 * q[5];
-        r[5] = i45 * q[4];
-        r[6] = i67 * q[7];
-        r[7] = i67 * q[6];
-        return inv;
-    }
-}
-
-// Batch inversion of two groups that share one reciprocal, each result scaled by its group's
-// factor: r[j] = s_lo / q[j] (j < N/2), s_hi / q[j] (j >= N/2).  The factors enter at the
-// top of the back-substitution (two multiplies) instead of once per element afterwards.
-template <int N>
-__device__ __forceinline__ void batch_rcp_scaled2(const double (&q)[N], double s_lo, double s_hi, double (&r)[N]) {
-    if constexpr (N == 2) {
-        const double inv = fast_rcp(q[0] * q[1]);
-        r[0] = inv * (q[1] * s_lo);
-        r[1] = inv * (q[0] * s_hi);
-    } else if constexpr (N == 4) {
-        const double p01 = q[0] * q[1], p23 = q[2] * q[3];
-        const double inv = fast_rcp(p01 * p23);
-        const double i01 = inv * (p23 * s_lo), i23 = inv * (p01 * s_hi);
-        r[0] = i01 * q[1];
-        r[1] = i01 * q[0];
-        r[2] = i23 * q[3];
-        r[3] = i23 * q[2];
-    } else {
-        static_assert(N == 8, "batch_rcp_scaled2: N must be 2, 4 or 8");
-        const double p01 = q[0] * q[1], p23 = q[2] * q[3], p45 = q[4] * q[5], p67 = q[6] * q[7];
-        const double p03 = p01 * p23, p47 = p45 * p67;
-        // (measured and rejected: the Newton step applied to the two half inverses instead of the root —
-        // one slot more, one dependent operation less: +1.6 % at c3, profiles/r03_sweep_accuracy.txt)
-        const double inv = fast_rcp(p03 * p47);
-        const double i03 = inv * (p47 * s_lo), i47 = inv * (p03 * s_hi);
-        const double i01 = i03 * p23, i23 = i03 * p01, i45 = i47 * p67, i67 = i47 * p45;
-        r[0] = i01 * q[1];
-        r[1] = i01 * q[0];
-        r[2] = i23 * q[3];
-        r[3] = i23 * q[2];
-        r[4] = i45 * q[5];
-        r[5] = i45 * q[4];
-        r[6] = i67 * q[7];
-        r[7] = i67 * q[6];
-    }
-}
-
 // 1/b with IEEE behaviour at the edges (b = 0 -> inf, b = inf -> 0, NaN -> NaN): the raw
 // v_rcp_f64 result is returned whenever the correction step produced a NaN.
 __device__ __forceinline__ double guarded_rcp(double b) {
@@ -133,6 +54,96 @@ __device__ __forceinline__ double guarded_rcp(double b) {
     const double e = fma(-b, r0, 1.0);
     const double r = fma(r0, fma(e, e, e), r0);
     return r == r ? r : r0;
+}
+
+// ---- the inversion tree ---------------------------------------------------------------
+// Montgomery's batch inversion, 1/leaf[i] for N = 1, 2, 4 or 8 leaves from ONE reciprocal of their product
+// (3(N-1) multiplies + 1 rcp instead of N rcp + 4N Newton FMAs), as a balanced tree in heap order: node i has the
+// children 2i and 2i + 1, the leaves are the nodes N .. 2N-1 and node 1 is the root.  Every loop is unrolled
+// over constant indices, so the arrays are registers.  The batch_* helpers below are this tree with their own
+// leaves, root policy (how the root reciprocal is obtained and range-checked) and scale factors.
+//   products:  t[N + i] = leaf[i],  t[i] = t[2i] t[2i+1]                (t[1]: the product of all leaves)
+template <int N>
+__device__ __forceinline__ void tree_products(const double (&leaf)[N], double (&t)[2 * N]) {
+    static_assert(N == 1 || N == 2 || N == 4 || N == 8, "inversion tree: 1, 2, 4 or 8 leaves");
+#pragma unroll
+    for (int i = 0; i < N; ++i) t[N + i] = leaf[i];
+#pragma unroll
+    for (int w = N / 2; w >= 1; w /= 2)      // level by level towards the root, each level left to right
+#pragma unroll
+        for (int i = w; i < 2 * w; ++i) t[i] = t[2 * i] * t[2 * i + 1];
+}
+//   magnitude: the sum of |leaf| in the same tree order (the range checks of the poisoned batches)
+template <int N>
+__device__ __forceinline__ double tree_magnitude(const double (&t)[2 * N]) {
+    double m[2 * N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) m[N + i] = fabs(t[N + i]);
+#pragma unroll
+    for (int w = N / 2; w >= 1; w /= 2)
+#pragma unroll
+        for (int i = w; i < 2 * w; ++i) m[i] = m[2 * i] + m[2 * i + 1];
+    return m[1];
+}
+//   inverses:  u[2i] = u[i] t[2i+1],  u[2i+1] = u[i] t[2i]  from node FROM on;  r[i] = u[N + i]
+template <int N, int FROM>
+__device__ __forceinline__ void tree_descend(const double (&t)[2 * N], double (&u)[2 * N], double (&r)[N]) {
+#pragma unroll
+    for (int i = FROM; i < N; ++i) {
+        u[2 * i] = u[i] * t[2 * i + 1];
+        u[2 * i + 1] = u[i] * t[2 * i];
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) r[i] = u[N + i];
+}
+//   r[i] = root_inv * t[1] / leaf[i]: root_inv is the (checked, scaled) reciprocal of the root
+template <int N>
+__device__ __forceinline__ void tree_inverses(const double (&t)[2 * N], double root_inv, double (&r)[N]) {
+    double u[2 * N];
+    u[1] = root_inv;
+    tree_descend<N, 1>(t, u, r);
+}
+//   ... with one factor per half of the leaves, r[i] = s_lo / leaf[i] (i < N/2), s_hi / leaf[i] (i >= N/2): the
+//   factors enter at the top split (two multiplies) instead of once per element afterwards
+template <int N>
+__device__ __forceinline__ void tree_inverses2(const double (&t)[2 * N], double root_inv, double s_lo, double s_hi,
+                                               double (&r)[N]) {
+    static_assert(N >= 2, "two halves");
+    double u[2 * N];
+    u[2] = root_inv * (t[3] * s_lo);
+    u[3] = root_inv * (t[2] * s_hi);
+    tree_descend<N, 2>(t, u, r);
+}
+// the pair products q[2h] q[2h+1]: the leaves of the helpers that stop the tree one level early and let the
+// caller's FMA multiply by the sibling (sibling_of):  a/q0 = (a / (q0 q1)) * q1
+template <int N>
+__device__ __forceinline__ void pair_products(const double (&q)[N], double* pp) {
+#pragma unroll
+    for (int h = 0; h < N / 2; ++h) pp[h] = q[2 * h] * q[2 * h + 1];
+}
+
+// r[j] = 1/q[j].  q >= 1 on every direct caller, so the product cannot underflow; it overflows only beyond
+// q ~ 1e77.
+template <int N>
+__device__ __forceinline__ void batch_rcp(const double (&q)[N], double (&r)[N]) {
+    if constexpr (N == 1) {
+        r[0] = exact_rcp(q[0]);
+    } else {
+        double t[2 * N];
+        tree_products<N>(q, t);
+        tree_inverses<N>(t, fast_rcp(t[1]), r);
+    }
+}
+
+// Two groups that share one reciprocal, each result scaled by its group's factor:
+// r[j] = s_lo / q[j] (j < N/2), s_hi / q[j] (j >= N/2).
+// (measured and rejected at N = 8: the Newton step applied to the two half inverses instead of the root — one slot
+// more, one dependent operation less: +1.6 % at c3, profiles/r03_sweep_accuracy.txt)
+template <int N>
+__device__ __forceinline__ void batch_rcp_scaled2(const double (&q)[N], double s_lo, double s_hi, double (&r)[N]) {
+    double t[2 * N];
+    tree_products<N>(q, t);
+    tree_inverses2<N>(t, fast_rcp(t[1]), s_lo, s_hi, r);
 }
 
 // Batch inversions for generated expression models, whose denominators are not known to be
@@ -151,28 +162,12 @@ template <int N>
 __device__ __forceinline__ void batch_div_poisoned(const double (&q)[N], double s, double (&ip)[(N + 1) / 2]) {
     if constexpr (N == 1) {
         ip[0] = s * guarded_rcp(q[0]);
-    } else if constexpr (N == 2) {
-        const double pp = q[0] * q[1];
-        const double inv = fast_rcp(pp);
-        ip[0] = poison_unless(fabs(pp) < 1e30 && fabs(inv) < 1e200, inv) * s;
-    } else if constexpr (N == 4) {
-        const double p0 = q[0] * q[1], p1 = q[2] * q[3];
-        const double inv = fast_rcp(p0 * p1);
-        const double is = poison_unless(fabs(p0) + fabs(p1) < 1e30 && fabs(inv) < 1e200, inv) * s;
-        ip[0] = is * p1;
-        ip[1] = is * p0;
     } else {
-        static_assert(N == 8, "batch_div_poisoned: N must be 1, 2, 4 or 8");
-        const double p0 = q[0] * q[1], p1 = q[2] * q[3], p2 = q[4] * q[5], p3 = q[6] * q[7];
-        const double p01 = p0 * p1, p23 = p2 * p3;
-        const double inv = fast_rcp(p01 * p23);
-        const double mag = (fabs(p0) + fabs(p1)) + (fabs(p2) + fabs(p3));
-        const double is = poison_unless(mag < 1e30 && fabs(inv) < 1e200, inv) * s;
-        const double i01 = is * p23, i23 = is * p01;
-        ip[0] = i01 * p1;
-        ip[1] = i01 * p0;
-        ip[2] = i23 * p3;
-        ip[3] = i23 * p2;
+        double pp[N / 2], t[N];
+        pair_products<N>(q, pp);
+        tree_products<N / 2>(pp, t);
+        const double inv = fast_rcp(t[1]);
+        tree_inverses<N / 2>(t, poison_unless(tree_magnitude<N / 2>(t) < 1e30 && fabs(inv) < 1e200, inv) * s, ip);
     }
 }
 template <int N>
@@ -188,42 +183,16 @@ __device__ __forceinline__ double sibling_of(const double (&q)[N], int j) {
 template <int N>
 __device__ __forceinline__ void batch_div_poisoned2(const double (&qa)[N], const double (&qb)[N], double sa, double sb,
                                                     double (&ipa)[N / 2], double (&ipb)[N / 2]) {
-    static_assert(N == 2 || N == 4 || N == 8, "batch_div_poisoned2: N must be 2, 4 or 8");
-    if constexpr (N == 2) {
-        const double a0 = qa[0] * qa[1], b0 = qb[0] * qb[1];
-        const double inv = fast_rcp(a0 * b0);
-        const double ok = poison_unless(fabs(a0) + fabs(b0) < 1e18 && fabs(inv) < 1e150, inv);
-        ipa[0] = ok * (b0 * sa);
-        ipb[0] = ok * (a0 * sb);
-    } else if constexpr (N == 4) {
-        const double a0 = qa[0] * qa[1], a1 = qa[2] * qa[3], b0 = qb[0] * qb[1], b1 = qb[2] * qb[3];
-        const double pa = a0 * a1, pb = b0 * b1;
-        const double inv = fast_rcp(pa * pb);
-        const double mag = (fabs(a0) + fabs(a1)) + (fabs(b0) + fabs(b1));
-        const double ok = poison_unless(mag < 1e18 && fabs(inv) < 1e150, inv);
-        const double ia = ok * (pb * sa), ib = ok * (pa * sb);
-        ipa[0] = ia * a1;
-        ipa[1] = ia * a0;
-        ipb[0] = ib * b1;
-        ipb[1] = ib * b0;
-    } else {
-        const double a0 = qa[0] * qa[1], a1 = qa[2] * qa[3], a2 = qa[4] * qa[5], a3 = qa[6] * qa[7];
-        const double b0 = qb[0] * qb[1], b1 = qb[2] * qb[3], b2 = qb[4] * qb[5], b3 = qb[6] * qb[7];
-        const double a01 = a0 * a1, a23 = a2 * a3, b01 = b0 * b1, b23 = b2 * b3;
-        const double pa = a01 * a23, pb = b01 * b23;
-        const double inv = fast_rcp(pa * pb);
-        const double mag = ((fabs(a0) + fabs(a1)) + (fabs(a2) + fabs(a3))) + ((fabs(b0) + fabs(b1)) + (fabs(b2) + fabs(b3)));
-        const double ok = poison_unless(mag < 1e18 && fabs(inv) < 1e150, inv);
-        const double ia = ok * (pb * sa), ib = ok * (pa * sb);
-        const double ia01 = ia * a23, ia23 = ia * a01, ib01 = ib * b23, ib23 = ib * b01;
-        ipa[0] = ia01 * a1;
-        ipa[1] = ia01 * a0;
-        ipa[2] = ia23 * a3;
-        ipa[3] = ia23 * a2;
-        ipb[0] = ib01 * b1;
-        ipb[1] = ib01 * b0;
-        ipb[2] = ib23 * b3;
-        ipb[3] = ib23 * b2;
+    double pp[N], t[2 * N], ip[N];
+    pair_products<N>(qa, pp);
+    pair_products<N>(qb, pp + N / 2);
+    tree_products<N>(pp, t);
+    const double inv = fast_rcp(t[1]);
+    tree_inverses2<N>(t, poison_unless(tree_magnitude<N>(t) < 1e18 && fabs(inv) < 1e150, inv), sa, sb, ip);
+#pragma unroll
+    for (int h = 0; h < N / 2; ++h) {
+        ipa[h] = ip[h];
+        ipb[h] = ip[N / 2 + h];
     }
 }
 template <int N>
@@ -256,26 +225,11 @@ template <int N>
 __device__ __forceinline__ void batch_div_ge1(const double (&q)[N], double s, double (&ip)[(N + 1) / 2]) {
     if constexpr (N == 1) {
         ip[0] = s * exact_rcp(q[0]);
-    } else if constexpr (N == 2) {
-        const double pp = q[0] * q[1];
-        ip[0] = poison_unless(pp < 1e250, fast_rcp(pp)) * s;
-    } else if constexpr (N == 4) {
-        const double p0 = q[0] * q[1], p1 = q[2] * q[3];
-        const double root = p0 * p1;
-        const double is = poison_unless(root < 1e250, fast_rcp(root)) * s;
-        ip[0] = is * p1;
-        ip[1] = is * p0;
     } else {
-        static_assert(N == 8, "batch_div_ge1: N must be 1, 2, 4 or 8");
-        const double p0 = q[0] * q[1], p1 = q[2] * q[3], p2 = q[4] * q[5], p3 = q[6] * q[7];
-        const double p01 = p0 * p1, p23 = p2 * p3;
-        const double root = p01 * p23;
-        const double is = poison_unless(root < 1e250, fast_rcp(root)) * s;
-        const double i01 = is * p23, i23 = is * p01;
-        ip[0] = i01 * p1;
-        ip[1] = i01 * p0;
-        ip[2] = i23 * p3;
-        ip[3] = i23 * p2;
+        double pp[N / 2], t[N];
+        pair_products<N>(q, pp);
+        tree_products<N / 2>(pp, t);
+        tree_inverses<N / 2>(t, poison_unless(t[1] < 1e250, fast_rcp(t[1])) * s, ip);
     }
 }
 
@@ -345,15 +299,20 @@ __device__ __forceinline__ double fast_cos(double x) {
     const double v = (static_cast<int>(k) & 1) ? -s : s;
     return fabs(x) < 1e9 ? v : __builtin_nan("");
 }
-// sqrt a = a * rsq(a): v_rsq_f64 (2^-23) + two Newton steps, then one correction of the root.
-// 0 -> 0, negative -> NaN, +inf -> NaN (repeat with the safe twin).
-__device__ __forceinline__ double fast_sqrt(double a) {
+// 1/sqrt(a): v_rsq_f64 (~2^-23) + two Newton steps
+__device__ __forceinline__ double fast_rsqrt(double a) {
     double y = __builtin_amdgcn_rsq(a);
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
         const double e = fma(-(a * y), y, 1.0);
         y = fma(y * 0.5, e, y);
     }
+    return y;
+}
+// sqrt a = a * fast_rsqrt(a), then one correction of the root.
+// 0 -> 0, negative -> NaN, +inf -> NaN (repeat with the safe twin).
+__device__ __forceinline__ double fast_sqrt(double a) {
+    const double y = fast_rsqrt(a);
     double s = a * y;
     s = fma(fma(-s, s, a), y * 0.5, s);
     return a == 0.0 ? 0.0 : s;
@@ -665,12 +624,7 @@ struct Rabi {
         for (int j = 0; j < SPT; ++j) {
             const double det = xs[j][1] - pk[1];
             const double f2 = fma(det, det, pk[0]);
-            double y = __builtin_amdgcn_rsq(f2);                // 1/f to ~2^-23, then two Newton steps
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const double e = fma(-(f2 * y), y, 1.0);
-                y = fma(y * 0.5, e, y);
-            }
+            const double y = fast_rsqrt(f2);                    // 1/f
             const double x = (f2 * y) * xs[j][0];               // f * tau
             const double r = x - rint(x);
             const double s = r * sinpi_over_r(r * r);           // +- sin(pi f tau)

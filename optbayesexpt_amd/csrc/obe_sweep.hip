@@ -45,8 +45,11 @@ static int64_t argmax_slots(int64_t n_settings) {
     return std::max<int64_t>(kMaxBlocks, (n_settings + kFinSettings - 1) / kFinSettings);
 }
 
-// one-workgroup path for reference-semantics sweeps (sweep_small_kernel)
+// one-workgroup path for reference-semantics sweeps (sweep_small_kernel): draws mode only
 constexpr int64_t kSmallSweepDraws = 256, kSmallSweepEvals = 131072;
+static bool one_workgroup_sweep(int64_t n_settings, int64_t n_draws) {
+    return n_draws <= kSmallSweepDraws && n_settings * n_draws <= kSmallSweepEvals;
+}
 
 // packed particle: M::NPK doubles + sqrt(weight), padded to 16 bytes
 template <class M>
@@ -129,6 +132,26 @@ __device__ __forceinline__ bool sweep_aborted(const unsigned* abort) {
     return abort && __builtin_amdgcn_readfirstlane(*abort) != 0u;
 }
 
+// the particle draw p stands for and its weight: the particle itself (full mode), or draw_idx[p] clamped to the
+// cloud with the uniform weight 1/n_draws
+__device__ __forceinline__ int64_t draw_source(const SweepArgs& a, int64_t p, double& w) {
+    if (!a.draw_idx) {
+        w = a.weights[p];
+        return p;
+    }
+    const int64_t src = a.draw_idx[p];
+    w = a.uniform_w;
+    return src < 0 ? 0 : (src >= a.n_particles ? a.n_particles - 1 : src);
+}
+
+// one evaluation into the running moments of its setting and channel about the shift c_s (v = sqrt(w) * y')
+template <bool SHIFT>
+__device__ __forceinline__ void add_to_moments(double c_s, double sw, double v, double& s1, double& s2) {
+    const double u = SHIFT ? fma(-c_s, sw, v) : v;   // sqrt(w) * (y' - c_s)
+    s1 = fma(sw, u, s1);                             // sum w (y' - c_s)
+    s2 = fma(u, u, s2);                              // sum w (y' - c_s)^2
+}
+
 // Every draw packed once per sweep: M::pack() (per-particle divisions, sqrt(w) folded into the
 // amplitudes) and sqrt(w), one 16-byte-aligned record per draw.
 template <class M>
@@ -145,15 +168,8 @@ __global__ __launch_bounds__(kBlock) void sweep_pack_kernel(SweepArgs a) {
         const int64_t p = p0 + threadIdx.x;
         double pk[NPKW];
         if (p < a.nd) {
-            int64_t src = p;
             double w;
-            if (a.draw_idx) {
-                src = a.draw_idx[p];
-                src = src < 0 ? 0 : (src >= a.n_particles ? a.n_particles - 1 : src);
-                w = a.uniform_w;
-            } else {
-                w = a.weights[p];
-            }
+            const int64_t src = draw_source(a, p, w);
             const double sw = sqrt(w);
             M::pack(ParamRef{a.particles + src, a.ld_p}, thbar, a.m, sw, pk);
             pk[NPK] = sw;
@@ -254,11 +270,7 @@ __global__ __launch_bounds__(kBlock) void sweep_kernel(SweepArgs a) {
 #pragma unroll
         for (int j = 0; j < SPT; ++j) {
 #pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const double u = SHIFT ? fma(-cs[j][c], sw, v[j][c]) : v[j][c];   // sqrt(w) * (y' - c_s)
-                s1[j][c] = fma(sw, u, s1[j][c]);                     // sum w (y' - c_s)
-                s2[j][c] = fma(u, u, s2[j][c]);                      // sum w (y' - c_s)^2
-            }
+            for (int c = 0; c < NC; ++c) add_to_moments<SHIFT>(cs[j][c], sw, v[j][c], s1[j][c], s2[j][c]);
         }
     };
     auto load_group = [&](int i0, double (&g)[G][NPKW]) {
@@ -266,6 +278,13 @@ __global__ __launch_bounds__(kBlock) void sweep_kernel(SweepArgs a) {
         for (int e = 0; e < G; ++e)
 #pragma unroll
             for (int k = 0; k < NPKW; ++k) g[e][k] = pk[(i0 + e) * NPKW + k];
+    };
+    // (always_inline: with two call sites the inliner's cost model would decide, and change the SAFE kernels' code)
+    auto process_one = [&](const double (&g)[NPKW]) __attribute__((always_inline)) {
+        double v[SPT][NC];
+        if constexpr (SAFE) M::template sweep_eval_safe<SPT>(xs, g, g[NPK], a.m, v);
+        else M::template sweep_eval<SPT>(xs, g, g[NPK], a.m, v);   // sqrt(w) * y'
+        accumulate(v, g[NPK]);
     };
     auto process_group = [&](const double (&g)[G][NPKW]) {
         if constexpr (PAIRS) {
@@ -279,12 +298,7 @@ __global__ __launch_bounds__(kBlock) void sweep_kernel(SweepArgs a) {
             }
         } else {
 #pragma unroll
-            for (int e = 0; e < G; ++e) {
-                double v[SPT][NC];
-                if constexpr (SAFE) M::template sweep_eval_safe<SPT>(xs, g[e], g[e][NPK], a.m, v);
-                else M::template sweep_eval<SPT>(xs, g[e], g[e][NPK], a.m, v);   // sqrt(w) * y'
-                accumulate(v, g[e][NPK]);
-            }
+            for (int e = 0; e < G; ++e) process_one(g[e]);
         }
     };
 
@@ -310,12 +324,10 @@ __global__ __launch_bounds__(kBlock) void sweep_kernel(SweepArgs a) {
         }
     }
     for (; i < n; ++i) {
-        double g[NPKW], v[SPT][NC];
+        double g[NPKW];
 #pragma unroll
         for (int k = 0; k < NPKW; ++k) g[k] = pk[i * NPKW + k];
-        if constexpr (SAFE) M::template sweep_eval_safe<SPT>(xs, g, g[NPK], a.m, v);
-        else M::template sweep_eval<SPT>(xs, g, g[NPK], a.m, v);
-        accumulate(v, g[NPK]);
+        process_one(g);
     }
 
     // (global stores only after the streaming loop: nothing may alias the packed draws before it,
@@ -385,14 +397,16 @@ static int make_util_args(UtilArgs& ua, const double* d_noise_var, int64_t noise
     return 0;
 }
 
-__device__ __forceinline__ double utility_of(const double* var, int nc, int64_t s, const UtilArgs& u) {
+// utility of setting s from its nc channel variances var[c * var_stride] (any number of channels)
+__device__ __forceinline__ double utility_of(const double* var, int64_t var_stride, int nc, int64_t s,
+                                             const UtilArgs& u) {
     // np.sum(var_p / var_n, axis=0) / cost   (obe_base.py:654-655)
     double acc = 0.0;
     for (int c = 0; c < nc; ++c) {
         const double nv = u.noise_ld > 0 ? u.noise_var[(int64_t)c * u.noise_ld + s]
                           : (u.noise_ld == 0 ? u.noise_var[c]
                                              : u.noise_var[2 + 2 * u.mom_dims + u.mom_rows[c]] / u.noise_var[0]);
-        acc = acc + var[c] / nv;
+        acc = acc + var[c * var_stride] / nv;
     }
     return acc / (u.cost ? u.cost[s] : u.cost_scalar);
 }
@@ -442,6 +456,35 @@ constexpr int kFinNarrowBelow = 128;       // ... used while 64 settings per wor
 // worst cancellation factor so far; a NaN (some variance is NaN) is sticky
 __device__ __forceinline__ double kappa_worst(double a, double b) {
     return a != a ? a : (b != b ? b : (a > b ? a : b));
+}
+
+// One setting and channel from its moments about the shift c_s: the variance (returned), and the cancellation
+// factor (mean of y')^2 / var an UNSHIFTED sweep would suffer, folded into kappa.
+// (Measured alternative: chunk partials combined with TwoSum and S1*(S1/W) formed exactly
+// with FMAs, plus per-tile flushing of the running sums, lowers the error of the
+// unshifted variance from ~1e-15*kappa to ~2e-16*kappa — but the exact product then
+// exposes the rounding of S2 itself, e.g. a non-zero variance for a single draw where
+// the plain formula cancels to the reference's exact 0.  Not kept.)
+__device__ __forceinline__ double variance_of_moments(double S1, double S2, double W, double c_s, double& kappa) {
+    const double mu = S1 / W;
+    double v = (S2 - S1 * mu) / W;
+    v = v > 0.0 ? v : (v != v ? v : 0.0);          // rounding may leave -0 / tiny negatives; NaN stays NaN (np.var)
+    const double m = c_s + mu;
+    const double k = v != v ? v : (v > 0.0 ? (m * m) / v : (m == 0.0 ? 0.0 : INFINITY));
+    kappa = kappa_worst(kappa, k);                 // a NaN variance is reported as kappa = NaN
+    return v;
+}
+
+// worst kappa over the workgroup (kBlock threads), returned to every thread
+__device__ __forceinline__ double block_kappa_worst(double kappa) {
+    __shared__ double kred[kBlock];
+    kred[threadIdx.x] = kappa;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) kred[threadIdx.x] = kappa_worst(kred[threadIdx.x], kred[threadIdx.x + o]);
+        __syncthreads();
+    }
+    return kred[0];
 }
 
 // Where the result goes on the host, as device-visible addresses (page-locked host memory), or all
@@ -526,7 +569,7 @@ __global__ __launch_bounds__(FG * WS) void sweep_finalize(const double* __restri
     const int lane = wlane % WS, grp = wave * (kWave / WS) + wlane / WS;      // setting within the tile, chunk group
     const int64_t s = (int64_t)blockIdx.x * WS + lane;
     double var[OBE_MAX_CHANNELS];
-    double kappa = 0.0;     // worst (mean of y')^2 / var: the cancellation an UNSHIFTED sweep would suffer
+    double kappa = 0.0;     // worst cancellation factor of this thread's setting
     for (int c = 0; c < nc; ++c) {
         double a1 = 0.0, a2 = 0.0;
         if (s < ns) {
@@ -577,25 +620,14 @@ __global__ __launch_bounds__(FG * WS) void sweep_finalize(const double* __restri
                 a1 += acc1[g][lane];
                 a2 += acc2[g][lane];
             }
-            // (Measured alternative: chunk partials combined with TwoSum and S1*(S1/W) formed exactly
-            // with FMAs, plus per-tile flushing of the running sums, lowers the error of the
-            // unshifted variance from ~1e-15*kappa to ~2e-16*kappa — but the exact product then
-            // exposes the rounding of S2 itself, e.g. a non-zero variance for a single draw where
-            // the plain formula cancels to the reference's exact 0.  Not kept.)
-            const double mu = a1 / W;
-            double v = (a2 - a1 * mu) / W;
-            v = v > 0.0 ? v : (v != v ? v : 0.0);          // rounding may leave -0 / tiny negatives; NaN stays NaN (np.var)
-            var[c] = v;
-            yvar[(int64_t)c * ns + s] = v;
-            const double m = cs[(int64_t)c * ns + s] + mu;
-            const double k = v != v ? v : (v > 0.0 ? (m * m) / v : (m == 0.0 ? 0.0 : INFINITY));
-            kappa = kappa_worst(kappa, k);                 // a NaN variance is reported as kappa = NaN
+            var[c] = variance_of_moments(a1, a2, W, cs[(int64_t)c * ns + s], kappa);
+            yvar[(int64_t)c * ns + s] = var[c];
         }
     }
     if (wave != 0) return;
     Best best{-INFINITY, INT64_MAX};
     if (grp == 0 && s < ns) {
-        const double u = utility_of(var, nc, s, ua);
+        const double u = utility_of(var, 1, nc, s, ua);
         utility[s] = u;
         best = Best{u, s};
     }
@@ -612,13 +644,7 @@ __global__ __launch_bounds__(kBlock) void utility_kernel(const double* __restric
                                                          double* __restrict__ bv, int64_t* __restrict__ bi) {
     Best best{-INFINITY, INT64_MAX};
     for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < ns; s += (int64_t)gridDim.x * kBlock) {
-        // np.sum(var_p / var_n, axis=0) / cost over ANY number of channels (obe_base.py:654-655; noise_ld >= 0 here)
-        double acc = 0.0;
-        for (int c = 0; c < nc; ++c) {
-            const double nv = ua.noise_ld > 0 ? ua.noise_var[(int64_t)c * ua.noise_ld + s] : ua.noise_var[c];
-            acc = acc + yvar[(int64_t)c * ns + s] / nv;
-        }
-        const double u = acc / (ua.cost ? ua.cost[s] : ua.cost_scalar);
+        const double u = utility_of(yvar + s, ns, nc, s, ua);      // (noise_ld >= 0 here: obe_utility_argmax)
         utility[s] = u;
         Best cand{u, s};
         if (better(cand, best)) best = cand;
@@ -669,36 +695,28 @@ __global__ __launch_bounds__(kBlock) void argmax_fold(const double* __restrict__
         }
     }
     block_argmax(best, out_v, out_i);   // gridDim.x == 1 -> writes element 0
-    __shared__ double kred[kBlock];
-    kred[threadIdx.x] = kmax;
-    __syncthreads();
-    for (int o = kBlock / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) kred[threadIdx.x] = kappa_worst(kred[threadIdx.x], kred[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) write_result_record(out_v, out_i, Best{out_v[0], out_i[0]}, kred[0], host);
+    const double k = block_kappa_worst(kmax);
+    if (threadIdx.x == 0) write_result_record(out_v, out_i, Best{out_v[0], out_i[0]}, k, host);
 }
 
 // Reference-semantics sweeps are tiny (201 settings x 30 draws in the demos): one workgroup
 // does what sweep_kernel + sweep_finalize + argmax_fold do in three launches — the draws are
 // packed into LDS once, each thread walks its settings, and the block folds utility, first
 // maximum and kappa.  Same formulas and summation order as the SPT = 1, one-chunk path of the
-// big kernels, hence the same bits.
+// big kernels, hence the same bits: the arithmetic is the same functions.
 template <class M, bool SAFE>
 __global__ __launch_bounds__(kBlock) void sweep_small_kernel(SweepArgs a, UtilArgs ua, double* __restrict__ yvar,
                                                              double* __restrict__ utility,
                                                              double* __restrict__ out_v,
                                                              int64_t* __restrict__ out_i, HostResult host) {
-    constexpr int NC = M::NC, NXS = M::NXS, NPK = M::NPK;
-    constexpr int NPKW = (NPK + 1 + 1) & ~1;
+    constexpr int NC = M::NC, NXS = M::NXS, NPK = M::NPK, NPKW = packed_width<M>();
     extern __shared__ __attribute__((aligned(16))) double tile[];
-    __shared__ double kred[kBlock];
     const double* __restrict__ thbar = a.moments + 2;
     const int nd = static_cast<int>(a.nd);
     for (int i = threadIdx.x; i < nd; i += kBlock) {
-        int64_t src = a.draw_idx[i];
-        src = src < 0 ? 0 : (src >= a.n_particles ? a.n_particles - 1 : src);
-        const double sw = sqrt(a.uniform_w);
+        double w;
+        const int64_t src = draw_source(a, i, w);
+        const double sw = sqrt(w);
         double pk[NPK];
         M::pack(ParamRef{a.particles + src, a.ld_p}, thbar, a.m, sw, pk);
 #pragma unroll
@@ -730,45 +748,22 @@ __global__ __launch_bounds__(kBlock) void sweep_small_kernel(SweepArgs a, UtilAr
             const double sw = tile[i * NPKW + NPK];
             eval(xs, pk, sw, v);
 #pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const double u = fma(-cs[0][c], sw, v[0][c]);
-                s1[c] = fma(sw, u, s1[c]);
-                s2[c] = fma(u, u, s2[c]);
-            }
+            for (int c = 0; c < NC; ++c) add_to_moments<true>(cs[0][c], sw, v[0][c], s1[c], s2[c]);
         }
         double var[OBE_MAX_CHANNELS];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const double mu = s1[c] / W;
-            double v = (s2[c] - s1[c] * mu) / W;
-            v = v > 0.0 ? v : (v != v ? v : 0.0);
-            var[c] = v;
-            yvar[(int64_t)c * a.ns + s] = v;
-            const double m = cs[0][c] + mu;
-            const double k = v != v ? v : (v > 0.0 ? (m * m) / v : (m == 0.0 ? 0.0 : INFINITY));
-            kappa = kappa_worst(kappa, k);
+            var[c] = variance_of_moments(s1[c], s2[c], W, cs[0][c], kappa);
+            yvar[(int64_t)c * a.ns + s] = var[c];
         }
-        const double u = utility_of(var, NC, s, ua);
+        const double u = utility_of(var, 1, NC, s, ua);
         utility[s] = u;
         const Best cand{u, s};
         if (better(cand, best)) best = cand;
     }
     block_argmax(best, out_v, out_i);       // one block: element 0
-    kred[threadIdx.x] = kappa;
-    __syncthreads();
-    for (int o = kBlock / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) kred[threadIdx.x] = kappa_worst(kred[threadIdx.x], kred[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {                 // the result record, as argmax_fold leaves it
-        const double k = kred[0];
-        out_v[1] = k;
-        out_v[2] = out_v[0];
-        reinterpret_cast<int64_t*>(out_v)[3] = out_i[0];
-        out_v[4] = k;
-        out_v[5] = 0.0;
-        deliver(host, out_v[0], out_i[0], k);
-    }
+    const double k = block_kappa_worst(kappa);
+    if (threadIdx.x == 0) write_result_record(out_v, out_i, Best{out_v[0], out_i[0]}, k, host);
 }
 
 // np.var(utility_y_space, axis=0): two-pass over the (small) draw axis
@@ -819,19 +814,23 @@ struct SweepTiming {
 };
 static SweepTiming g_timing;
 
+// the time between the pair of events (both completed) joins the totals, unless it is shorter than min_ms
+static void count_timed_sweep(double min_ms = 0.0) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, g_timing.e0, g_timing.e1) != hipSuccess) return;
+    if (ms >= min_ms) {
+        g_timing.total_ms += ms;
+        g_timing.launches += 1;
+    }
+}
+
 // A speculative call returns before its kernels have run: its pair of events is read at the next timed call
 // or query.  An aborted sweep (its update resampled) is not a sweep: shorter than any kernel could sweep
 // that many evaluations (half of 8e12 evaluations/s, well above this chip's rate), it is left out.
 static void resolve_pending_timing() {
     if (!g_timing.pending) return;
     g_timing.pending = false;
-    float ms = 0.f;
-    if (hipEventSynchronize(g_timing.e1) != hipSuccess) return;
-    if (hipEventElapsedTime(&ms, g_timing.e0, g_timing.e1) != hipSuccess) return;
-    if (ms >= g_timing.pending_min_ms) {
-        g_timing.total_ms += ms;
-        g_timing.launches += 1;
-    }
+    if (hipEventSynchronize(g_timing.e1) == hipSuccess) count_timed_sweep(g_timing.pending_min_ms);
 }
 
 struct SweepWs {
@@ -1016,7 +1015,7 @@ int obe_sweep_settings_per_lane(int64_t n_settings) {
 int obe_sweep_settings_per_lane_for(int64_t n_settings, int64_t n_draws) {
     if (n_settings < 1) n_settings = 1;
     if (n_draws < 1) return obe_sweep_settings_per_lane(n_settings);
-    if (n_draws <= kSmallSweepDraws && n_settings * n_draws <= kSmallSweepEvals) return 1;   // one-workgroup path
+    if (one_workgroup_sweep(n_settings, n_draws)) return 1;
     return plan_sweep(n_settings, n_draws).spt;
 }
 
@@ -1071,11 +1070,10 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     if (nowait && !out.by_kernel)
         return bad_arg("obe_sweep_utility: OBE_SWEEP_SPECULATIVE / OBE_SWEEP_NOWAIT need page-locked host outputs");
     const HostResult hr = out.arm(result_tail(d_ws, ws_bytes, sweep_ws_need));
-    if (d_draw_idx && n_draws <= kSmallSweepDraws && n_settings * n_draws <= kSmallSweepEvals) {
+    if (d_draw_idx && one_workgroup_sweep(n_settings, n_draws)) {
         int rc = dispatch_model(mm, [&](auto M) -> int {
             using Model = decltype(M);
-            constexpr int NPKW = (Model::NPK + 2) & ~1;
-            const size_t lds = (size_t)n_draws * NPKW * sizeof(double);
+            const size_t lds = (size_t)n_draws * packed_width<Model>() * sizeof(double);
             bool safe = false;
             if constexpr (has_safe_eval<Model>::value) safe = shifted & OBE_SWEEP_SAFE;
             if (safe) {
@@ -1141,13 +1139,7 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     }
     rc = out.read(w, st);
     if (timed && !rc && !(h_best || h_best_idx || h_kappa)) rc = (int)hipEventSynchronize(g_timing.e1);
-    if (timed && !rc) {                       // the stream is drained: both events have completed
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, g_timing.e0, g_timing.e1) == hipSuccess) {
-            g_timing.total_ms += ms;
-            g_timing.launches += 1;
-        }
-    }
+    if (timed && !rc) count_timed_sweep();    // the stream is drained: both events have completed
     return rc;
 }
 
