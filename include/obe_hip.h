@@ -346,6 +346,19 @@ OBE_API int obe_resample_particles_aos_masked(const double* d_old_aos, int32_t n
                                       double* d_new, int64_t ld_new, double* d_weights,
                                       const int32_t* h_rows, int32_t n_rows, double* d_mask_partials, void* stream);
 
+/* The masked gather for declarative bounds on any parameter rows (OptBayesExpt.set_parameter_bounds; the hooks of
+ * obe_noiseparam.py:57-79 and demos/lockin/lockin_of_coil.py:115-133 as data): a new particle whose row h_rows[k]
+ * lies outside [h_lower[k], h_upper[k]] for any k — see obe_mask_bounds for h_open and the refusals, rows in
+ * [0, n_dims) — gets weight 0 instead of 1/N.  d_mask_partials receives the same {sum w, count} partials as
+ * obe_resample_particles_aos_masked leaves, for the same obe_mask_renorm_moments().  n_dims <= OBE_FAST_DIMS. */
+OBE_API int obe_resample_particles_aos_bounded(const double* d_old_aos, int32_t n_dims, int64_t n_particles,
+                                       const int64_t* d_idx, const double* d_normals,
+                                       const double* h_factor, const double* h_mean,
+                                       double a_param, int32_t scale,
+                                       double* d_new, int64_t ld_new, double* d_weights,
+                                       const int32_t* h_rows, const double* h_lower, const double* h_upper,
+                                       const int32_t* h_open, int32_t n_rows, double* d_mask_partials, void* stream);
+
 /* resample(), the device side up to the host's factorisation of the covariance, enqueued by ONE call
  * (particlepdf.py:260-301; RNG order as there: N uniforms for rng.choice, then N x D normals): the caller's
  * PCG64 stream continued on the device (h_pcg_state4 = {state hi, lo, increment hi, lo}; n_raw >= N + N D +
@@ -400,6 +413,36 @@ OBE_API int obe_mask_renorm_moments(const double* d_particles, int64_t ld_p, int
                             double* h_moments, int64_t* h_changed, void* d_ws, int64_t ws_bytes, void* stream);
 OBE_API int obe_noise_var_from_moments(const double* d_moments, int32_t n_dims, const int32_t* h_rows,
                                int32_t n_rows, double* d_out, void* stream);
+
+/* ---- K6 for any rows: declarative parameter bounds (OptBayesExpt.set_parameter_bounds) ----
+ * What the reference's users write as a NumPy hook — obe_noiseparam.py:57-79 (sigma <= 0), demos/lockin/
+ * lockin_of_coil.py:115-133 (any parameter < 0) — as data: zero the weight of every particle whose row h_rows[k] is
+ * below h_lower[k] or above h_upper[k] for any k, renormalise if anything changed.  h_open[k]: bit 0 = the lower
+ * end is exclusive (a value EQUAL to h_lower[k] violates too), bit 1 = the upper end; an absent end is -inf / +inf
+ * (its bit is ignored: a value of -inf / +inf never violates an absent end).
+ * A NaN value violates nothing.  If every particle violates, the weights become NaN (0 / 0, as in NumPy and in
+ * obe_mask_nonpositive).  Several entries may name one row: they intersect.  Model-independent.
+ * Refused (-1) before anything is launched: a NULL pointer, n_rows outside 1..OBE_MAX_DIMS, a row outside
+ * [0, OBE_CLOUD_MAX_DIMS) — [0, n_dims) where the call has n_dims —, a NaN bound, lower > upper, ld_p < n_particles.
+ * *h_count = number of particles zeroed (sync).  (h_count / h_first_moments are obe_mask_nonpositive*'s h_changed /
+ * h_moments: the delivery audit keeps its rules for these two calls in a table of their own, _audit._BOUNDS_RULES,
+ * and reads the arguments by these names.)  Same grid, order and second half as obe_mask_nonpositive: the
+ * same set of violators leaves the same bits. */
+OBE_API int obe_mask_bounds(const double* d_particles, int64_t ld_p, int64_t n_particles,
+                    const int32_t* h_rows, const double* h_lower, const double* h_upper, const int32_t* h_open,
+                    int32_t n_rows, double* d_weights, int64_t* h_count, void* d_ws, int64_t ws_bytes,
+                    void* stream);
+
+/* The same mask AND the first moments of the constrained cloud, in two launches, nothing waited for: page-locked
+ * h_count (1 word) and h_first_moments (2 + 4 n_dims values; either may be NULL) are armed here, as
+ * obe_mask_nonpositive_moments arms its h_changed and h_moments, and the caller waits with obe_host_words_wait()
+ * (obe_noiseparam.py:57-79, demos/lockin/lockin_of_coil.py:115-133 + particlepdf.py:173-214); pageable host buffers or more than
+ * OBE_FAST_DIMS rows: obe_mask_bounds() + obe_moments(want_cov = 0), synchronously.  Bit for bit what those two
+ * calls leave. */
+OBE_API int obe_mask_bounds_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                            const int32_t* h_rows, const double* h_lower, const double* h_upper,
+                            const int32_t* h_open, int32_t n_rows, double* d_weights, double* d_moments,
+                            double* h_first_moments, int64_t* h_count, void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ---- good_setting (obe_base.py:781-784): p = nan_to_num(u ** exponent); p /= sum(p) ---- */
 OBE_API int obe_power_normalize(const double* d_u, int64_t n, double exponent, double* d_p_out,

@@ -99,7 +99,7 @@ class _Audit(_NoAudit):
         self.violations = []
         self.counts = dict(zones=0, armed=0, waited=0, reads=0, syncs=0)
         self.rules = {}           # entry point -> (rule, the argument positions of the parameters it reads)
-        for fn, (rule, *names) in _RULES.items():
+        for fn, (rule, *names) in {**_RULES, **_BOUNDS_RULES}.items():
             params = [name for _, name in PROTOTYPES[fn][1]]
             self.rules[fn] = (rule, tuple(params.index(name) for name in names))
 
@@ -275,6 +275,13 @@ _RULES = {
     "obe_weight_cdf": (_delivered(words=1), "h_total"),
     "obe_utility_argmax": (_delivered(words=1), "h_best", "h_best_idx"),
     "obe_argmax": (_delivered(words=1), "h_best", "h_best_idx"),
+}
+
+# the declarative-bounds forms of the two masks (include/obe_hip.h: K6 for any rows): the words of their noise-only
+# twins, under the parameter names of their own prototypes
+_BOUNDS_RULES = {
+    "obe_mask_bounds_moments": (_mask_moments, "n_dims", "h_first_moments", "h_count"),
+    "obe_mask_bounds": (_delivered(words=1), "h_count"),
 }
 
 audit = _Audit() if os.environ.get("OBE_CHECK_DELIVERY") == "1" else _NoAudit()

@@ -167,7 +167,10 @@ def snapshot(obj, on_device=False):
                   last_setting_index=obj.last_setting_index, measurement_results=obj.measurement_results,
                   utility_y_space=np.array(obj.utility_y_space), last_sweep=obj.__dict__.get("last_sweep"),
                   sharded_sweeps=int(obj._sharded_sweeps),
-                  parameters=None if obj._parameters is pm else _mirror_state(obj._parameters, on_device))
+                  parameters=None if obj._parameters is pm else _mirror_state(obj._parameters, on_device),
+                  parameter_bounds=obj.parameter_bounds)
+        if "_changed_pinned" in obj.__dict__:
+            st["constraint_count"] = obj.last_constraint_count
         s = obj._sweeps
         # (the counters that decide the next sweep's form and shift; versions are kept as "is it this cloud")
         st["sweeps"] = dict(safe_streak=s.safe_streak, safe_run=s.safe_run, unshifted=s.unshifted, streak=s.streak,
@@ -274,7 +277,9 @@ def restore(state, device=None, settings_shard=None, into=None):
         s.streak, s.resample_rate, s.unavailable = sw["streak"], sw["resample_rate"], sw["unavailable"]
         s.range_hint_key = pm.version if sw["range_hint_seen"] else None
         s.updated_cloud = cloud if sw["updated_cloud"] else None
-    if isinstance(obj, OptBayesExptNoiseParameter):
+        # (a state written before there were bounds has none)
+        obj._adopt_bounds(state.get("parameter_bounds"))
+    if "constraint_count" in state:
         changed = obj._changed_pinned = _lib.pinned_array(1, np.int64)
         changed[0] = state["constraint_count"]
         obj._constraint_pending = False

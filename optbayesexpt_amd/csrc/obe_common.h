@@ -238,6 +238,47 @@ __device__ __forceinline__ double nan_to_num(double v) {
     return v;
 }
 
+// ---- declarative parameter bounds (OptBayesExpt.set_parameter_bounds; the constraint hooks of obe_noiseparam.py:57-79
+// and demos/lockin/lockin_of_coil.py:115-133).  "This value violates its bound", stated once for mask_bounds_kernel
+// (obe_update_common.hip) and the bounded gather (obe_resample.hip).  open: bit 0 = the lower bound itself violates
+// (v <= lo instead of v < lo), bit 1 = the upper one; an absent end is -inf / +inf, inclusive.  Every comparison is
+// false for a NaN value: it violates nothing, as in the reference's idioms.
+__device__ __forceinline__ bool outside_bounds(double v, double lo, double hi, int open) {
+    const bool below = (open & 1) ? v <= lo : v < lo;
+    const bool above = (open & 2) ? v >= hi : v > hi;
+    return below || above;
+}
+
+// the bounded rows of a call, by value in the kernel arguments (as RowsArg)
+struct BoundsArg {
+    int n;
+    int rows[OBE_MAX_DIMS];
+    double lo[OBE_MAX_DIMS], hi[OBE_MAX_DIMS];
+    unsigned char open[OBE_MAX_DIMS];
+};
+// 0, or the refusal (-1): a NULL array, n_rows outside 1..OBE_MAX_DIMS, a row outside [0, n_dims_limit) — the kernels
+// index the cloud with these —, a NaN bound, lower > upper
+inline int make_bounds_arg(BoundsArg& ba, const int32_t* h_rows, const double* h_lower, const double* h_upper,
+                           const int32_t* h_open, int n_rows, int n_dims_limit) {
+    if (!h_rows || !h_lower || !h_upper || !h_open) return bad_arg("parameter bounds: null pointer");
+    if (n_rows < 1 || n_rows > OBE_MAX_DIMS) return bad_arg("parameter bounds: n_rows outside 1..OBE_MAX_DIMS");
+    ba = BoundsArg{};
+    ba.n = n_rows;
+    for (int k = 0; k < n_rows; ++k) {
+        if (h_rows[k] < 0 || h_rows[k] >= n_dims_limit) return bad_arg("parameter bounds: row index out of range");
+        if (h_lower[k] != h_lower[k] || h_upper[k] != h_upper[k]) return bad_arg("parameter bounds: NaN bound");
+        if (h_lower[k] > h_upper[k]) return bad_arg("parameter bounds: lower > upper");
+        ba.rows[k] = h_rows[k];
+        ba.lo[k] = h_lower[k];
+        ba.hi[k] = h_upper[k];
+        // (an infinite end is an absent one: nothing is excluded there, whatever its flag says)
+        const int lower_open = h_lower[k] > -INFINITY ? h_open[k] & 1 : 0;
+        const int upper_open = h_upper[k] < INFINITY ? h_open[k] & 2 : 0;
+        ba.open[k] = (unsigned char)(lower_open | upper_open);
+    }
+    return 0;
+}
+
 // ---- reductions: wave shuffle, then 4 partials through LDS; fixed order => deterministic
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

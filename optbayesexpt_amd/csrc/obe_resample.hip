@@ -390,13 +390,23 @@ __global__ __launch_bounds__(kBlock) void soa_to_aos_kernel(const double* __rest
 // the partial sums of the weights and of the zeroed count that mask_kernel (obe_update.hip) would leave —
 // the same grid, the same per-thread order, the same block reductions: the same bits — for
 // obe_mask_renorm_moments().  One launch and one pass over the noise rows and the weights less.
-template <int D, bool AOS, bool MASK = false>
+// BOUNDS (one GatherBounds behind the other arguments, with MASK and mask_bits = 0; every other instantiation has an
+// empty pack and its former arguments): the same for declarative bounds on any rows (OptBayesExpt.set_parameter_bounds,
+// obe_resample_particles_aos_bounded) — a new particle that is outside_bounds() on any row gets weight 0; the
+// partial sums, and everything behind them, are the MASK branch's own.
+struct GatherBounds {                      // one entry per row of the cloud; an unbounded row is [-inf, +inf]
+    double lo[kFastDims], hi[kFastDims];
+    unsigned char open[kFastDims];
+};
+
+template <int D, bool AOS, bool MASK = false, class... BOUNDS>
 __global__ __launch_bounds__(kBlock) void resample_kernel(NudgeArgs na, const double* __restrict__ old, int64_t ld_old,
                                                           int64_t n, const int64_t* __restrict__ idx,
                                                           const double* __restrict__ z, double* __restrict__ out,
                                                           int64_t ld_new, double* __restrict__ weights,
                                                           unsigned mask_bits = 0u, double* __restrict__ psum = nullptr,
-                                                          double* __restrict__ pcount = nullptr) {
+                                                          double* __restrict__ pcount = nullptr, BOUNDS... gb) {
+    static_assert(MASK || sizeof...(BOUNDS) == 0, "the bounded gather leaves its partial sums through the MASK branch");
     // the (N, D) row-major normals of a workgroup's 256 particles are one contiguous run: read it
     // lane-contiguously into LDS (a thread reading its own row makes every load touch 64 lines)
     __shared__ double zs[kBlock * D];
@@ -443,6 +453,7 @@ __global__ __launch_bounds__(kBlock) void resample_kernel(NudgeArgs na, const do
             }
             out[(int64_t)i * ld_new + p] = v;
             if constexpr (MASK) bad = bad || (((mask_bits >> i) & 1u) && v <= 0.0);
+            bad = bad || (... || outside_bounds(v, gb.lo[i], gb.hi[i], gb.open[i]));      // (an empty pack: false)
         }
         if constexpr (MASK) {
             const double w = bad ? 0.0 : na.uniform_w;
@@ -497,9 +508,14 @@ __global__ __launch_bounds__(kBlock) void resample_wide_kernel(const double* __r
 template <int D>
 static int launch_resample(const NudgeArgs& na, const double* d_old, int64_t ld_old, int64_t n, const int64_t* d_idx,
                            const double* d_normals, double* d_new, int64_t ld_new, double* d_weights, void* d_ws,
-                           int64_t ws_bytes, hipStream_t st, unsigned mask_bits = 0u, double* d_mask_partials = nullptr) {
+                           int64_t ws_bytes, hipStream_t st, unsigned mask_bits = 0u, double* d_mask_partials = nullptr,
+                           const GatherBounds* bounds = nullptr) {
     const int blocks = stream_blocks(n, kBlock);
-    if (!d_old && mask_bits) {
+    if (!d_old && bounds) {
+        resample_kernel<D, true, true, GatherBounds><<<blocks, kBlock, 0, st>>>(
+            na, static_cast<const double*>(d_ws), 0, n, d_idx, d_normals, d_new, ld_new, d_weights, 0u, d_mask_partials,
+            d_mask_partials + kMaxBlocks, *bounds);
+    } else if (!d_old && mask_bits) {
         resample_kernel<D, true, true><<<blocks, kBlock, 0, st>>>(na, static_cast<const double*>(d_ws), 0, n, d_idx,
                                                                   d_normals, d_new, ld_new, d_weights, mask_bits,
                                                                   d_mask_partials, d_mask_partials + kMaxBlocks);
@@ -682,7 +698,7 @@ static int resample_particles(const double* d_old, int64_t ld_old, int32_t n_dim
                               const int64_t* d_idx, const double* d_normals, const double* h_factor,
                               const double* h_mean, double a_param, int32_t scale, double* d_new, int64_t ld_new,
                               double* d_weights, void* d_ws, int64_t ws_bytes, void* stream, unsigned mask_bits = 0u,
-                              double* d_mask_partials = nullptr);
+                              double* d_mask_partials = nullptr, const GatherBounds* bounds = nullptr);
 
 int obe_resample_particles(const double* d_old, int64_t ld_old, int32_t n_dims, int64_t n_particles,
                            const int64_t* d_idx, const double* d_normals, const double* h_factor,
@@ -719,11 +735,48 @@ int obe_resample_particles_aos_masked(const double* d_old_aos, int32_t n_dims, i
                               ld_new, d_weights, const_cast<double*>(d_old_aos), 0, stream, bits, d_mask_partials);
 }
 
+// The masked gather for declarative bounds (obe_noiseparam.py:57-79, demos/lockin/lockin_of_coil.py:115-133): the
+// bounds of the call, one entry per bounded row, become one interval per row of the cloud (several entries for a row
+// intersect; at equal values the exclusive end is the narrower one)
+int obe_resample_particles_aos_bounded(const double* d_old_aos, int32_t n_dims, int64_t n_particles,
+                                       const int64_t* d_idx, const double* d_normals, const double* h_factor,
+                                       const double* h_mean, double a_param, int32_t scale, double* d_new,
+                                       int64_t ld_new, double* d_weights, const int32_t* h_rows, const double* h_lower,
+                                       const double* h_upper, const int32_t* h_open, int32_t n_rows,
+                                       double* d_mask_partials, void* stream) {
+    if (!d_old_aos || d_old_aos == d_new || !d_mask_partials || n_dims < 1 || n_dims > kFastDims)
+        return bad_arg("obe_resample_particles_aos_bounded: bad pointer/size");
+    BoundsArg ba;
+    if (int rc = make_bounds_arg(ba, h_rows, h_lower, h_upper, h_open, n_rows, n_dims)) return rc;
+    GatherBounds gb{};
+    for (int i = 0; i < kFastDims; ++i) {
+        gb.lo[i] = -INFINITY;
+        gb.hi[i] = INFINITY;
+    }
+    for (int k = 0; k < ba.n; ++k) {
+        const int i = ba.rows[k];
+        if (ba.lo[k] > gb.lo[i]) {
+            gb.lo[i] = ba.lo[k];
+            gb.open[i] = (gb.open[i] & 2) | (ba.open[k] & 1);
+        } else if (ba.lo[k] == gb.lo[i]) {
+            gb.open[i] |= ba.open[k] & 1;
+        }
+        if (ba.hi[k] < gb.hi[i]) {
+            gb.hi[i] = ba.hi[k];
+            gb.open[i] = (gb.open[i] & 1) | (ba.open[k] & 2);
+        } else if (ba.hi[k] == gb.hi[i]) {
+            gb.open[i] |= ba.open[k] & 2;
+        }
+    }
+    return resample_particles(nullptr, 0, n_dims, n_particles, d_idx, d_normals, h_factor, h_mean, a_param, scale, d_new,
+                              ld_new, d_weights, const_cast<double*>(d_old_aos), 0, stream, 0u, d_mask_partials, &gb);
+}
+
 static int resample_particles(const double* d_old, int64_t ld_old, int32_t n_dims, int64_t n_particles,
                               const int64_t* d_idx, const double* d_normals, const double* h_factor,
                               const double* h_mean, double a_param, int32_t scale, double* d_new, int64_t ld_new,
                               double* d_weights, void* d_ws, int64_t ws_bytes, void* stream, unsigned mask_bits,
-                              double* d_mask_partials) {
+                              double* d_mask_partials, const GatherBounds* bounds) {
     if (!d_idx || !d_normals || !h_factor || !h_mean || !d_new || !d_weights || n_particles <= 0)
         return bad_arg("obe_resample_particles: bad pointer/size");
     if (n_dims < 1 || n_dims > OBE_CLOUD_MAX_DIMS) return bad_arg("obe_resample_particles: n_dims must be 1..1024");
@@ -752,7 +805,7 @@ static int resample_particles(const double* d_old, int64_t ld_old, int32_t n_dim
     hipStream_t st = as_stream(stream);
     return dispatch_dims(n_dims, "obe_resample_particles: n_dims must be 1..16", [&](auto D) -> int {
         return launch_resample<decltype(D)::value>(na, d_old, ld_old, n_particles, d_idx, d_normals, d_new, ld_new,
-                                                   d_weights, d_ws, ws_bytes, st, mask_bits, d_mask_partials);
+                                                   d_weights, d_ws, ws_bytes, st, mask_bits, d_mask_partials, bounds);
     });
 }
 

@@ -268,6 +268,36 @@ __global__ __launch_bounds__(kBlock) void mask_kernel(RowsArg ra, const double* 
     }
 }
 
+// The same first half for declarative bounds on any rows (OptBayesExpt.set_parameter_bounds): mask_kernel's grid,
+// per-thread order and block reductions, so that everything behind it — fold2_kernel, mask_renorm_kernel,
+// mask_renorm_moments_kernel — is shared and a given set of violators leaves the same bits whichever kernel found it.
+// An HBM stream of 8 (bounded rows + 2) bytes per particle.
+__global__ __launch_bounds__(kBlock) void mask_bounds_kernel(BoundsArg ba, const double* __restrict__ particles,
+                                                             int64_t ld, int64_t n, double* __restrict__ weights,
+                                                             double* __restrict__ psum, double* __restrict__ pcount) {
+    __shared__ double red[kBlock / kWave];
+    double acc = 0.0, cnt = 0.0;
+    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kBlock) {
+        bool bad = false;
+        for (int k = 0; k < ba.n; ++k)
+            bad = bad || outside_bounds(particles[(int64_t)ba.rows[k] * ld + p], ba.lo[k], ba.hi[k], ba.open[k]);
+        double w = weights[p];
+        if (bad) {
+            w = 0.0;
+            weights[p] = 0.0;
+            cnt += 1.0;
+        }
+        acc += w;
+    }
+    const double s = block_sum(acc, red);
+    __syncthreads();
+    const double c = block_sum(cnt, red);
+    if (threadIdx.x == 0) {
+        psum[blockIdx.x] = s;
+        pcount[blockIdx.x] = c;
+    }
+}
+
 // renormalise only if anything was zeroed (scalars[1] = count)
 // (host_changed: the device view of the caller's page-locked count, or NULL)
 __global__ __launch_bounds__(kBlock) void mask_renorm_kernel(const double* __restrict__ scalars, int64_t n,
@@ -801,6 +831,65 @@ int obe_mask_nonpositive_moments(const double* d_particles, int64_t ld_p, int32_
     const int nb = stream_blocks(n_particles, kBlock);
     mask_kernel<<<nb, kBlock, 0, st>>>(ra, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
     OBE_CHECK_LAUNCH("mask_kernel");
+    return mask_renorm_moments(d_particles, ld_p, n_dims, n_particles, w.pa, w.pb, nb, d_weights, d_moments, moments,
+                               changed, counter, w.mom, st);
+}
+
+// ---- declarative bounds on any parameter rows: obe_mask_nonpositive / obe_mask_nonpositive_moments with
+// mask_bounds_kernel in front of the same second halves
+int obe_mask_bounds(const double* d_particles, int64_t ld_p, int64_t n_particles, const int32_t* h_rows,
+                    const double* h_lower, const double* h_upper, const int32_t* h_open, int32_t n_rows,
+                    double* d_weights, int64_t* h_count, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_particles || !d_weights || n_particles <= 0 || ld_p < n_particles)
+        return bad_arg("obe_mask_bounds: bad pointer/size");
+    BoundsArg ba;
+    if (int rc = make_bounds_arg(ba, h_rows, h_lower, h_upper, h_open, n_rows, OBE_CLOUD_MAX_DIMS)) return rc;
+    UpdateWs w;
+    if (int rc = carve_update_ws(d_ws, ws_bytes, w)) return rc;
+    hipStream_t st = as_stream(stream);
+    const int nb = stream_blocks(n_particles, kBlock);
+    HostWords changed(h_count, 1);
+    changed.arm();
+    mask_bounds_kernel<<<nb, kBlock, 0, st>>>(ba, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
+    OBE_CHECK_LAUNCH("mask_bounds_kernel");
+    fold2_kernel<<<1, kBlock, 0, st>>>(w.pa, w.pb, nb, w.scalars, nullptr);
+    OBE_CHECK_LAUNCH("fold2_kernel");
+    mask_renorm_kernel<<<nb, kBlock, 0, st>>>(w.scalars, n_particles, d_weights, changed.view<int64_t>());
+    OBE_CHECK_LAUNCH("mask_renorm_kernel");
+    if (!h_count || changed.view<int64_t>()) return changed.wait(st);        // (as obe_mask_nonpositive)
+    double sc[2];
+    OBE_HIP_TRY(hipMemcpyAsync(sc, w.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    OBE_HIP_TRY(hipStreamSynchronize(st));
+    *h_count = (int64_t)sc[1];
+    return 0;
+}
+
+int obe_mask_bounds_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                            const int32_t* h_rows, const double* h_lower, const double* h_upper,
+                            const int32_t* h_open, int32_t n_rows, double* d_weights, double* d_moments,
+                            double* h_first_moments, int64_t* h_count, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_particles || !d_weights || !d_moments || n_particles <= 0 || ld_p < n_particles)
+        return bad_arg("obe_mask_bounds_moments: bad pointer/size");
+    if (n_dims < 1 || n_dims > OBE_CLOUD_MAX_DIMS) return bad_arg("obe_mask_bounds_moments: n_dims must be 1..1024");
+    BoundsArg ba;
+    if (int rc = make_bounds_arg(ba, h_rows, h_lower, h_upper, h_open, n_rows, n_dims)) return rc;
+    UpdateWs w;
+    if (int rc = carve_update_ws(d_ws, ws_bytes, w)) return rc;      // (what either route needs at least)
+    hipStream_t st = as_stream(stream);
+    unsigned* counter = stream_control_words(st);
+    HostWords changed(h_count, 1), moments(h_first_moments, 2 + 4 * (int64_t)n_dims);
+    if (!counter || (h_count && !changed.view<void>()) || (h_first_moments && !moments.view<void>()) || n_dims > kFastDims) {
+        // (as obe_mask_nonpositive_moments: the two separate calls, synchronous)
+        if (int rc = obe_mask_bounds(d_particles, ld_p, n_particles, h_rows, h_lower, h_upper, h_open, n_rows, d_weights,
+                                     h_count, d_ws, ws_bytes, stream))
+            return rc;
+        return obe_moments(d_particles, ld_p, n_dims, n_particles, d_weights, 0, d_moments, h_first_moments, d_ws, ws_bytes,
+                           stream);
+    }
+    if (int rc = carve_update_ws(d_ws, ws_bytes, w, n_dims)) return rc;
+    const int nb = stream_blocks(n_particles, kBlock);
+    mask_bounds_kernel<<<nb, kBlock, 0, st>>>(ba, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
+    OBE_CHECK_LAUNCH("mask_bounds_kernel");
     return mask_renorm_moments(d_particles, ld_p, n_dims, n_particles, w.pa, w.pb, nb, d_weights, d_moments, moments,
                                changed, counter, w.mom, st);
 }

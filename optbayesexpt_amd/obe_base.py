@@ -33,7 +33,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _devrng, _lib, _predictive
+from . import _bounds, _devrng, _lib, _predictive
 from ._sweepstate import Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
@@ -70,6 +70,12 @@ def _overridden(obj, name, *owners):
     if hit is None or hit[0] is not impl:       # (a method patched onto the class later is seen too)
         hit = _OVERRIDDEN[key] = (impl, all(impl is not getattr(o, name) for o in owners))
     return hit[1]
+
+
+def _constraint_owners():
+    """The classes of this package that define enforce_parameter_constraints() (the device masks)."""
+    from .obe_noiseparam import OptBayesExptNoiseParameter
+    return OptBayesExpt, OptBayesExptNoiseParameter
 
 
 class _LazyState:
@@ -471,6 +477,22 @@ class OptBayesExpt(ParticlePDF):
     def pdf_update(self, measurement_record, y_model_data=None):
         """Bayesian update of the parameter distribution from one measurement
         (obe_base.py:340-399).  Returns ``(particles, particle_weights)``."""
+        # (inside: the resample that resample_test() reports is followed by enforce_parameter_constraints() —
+        # see _resample_mask_rows)
+        self._constraint_follows = True
+        try:
+            return self._pdf_update(measurement_record, y_model_data)
+        finally:
+            self._constraint_follows = False
+            masked = self.__dict__.get("_masked_by_gather")
+            if masked is not None:
+                # a gather masked the weights and no enforce_parameter_constraints() consumed it (an exception between
+                # the two): what the reference's resample() leaves behind is uniform weights (particlepdf.py:308-309)
+                self._masked_by_gather = None
+                if masked == (self._particles.version, self._weights.version):
+                    self.particle_weights = np.ones(self.n_particles) / self.n_particles
+
+    def _pdf_update(self, measurement_record, y_model_data):
         onesetting = measurement_record[0]
         fused = (self._device_model is not None and y_model_data is None
                  and not _overridden(self, "eval_over_all_parameters", OptBayesExpt)
@@ -678,9 +700,130 @@ class OptBayesExpt(ParticlePDF):
         rows = [np.broadcast_to(np.asarray(r, dtype=np.float64), (self.n_particles,)) for r in y_model_data]
         return torch.from_numpy(np.array(rows[:self.n_channels], dtype=np.float64)).to(self._device)
 
+    # ------------------------------------------------------- parameter constraints
+    # The reference's one hook to keep a posterior physical (obe_base.py:401-416), called by pdf_update() right after
+    # every resample.  Its callers fill it with a NumPy loop over the cloud (obe_noiseparam.py:57-79: sigma <= 0;
+    # demos/lockin/lockin_of_coil.py:115-133: any parameter < 0); such an override still works here, through the host
+    # mirrors.  A constraint that is a box per parameter row is given as data instead and stays on the device.
+    def set_parameter_bounds(self, bounds, inclusive=True):
+        """Bounds that ``enforce_parameter_constraints()`` applies on the device after every resample: particles with
+        a parameter outside them get zero weight, and the weights are divided by their new sum if anything was zeroed
+        (the reference's semantics, obe_noiseparam.py:65-79; if EVERY particle violates, the weights become NaN, as
+        0/0 does there).  ``bounds``: a mapping row -> ``(lower, upper)`` or one such pair (or None) per row, an end
+        that is None or infinite being absent; None clears.  Rows may be negative, as in NumPy.  ``inclusive=True``:
+        a value violates by ``v < lower or v > upper``; ``False``: by ``v <= lower or v >= upper``; or per row (a
+        mapping or sequence) a bool or ``(bool_lower, bool_upper)``.  A NaN value never violates.  At most
+        OBE_MAX_DIMS rows may be bounded.  Coupled constraints (``L * C < 1``) remain a hook's business."""
+        self._adopt_bounds(_bounds.normalize(bounds, self.n_dims, inclusive))
+
+    def _adopt_bounds(self, normal):
+        packed = _bounds.pack(self._effective_bounds(normal))       # (refusals first: nothing is kept of a bad call)
+        self._parameter_bounds = normal
+        self._bounds_call = None if packed is None else packed + tuple(_lib.host_ptr(a) for a in packed) \
+            + (int(packed[0].size),)
+
+    @property
+    def parameter_bounds(self):
+        """``(lower, upper, lower_open, upper_open)`` arrays of ``n_dims`` as given (-inf / +inf: no bound), or None."""
+        b = self.__dict__.get("_parameter_bounds")
+        return None if b is None else tuple(a.copy() for a in b)
+
+    def _effective_bounds(self, normal):
+        """The bounds that are enforced for the user's ``normal`` ones (the noise-parameter class adds its own)."""
+        return normal
+
+    def _device_constraint(self):
+        """(mask entry point, gather entry point, their constraint arguments, lazy wide moments), or None: the
+        constraint this class's own enforce_parameter_constraints() applies.  The arguments are the ones in front of
+        ``d_weights`` in obe_mask_bounds[_moments] and behind it in obe_resample_particles_aos_bounded; the last
+        item says that a cloud wider than OBE_FAST_DIMS takes the mask alone (its moments are computed when they are
+        asked for) instead of the _moments form's synchronous pair of calls."""
+        call = self.__dict__.get("_bounds_call")
+        if call is None:
+            return None
+        return "obe_mask_bounds", "obe_resample_particles_aos_bounded", call[4:], True
+
     def enforce_parameter_constraints(self):
-        """Stub for subclasses (obe_base.py:401-416); called after each resample."""
-        pass
+        """Called after each resample (obe_base.py:401-416).  Without bounds: nothing, the reference's stub.  With
+        ``set_parameter_bounds()``: the device mask — two launches that also leave the first moments of the
+        constrained cloud (the next sweep's shift and noise variance need them), one if the gather of the resample
+        has applied the bounds already; nothing is waited for, ``last_constraint_count`` reads the count when asked."""
+        constraint = self._device_constraint()
+        if constraint is None:
+            return
+        mask, _, cargs, lazy_wide = constraint
+        self._await_host_moments()        # (a second call in a row re-arms the words the first one delivers into)
+        par = self._parameters.tensor()
+        w = self._weights.tensor()
+        changed = self.__dict__.get("_changed_pinned")
+        if changed is None:
+            changed = self._changed_pinned = _lib.pinned_array(1, np.int64)
+        masked = self.__dict__.get("_masked_by_gather")
+        self._masked_by_gather = None
+        if self._parameters is self._particles and not (lazy_wide and self.n_dims > _lib.OBE_FAST_DIMS):
+            done = False
+            if masked is not None and masked == (self._particles.version, self._weights.version):
+                # the gather of the resample that pdf_update() has just run zeroed these weights already and left
+                # the partial sums: only the renormalisation + first moments remain (one launch instead of two)
+                try:
+                    self._lib.call("obe_mask_renorm_moments", _ptr(par), par.shape[1], self.n_dims, self.n_particles,
+                                   _ptr(self._mask_partials), _ptr(w), _ptr(self._moments_dev),
+                                   self._hargs.ptr_keep(self._moments_host), _lib.host_ptr(changed), _ptr(self._ws),
+                                   self._ws_bytes, self._stream())
+                    done = True
+                except _lib.ObeHipError as exc:
+                    if not exc.refused_before_launch:
+                        raise
+                    # (refused before any launch: the full form below finds the same particles)
+            if not done:
+                self._lib.call(mask + "_moments", _ptr(par), par.shape[1], self.n_dims, self.n_particles, *cargs,
+                               _ptr(w), _ptr(self._moments_dev), self._hargs.ptr_keep(self._moments_host),
+                               _lib.host_ptr(changed), _ptr(self._ws), self._ws_bytes, self._stream())
+            self._constraint_pending = True
+            # (weights may have changed: a new version either way; the moments describe exactly them)
+            self._weights.mark_device_written()
+            self._mom_host_key = self._mom_dev_key = (self._particles.version, self._weights.version, False)
+            # (the host copy is complete once every word of it — and the count — has arrived: armed by the call)
+            self._mom_host_wait = ((self._hargs.ptr_keep(self._moments_host), self._layout.first_len),
+                                   (_lib.host_ptr(changed), 1))
+        else:
+            # a stale `parameters` alias (set_pdf between updates): the mask alone, on those rows; a cloud wider than
+            # OBE_FAST_DIMS: the mask alone as well, the moments are computed when they are asked for
+            self._lib.call(mask, _ptr(par), par.shape[1], self.n_particles, *cargs, _ptr(w), _lib.host_ptr(changed),
+                           _ptr(self._ws), self._ws_bytes, self._stream())
+            self._constraint_pending = False
+            if changed[0]:
+                self._weights.mark_device_written()
+
+    def _resample_mask_rows(self):
+        """The gather of a resample may apply this class's constraint itself when that constraint is certain to
+        follow: the resample is the one resample_test() runs and reports through ``just_resampled``, inside this
+        class's pdf_update() (which then calls enforce_parameter_constraints() — a resample() reached any other way,
+        on its own or from an overriding hook, must leave uniform weights, like the reference's), every hook on that
+        path is the class's own, and tuning_parameters['mask_in_gather'] (default True) does not say otherwise.
+        Returns (gather entry point, its constraint arguments), or None."""
+        if not self.__dict__.get("_constraint_follows") or not self.__dict__.get("_in_reported_resample") \
+                or not self.tuning_parameters.get("mask_in_gather", True):
+            return None
+        constraint = self._device_constraint()
+        if constraint is None or self.n_dims > _lib.OBE_FAST_DIMS \
+                or _overridden(self, "enforce_parameter_constraints", *_constraint_owners()) \
+                or _overridden(self, "resample_test", ParticlePDF) or _overridden(self, "resample", ParticlePDF) \
+                or _overridden(self, "bayesian_update", ParticlePDF):
+            return None           # (a replaced hook might resample without reporting it: no constraint would follow)
+        return constraint[1], constraint[2]
+
+    @property
+    def last_constraint_count(self):
+        """Particles the most recent enforce_parameter_constraints() gave zero weight (waits for the
+        kernel that counts them if it has not delivered yet)."""
+        changed = self.__dict__.get("_changed_pinned")
+        if changed is None:
+            return 0
+        if self.__dict__.get("_constraint_pending"):
+            self._lib.call("obe_host_word_wait", _lib.host_ptr(changed), self._stream())
+            self._constraint_pending = False
+        return int(changed[0])
 
     def likelihood(self, y_model, measurement_record):
         """Gaussian likelihood of the measurement for every parameter sample

@@ -8,9 +8,9 @@ three run in libobe_hip kernels (K2 with ``h_noise_rows``, the K3 moment block, 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _bounds, _lib
 from .obe_base import OptBayesExpt, _overridden
-from .particlepdf import ParticlePDF, _ptr
+from .particlepdf import _ptr
 
 
 class OptBayesExptNoiseParameter(OptBayesExpt):
@@ -47,95 +47,23 @@ class OptBayesExptNoiseParameter(OptBayesExpt):
         return OptBayesExpt.likelihood(self, y_model, measurement_record)
 
     # -- constraint: sigma > 0 (obe_noiseparam.py:57-79) ------------------------------
-    def enforce_parameter_constraints(self):
-        """Zero the weight of every particle whose noise parameter is <= 0 and
-        renormalise; called by ``pdf_update`` right after a resample.  The same two launches leave the
-        first moments of the constrained cloud behind (the next sweep's shift and noise variance need
-        them), and nothing is waited for: ``last_constraint_count`` reads the count when asked."""
-        self._await_host_moments()        # (a second call in a row re-arms the words the first one delivers into)
-        par = self._parameters.tensor()
-        w = self._weights.tensor()
-        changed = self.__dict__.get("_changed_pinned")
-        if changed is None:
-            changed = self._changed_pinned = _lib.pinned_array(1, np.int64)
-        fused = self._parameters is self._particles
-        masked = self.__dict__.get("_masked_by_gather")
-        self._masked_by_gather = None
-        if fused:
-            done = False
-            if masked is not None and masked == (self._particles.version, self._weights.version):
-                # the gather of the resample that pdf_update() has just run zeroed these weights already and left
-                # the partial sums: only the renormalisation + first moments remain (one launch instead of two)
-                try:
-                    self._lib.call("obe_mask_renorm_moments", _ptr(par), par.shape[1], self.n_dims, self.n_particles,
-                                   _ptr(self._mask_partials), _ptr(w), _ptr(self._moments_dev),
-                                   self._hargs.ptr_keep(self._moments_host), _lib.host_ptr(changed), _ptr(self._ws),
-                                   self._ws_bytes, self._stream())
-                    done = True
-                except _lib.ObeHipError as exc:
-                    if not exc.refused_before_launch:
-                        raise
-                    # (refused before any launch: the full form below finds the same particles)
-            if not done:
-                self._lib.call("obe_mask_nonpositive_moments", _ptr(par), par.shape[1], self.n_dims, self.n_particles,
-                               _lib.host_ptr(self._noise_rows), self.n_channels, _ptr(w), _ptr(self._moments_dev),
-                               self._hargs.ptr_keep(self._moments_host), _lib.host_ptr(changed), _ptr(self._ws),
-                               self._ws_bytes, self._stream())
-            self._constraint_pending = True
-            # (weights may have changed: a new version either way; the moments describe exactly them)
-            self._weights.mark_device_written()
-            self._mom_host_key = self._mom_dev_key = (self._particles.version, self._weights.version, False)
-            # (the host copy is complete once every word of it — and the count — has arrived: armed by the call)
-            self._mom_host_wait = ((self._hargs.ptr_keep(self._moments_host), self._layout.first_len),
-                                   (_lib.host_ptr(changed), 1))
-        else:       # a stale `parameters` alias (set_pdf between updates): the mask alone, on those rows
-            self._lib.call("obe_mask_nonpositive", _ptr(par), par.shape[1], self.n_particles,
-                           _lib.host_ptr(self._noise_rows), self.n_channels, _ptr(w), _lib.host_ptr(changed),
-                           _ptr(self._ws), self._ws_bytes, self._stream())
-            self._constraint_pending = False
-            if changed[0]:
-                self._weights.mark_device_written()
+    # enforce_parameter_constraints(), the gather that applies the constraint itself and last_constraint_count are the
+    # base class's (obe_base.py): this class says which constraint.
+    def _effective_bounds(self, normal):
+        """The user's bounds AND this class's sigma > 0 on the noise rows, as one set of bounds."""
+        if normal is None:
+            return None
+        return _bounds.intersect_positive(normal, self._noise_rows[:self.n_channels])
 
-    def _resample_mask_rows(self):
-        """The gather of a resample may apply this class's constraint itself when that constraint is certain to
-        follow: the resample is the one resample_test() runs and reports through ``just_resampled``, inside this
-        class's pdf_update() (which then calls enforce_parameter_constraints() — a resample() reached any other way,
-        on its own or from an overriding hook, must leave uniform weights, like the reference's), every hook on that
-        path is the class's own, and tuning_parameters['mask_in_gather'] (default True) does not say otherwise."""
-        if not self.__dict__.get("_constraint_follows") or not self.__dict__.get("_in_reported_resample") \
-                or not self.tuning_parameters.get("mask_in_gather", True) \
-                or _overridden(self, "enforce_parameter_constraints", OptBayesExpt, OptBayesExptNoiseParameter) \
-                or _overridden(self, "resample_test", ParticlePDF) or _overridden(self, "resample", ParticlePDF) \
-                or _overridden(self, "bayesian_update", ParticlePDF):
-            return None           # (a replaced hook might resample without reporting it: no constraint would follow)
-        return self._noise_rows, self.n_channels
-
-    def pdf_update(self, measurement_record, y_model_data=None):
-        """obe_base.py:340-399 (the noise-parameter class inherits it); see _resample_mask_rows."""
-        self._constraint_follows = True
-        try:
-            return OptBayesExpt.pdf_update(self, measurement_record, y_model_data)
-        finally:
-            self._constraint_follows = False
-            masked = self.__dict__.get("_masked_by_gather")
-            if masked is not None:
-                # a gather masked the weights and no enforce_parameter_constraints() consumed it (an exception between
-                # the two): what the reference's resample() leaves behind is uniform weights (particlepdf.py:308-309)
-                self._masked_by_gather = None
-                if masked == (self._particles.version, self._weights.version):
-                    self.particle_weights = np.ones(self.n_particles) / self.n_particles
-
-    @property
-    def last_constraint_count(self):
-        """Particles the most recent enforce_parameter_constraints() gave zero weight (waits for the
-        kernel that counts them if it has not delivered yet)."""
-        changed = self.__dict__.get("_changed_pinned")
-        if changed is None:
-            return 0
-        if self.__dict__.get("_constraint_pending"):
-            self._lib.call("obe_host_word_wait", _lib.host_ptr(changed), self._stream())
-            self._constraint_pending = False
-        return int(changed[0])
+    def _device_constraint(self):
+        """Without bounds: zero the weight of every particle whose noise parameter is <= 0 and renormalise, by the
+        entry points written for exactly that (obe_mask_nonpositive*).  With set_parameter_bounds(): one mask of the
+        intersection (_effective_bounds), by the bounds' entry points."""
+        bounded = OptBayesExpt._device_constraint(self)
+        if bounded is not None:
+            return bounded
+        return ("obe_mask_nonpositive", "obe_resample_particles_aos_masked",
+                (self._hargs.ptr_keep(self._noise_rows), self.n_channels), False)
 
     # -- noise model: weighted mean of sigma^2 (obe_noiseparam.py:122-136) ------------
     def yvar_noise_model(self):

@@ -354,7 +354,7 @@ class ParticlePDF:
     def _resample_reported(self):
         """The resample of resample_test(): the only one whose outcome is reported through ``just_resampled`` — and
         therefore the only one a caller (OptBayesExpt.pdf_update) is certain to follow with its parameter
-        constraints (see OptBayesExptNoiseParameter._resample_mask_rows)."""
+        constraints (see OptBayesExpt._resample_mask_rows)."""
         self._in_reported_resample = True
         try:
             self.resample()
@@ -559,8 +559,8 @@ class ParticlePDF:
         return factor, mean
 
     def _resample_mask_rows(self):
-        """Hook: (int32 rows array, n) if a positivity constraint on those parameter rows is KNOWN to follow this
-        resample (OptBayesExptNoiseParameter inside pdf_update()): the gather then zeroes those weights itself."""
+        """Hook: (masked gather entry point, its constraint arguments) if a constraint on parameter rows is KNOWN to
+        follow this resample (OptBayesExpt inside pdf_update()): the gather then zeroes those weights itself."""
         return None
 
     def _resample_apply(self, idx, z_dev, factor, mean, aos=None, new=None):
@@ -577,10 +577,10 @@ class ParticlePDF:
             partials = self.__dict__.get("_mask_partials")
             if partials is None:          # {sum w, count} per workgroup of the gather: the object's own, not the workspace
                 partials = self._mask_partials = torch.empty(2 * 2048, dtype=torch.float64, device=self._device)
-            self._lib.call("obe_resample_particles_aos_masked", _ptr(aos), d, n, _ptr(idx), _ptr(z_dev),
+            self._lib.call(mask[0], _ptr(aos), d, n, _ptr(idx), _ptr(z_dev),
                            _lib.host_ptr(factor), _lib.host_ptr(mean), float(self.tuning_parameters["a_param"]),
-                           1 if self.tuning_parameters["scale"] else 0, _ptr(new), n, _ptr(w), _lib.host_ptr(mask[0]),
-                           mask[1], _ptr(partials), self._stream())
+                           1 if self.tuning_parameters["scale"] else 0, _ptr(new), n, _ptr(w), *mask[1],
+                           _ptr(partials), self._stream())
         elif aos is not None:
             self._lib.call("obe_resample_particles_aos", _ptr(aos), d, n, _ptr(idx), _ptr(z_dev),
                            _lib.host_ptr(factor), _lib.host_ptr(mean), float(self.tuning_parameters["a_param"]),
