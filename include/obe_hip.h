@@ -338,7 +338,9 @@ OBE_API int obe_resample_particles_aos(const double* d_old_aos, int32_t n_dims, 
  * whose parameter h_rows[k] <= 0 for any k gets weight 0 instead of 1/N, and d_mask_partials (2 x 2048 doubles,
  * the caller's) receives the partial sums {sum w, count} that obe_mask_nonpositive()'s first kernel would leave —
  * same grid, same order, same bits — for obe_mask_renorm_moments().  ONLY for a resample that the constraint
- * follows: the reference's resample() on its own leaves uniform weights. */
+ * follows: the reference's resample() on its own leaves uniform weights.  This is
+ * obe_resample_particles_aos_bounded with the bound (0, +inf) on the given rows (rows in [0, n_dims), at most
+ * OBE_FAST_DIMS of them). */
 OBE_API int obe_resample_particles_aos_masked(const double* d_old_aos, int32_t n_dims, int64_t n_particles,
                                       const int64_t* d_idx, const double* d_normals,
                                       const double* h_factor, const double* h_mean,
@@ -349,8 +351,9 @@ OBE_API int obe_resample_particles_aos_masked(const double* d_old_aos, int32_t n
 /* The masked gather for declarative bounds on any parameter rows (OptBayesExpt.set_parameter_bounds; the hooks of
  * obe_noiseparam.py:57-79 and demos/lockin/lockin_of_coil.py:115-133 as data): a new particle whose row h_rows[k]
  * lies outside [h_lower[k], h_upper[k]] for any k — see obe_mask_bounds for h_open and the refusals, rows in
- * [0, n_dims) — gets weight 0 instead of 1/N.  d_mask_partials receives the same {sum w, count} partials as
- * obe_resample_particles_aos_masked leaves, for the same obe_mask_renorm_moments().  n_dims <= OBE_FAST_DIMS. */
+ * [0, n_dims) — gets weight 0 instead of 1/N.  d_mask_partials (2 x 2048 doubles, the caller's) receives the partial
+ * sums {sum w, count} that obe_mask_bounds()'s first kernel would leave — same grid, same order, same bits — for
+ * obe_mask_renorm_moments().  n_dims <= OBE_FAST_DIMS. */
 OBE_API int obe_resample_particles_aos_bounded(const double* d_old_aos, int32_t n_dims, int64_t n_particles,
                                        const int64_t* d_idx, const double* d_normals,
                                        const double* h_factor, const double* h_mean,
@@ -385,7 +388,9 @@ OBE_API int obe_resample_begin(const double* d_particles, int64_t ld_p, int32_t 
 /* ---- K6: OptBayesExptNoiseParameter extras ----
  * enforce_parameter_constraints (obe_noiseparam.py:57-79): zero the weight of every
  * particle whose row h_rows[k] <= 0 for any k, renormalise if anything changed.
- * *h_changed = number of particles zeroed (sync). */
+ * *h_changed = number of particles zeroed (sync).  obe_mask_nonpositive and obe_mask_nonpositive_moments are
+ * obe_mask_bounds and obe_mask_bounds_moments (below) with the bound (0, +inf) on the given rows, under their own
+ * argument checks. */
 OBE_API int obe_mask_nonpositive(const double* d_particles, int64_t ld_p, int64_t n_particles,
                          const int32_t* h_rows, int32_t n_rows, double* d_weights,
                          int64_t* h_changed, void* d_ws, int64_t ws_bytes, void* stream);
@@ -426,8 +431,7 @@ OBE_API int obe_noise_var_from_moments(const double* d_moments, int32_t n_dims, 
  * [0, OBE_CLOUD_MAX_DIMS) — [0, n_dims) where the call has n_dims —, a NaN bound, lower > upper, ld_p < n_particles.
  * *h_count = number of particles zeroed (sync).  (h_count / h_first_moments are obe_mask_nonpositive*'s h_changed /
  * h_moments: the delivery audit keeps its rules for these two calls in a table of their own, _audit._BOUNDS_RULES,
- * and reads the arguments by these names.)  Same grid, order and second half as obe_mask_nonpositive: the
- * same set of violators leaves the same bits. */
+ * and reads the arguments by these names.) */
 OBE_API int obe_mask_bounds(const double* d_particles, int64_t ld_p, int64_t n_particles,
                     const int32_t* h_rows, const double* h_lower, const double* h_upper, const int32_t* h_open,
                     int32_t n_rows, double* d_weights, int64_t* h_count, void* d_ws, int64_t ws_bytes,

@@ -384,29 +384,56 @@ __global__ __launch_bounds__(kBlock) void soa_to_aos_kernel(const double* __rest
 }
 
 // AOS: `old` is the (N, D) copy made by soa_to_aos_kernel (ld_old unused)
-// MASK (round 5): the first half of OptBayesExptNoiseParameter.enforce_parameter_constraints
-// (obe_noiseparam.py:57-79), which pdf_update() calls right after this resample, done here: a new particle
-// whose parameter `row` <= 0 for any row of mask_bits gets weight 0 instead of 1/N, and the workgroup leaves
-// the partial sums of the weights and of the zeroed count that mask_kernel (obe_update.hip) would leave —
-// the same grid, the same per-thread order, the same block reductions: the same bits — for
-// obe_mask_renorm_moments().  One launch and one pass over the noise rows and the weights less.
-// BOUNDS (one GatherBounds behind the other arguments, with MASK and mask_bits = 0; every other instantiation has an
-// empty pack and its former arguments): the same for declarative bounds on any rows (OptBayesExpt.set_parameter_bounds,
-// obe_resample_particles_aos_bounded) — a new particle that is outside_bounds() on any row gets weight 0; the
-// partial sums, and everything behind them, are the MASK branch's own.
+// BOUNDS (one GatherBounds behind the other arguments; a plain gather has an empty pack and leaves psum / pcount
+// alone): the first half of enforce_parameter_constraints() (OptBayesExpt.set_parameter_bounds; obe_noiseparam.py:57-79
+// is sigma in (0, +inf)), which pdf_update() calls right after this resample, done here: a new particle that is
+// outside_bounds() on any row gets weight 0 instead of 1/N, and the workgroup leaves the partial sums of the weights
+// and of the zeroed count that mask_bounds_kernel (obe_update_common.hip) would leave — the same grid, the same
+// per-thread order, the same block reductions: the same bits — for obe_mask_renorm_moments().  One launch and one
+// pass over the bounded rows and the weights less.
 struct GatherBounds {                      // one entry per row of the cloud; an unbounded row is [-inf, +inf]
     double lo[kFastDims], hi[kFastDims];
     unsigned char open[kFastDims];
 };
+static GatherBounds unbounded_rows() {
+    GatherBounds gb{};
+    for (int i = 0; i < kFastDims; ++i) {
+        gb.lo[i] = -INFINITY;
+        gb.hi[i] = INFINITY;
+    }
+    return gb;
+}
+// the bounds of a call, one entry per bounded row, as one interval per row of the cloud: several entries for a row
+// intersect; at equal values the exclusive end is the narrower one
+static GatherBounds intersect_per_row(const BoundsArg& ba) {
+    GatherBounds gb = unbounded_rows();
+    for (int k = 0; k < ba.n; ++k) {
+        const int i = ba.rows[k];
+        if (ba.lo[k] > gb.lo[i]) {
+            gb.lo[i] = ba.lo[k];
+            gb.open[i] = (gb.open[i] & 2) | (ba.open[k] & 1);
+        } else if (ba.lo[k] == gb.lo[i]) {
+            gb.open[i] |= ba.open[k] & 1;
+        }
+        if (ba.hi[k] < gb.hi[i]) {
+            gb.hi[i] = ba.hi[k];
+            gb.open[i] = (gb.open[i] & 1) | (ba.open[k] & 2);
+        } else if (ba.hi[k] == gb.hi[i]) {
+            gb.open[i] |= ba.open[k] & 2;
+        }
+    }
+    return gb;
+}
 
-template <int D, bool AOS, bool MASK = false, class... BOUNDS>
+template <int D, bool AOS, class... BOUNDS>
 __global__ __launch_bounds__(kBlock) void resample_kernel(NudgeArgs na, const double* __restrict__ old, int64_t ld_old,
                                                           int64_t n, const int64_t* __restrict__ idx,
                                                           const double* __restrict__ z, double* __restrict__ out,
                                                           int64_t ld_new, double* __restrict__ weights,
-                                                          unsigned mask_bits = 0u, double* __restrict__ psum = nullptr,
+                                                          double* __restrict__ psum = nullptr,
                                                           double* __restrict__ pcount = nullptr, BOUNDS... gb) {
-    static_assert(MASK || sizeof...(BOUNDS) == 0, "the bounded gather leaves its partial sums through the MASK branch");
+    constexpr bool BOUNDED = sizeof...(BOUNDS) == 1;
+    static_assert(sizeof...(BOUNDS) <= 1, "at most one GatherBounds");
     // the (N, D) row-major normals of a workgroup's 256 particles are one contiguous run: read it
     // lane-contiguously into LDS (a thread reading its own row makes every load touch 64 lines)
     __shared__ double zs[kBlock * D];
@@ -452,10 +479,9 @@ __global__ __launch_bounds__(kBlock) void resample_kernel(NudgeArgs na, const do
                 v = va + mc;
             }
             out[(int64_t)i * ld_new + p] = v;
-            if constexpr (MASK) bad = bad || (((mask_bits >> i) & 1u) && v <= 0.0);
             bad = bad || (... || outside_bounds(v, gb.lo[i], gb.hi[i], gb.open[i]));      // (an empty pack: false)
         }
-        if constexpr (MASK) {
+        if constexpr (BOUNDED) {
             const double w = bad ? 0.0 : na.uniform_w;
             weights[p] = w;
             acc += w;
@@ -464,7 +490,7 @@ __global__ __launch_bounds__(kBlock) void resample_kernel(NudgeArgs na, const do
             weights[p] = na.uniform_w;
         }
     }
-    if constexpr (MASK) {
+    if constexpr (BOUNDED) {
         const double s = block_sum(acc, red);
         __syncthreads();
         const double c = block_sum(cnt, red);
@@ -508,17 +534,13 @@ __global__ __launch_bounds__(kBlock) void resample_wide_kernel(const double* __r
 template <int D>
 static int launch_resample(const NudgeArgs& na, const double* d_old, int64_t ld_old, int64_t n, const int64_t* d_idx,
                            const double* d_normals, double* d_new, int64_t ld_new, double* d_weights, void* d_ws,
-                           int64_t ws_bytes, hipStream_t st, unsigned mask_bits = 0u, double* d_mask_partials = nullptr,
+                           int64_t ws_bytes, hipStream_t st, double* d_mask_partials = nullptr,
                            const GatherBounds* bounds = nullptr) {
     const int blocks = stream_blocks(n, kBlock);
     if (!d_old && bounds) {
-        resample_kernel<D, true, true, GatherBounds><<<blocks, kBlock, 0, st>>>(
-            na, static_cast<const double*>(d_ws), 0, n, d_idx, d_normals, d_new, ld_new, d_weights, 0u, d_mask_partials,
+        resample_kernel<D, true, GatherBounds><<<blocks, kBlock, 0, st>>>(
+            na, static_cast<const double*>(d_ws), 0, n, d_idx, d_normals, d_new, ld_new, d_weights, d_mask_partials,
             d_mask_partials + kMaxBlocks, *bounds);
-    } else if (!d_old && mask_bits) {
-        resample_kernel<D, true, true><<<blocks, kBlock, 0, st>>>(na, static_cast<const double*>(d_ws), 0, n, d_idx,
-                                                                  d_normals, d_new, ld_new, d_weights, mask_bits,
-                                                                  d_mask_partials, d_mask_partials + kMaxBlocks);
     } else if (!d_old) {
         resample_kernel<D, true><<<blocks, kBlock, 0, st>>>(na, static_cast<const double*>(d_ws), 0, n, d_idx, d_normals,
                                                             d_new, ld_new, d_weights);
@@ -697,7 +719,7 @@ int obe_gather_columns(const double* d_particles, int64_t ld_p, int32_t n_dims, 
 static int resample_particles(const double* d_old, int64_t ld_old, int32_t n_dims, int64_t n_particles,
                               const int64_t* d_idx, const double* d_normals, const double* h_factor,
                               const double* h_mean, double a_param, int32_t scale, double* d_new, int64_t ld_new,
-                              double* d_weights, void* d_ws, int64_t ws_bytes, void* stream, unsigned mask_bits = 0u,
+                              double* d_weights, void* d_ws, int64_t ws_bytes, void* stream,
                               double* d_mask_partials = nullptr, const GatherBounds* bounds = nullptr);
 
 int obe_resample_particles(const double* d_old, int64_t ld_old, int32_t n_dims, int64_t n_particles,
@@ -726,18 +748,17 @@ int obe_resample_particles_aos_masked(const double* d_old_aos, int32_t n_dims, i
     if (!d_old_aos || d_old_aos == d_new || !h_rows || !d_mask_partials || n_rows < 1 || n_rows > kFastDims ||
         n_dims > kFastDims)
         return bad_arg("obe_resample_particles_aos_masked: bad pointer/size");
-    unsigned bits = 0u;
+    GatherBounds gb = unbounded_rows();
     for (int k = 0; k < n_rows; ++k) {
         if (h_rows[k] < 0 || h_rows[k] >= n_dims) return bad_arg("obe_resample_particles_aos_masked: row index out of range");
-        bits |= 1u << h_rows[k];
+        gb.lo[h_rows[k]] = 0.0;           // sigma in (0, +inf): outside_bounds(v, 0, +inf, 1) is v <= 0
+        gb.open[h_rows[k]] = 1;
     }
     return resample_particles(nullptr, 0, n_dims, n_particles, d_idx, d_normals, h_factor, h_mean, a_param, scale, d_new,
-                              ld_new, d_weights, const_cast<double*>(d_old_aos), 0, stream, bits, d_mask_partials);
+                              ld_new, d_weights, const_cast<double*>(d_old_aos), 0, stream, d_mask_partials, &gb);
 }
 
-// The masked gather for declarative bounds (obe_noiseparam.py:57-79, demos/lockin/lockin_of_coil.py:115-133): the
-// bounds of the call, one entry per bounded row, become one interval per row of the cloud (several entries for a row
-// intersect; at equal values the exclusive end is the narrower one)
+// The same gather for declarative bounds on any rows (obe_noiseparam.py:57-79, demos/lockin/lockin_of_coil.py:115-133)
 int obe_resample_particles_aos_bounded(const double* d_old_aos, int32_t n_dims, int64_t n_particles,
                                        const int64_t* d_idx, const double* d_normals, const double* h_factor,
                                        const double* h_mean, double a_param, int32_t scale, double* d_new,
@@ -748,41 +769,22 @@ int obe_resample_particles_aos_bounded(const double* d_old_aos, int32_t n_dims, 
         return bad_arg("obe_resample_particles_aos_bounded: bad pointer/size");
     BoundsArg ba;
     if (int rc = make_bounds_arg(ba, h_rows, h_lower, h_upper, h_open, n_rows, n_dims)) return rc;
-    GatherBounds gb{};
-    for (int i = 0; i < kFastDims; ++i) {
-        gb.lo[i] = -INFINITY;
-        gb.hi[i] = INFINITY;
-    }
-    for (int k = 0; k < ba.n; ++k) {
-        const int i = ba.rows[k];
-        if (ba.lo[k] > gb.lo[i]) {
-            gb.lo[i] = ba.lo[k];
-            gb.open[i] = (gb.open[i] & 2) | (ba.open[k] & 1);
-        } else if (ba.lo[k] == gb.lo[i]) {
-            gb.open[i] |= ba.open[k] & 1;
-        }
-        if (ba.hi[k] < gb.hi[i]) {
-            gb.hi[i] = ba.hi[k];
-            gb.open[i] = (gb.open[i] & 1) | (ba.open[k] & 2);
-        } else if (ba.hi[k] == gb.hi[i]) {
-            gb.open[i] |= ba.open[k] & 2;
-        }
-    }
+    const GatherBounds gb = intersect_per_row(ba);
     return resample_particles(nullptr, 0, n_dims, n_particles, d_idx, d_normals, h_factor, h_mean, a_param, scale, d_new,
-                              ld_new, d_weights, const_cast<double*>(d_old_aos), 0, stream, 0u, d_mask_partials, &gb);
+                              ld_new, d_weights, const_cast<double*>(d_old_aos), 0, stream, d_mask_partials, &gb);
 }
 
 static int resample_particles(const double* d_old, int64_t ld_old, int32_t n_dims, int64_t n_particles,
                               const int64_t* d_idx, const double* d_normals, const double* h_factor,
                               const double* h_mean, double a_param, int32_t scale, double* d_new, int64_t ld_new,
-                              double* d_weights, void* d_ws, int64_t ws_bytes, void* stream, unsigned mask_bits,
-                              double* d_mask_partials, const GatherBounds* bounds) {
+                              double* d_weights, void* d_ws, int64_t ws_bytes, void* stream, double* d_mask_partials,
+                              const GatherBounds* bounds) {
     if (!d_idx || !d_normals || !h_factor || !h_mean || !d_new || !d_weights || n_particles <= 0)
         return bad_arg("obe_resample_particles: bad pointer/size");
     if (n_dims < 1 || n_dims > OBE_CLOUD_MAX_DIMS) return bad_arg("obe_resample_particles: n_dims must be 1..1024");
     if (n_dims > kFastDims) {
-        // wide cloud: only the plain form (the (D, N) cloud, no mask); F and the mean travel through the workspace
-        if (!d_old || mask_bits) return bad_arg("obe_resample_particles_aos: more than OBE_FAST_DIMS parameters (use obe_resample_particles)");
+        // wide cloud: only the plain form (the (D, N) cloud, no bounds); F and the mean travel through the workspace
+        if (!d_old) return bad_arg("obe_resample_particles_aos: more than OBE_FAST_DIMS parameters (use obe_resample_particles)");
         if (!d_ws || ws_bytes < resample_wide_ws_bytes(n_dims)) return bad_arg("obe_resample_particles: workspace too small");
         hipStream_t ws_st = as_stream(stream);
         double* fm = static_cast<double*>(d_ws);
@@ -805,7 +807,7 @@ static int resample_particles(const double* d_old, int64_t ld_old, int32_t n_dim
     hipStream_t st = as_stream(stream);
     return dispatch_dims(n_dims, "obe_resample_particles: n_dims must be 1..16", [&](auto D) -> int {
         return launch_resample<decltype(D)::value>(na, d_old, ld_old, n_particles, d_idx, d_normals, d_new, ld_new,
-                                                   d_weights, d_ws, ws_bytes, st, mask_bits, d_mask_partials, bounds);
+                                                   d_weights, d_ws, ws_bytes, st, d_mask_partials, bounds);
     });
 }
 

@@ -227,7 +227,8 @@ __global__ __launch_bounds__(kBlock) void choke_kernel(double* __restrict__ lk, 
         lk[p] = pow(lk[p], choke);
 }
 
-// ---- OptBayesExptNoiseParameter.enforce_parameter_constraints (obe_noiseparam.py:57-79)
+// ---- the constraint mask: declarative bounds on any rows (OptBayesExpt.set_parameter_bounds), of which
+// OptBayesExptNoiseParameter.enforce_parameter_constraints (obe_noiseparam.py:57-79) is sigma in (0, +inf)
 struct RowsArg {
     int n;
     int rows[OBE_MAX_DIMS];
@@ -242,36 +243,25 @@ static bool make_rows_arg(RowsArg& ra, const int32_t* h_rows, int n_rows, int n_
     }
     return true;
 }
-
-__global__ __launch_bounds__(kBlock) void mask_kernel(RowsArg ra, const double* __restrict__ particles, int64_t ld,
-                                                      int64_t n, double* __restrict__ weights,
-                                                      double* __restrict__ psum, double* __restrict__ pcount) {
-    __shared__ double red[kBlock / kWave];
-    double acc = 0.0, cnt = 0.0;
-    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kBlock) {
-        bool bad = false;
-        for (int k = 0; k < ra.n; ++k) bad = bad || (particles[(int64_t)ra.rows[k] * ld + p] <= 0.0);
-        double w = weights[p];
-        if (bad) {
-            w = 0.0;
-            weights[p] = 0.0;
-            cnt += 1.0;
-        }
-        acc += w;
+// sigma > 0 on these rows as bounds: (0, +inf) with an exclusive lower end.  outside_bounds(v, 0, +inf, 1) is v <= 0
+// for every double: a NaN violates nothing, -0.0 and -5e-324 do, +inf does not.
+static BoundsArg positive_rows(const RowsArg& ra) {
+    BoundsArg ba{};
+    ba.n = ra.n;
+    for (int k = 0; k < ra.n; ++k) {
+        ba.rows[k] = ra.rows[k];
+        ba.lo[k] = 0.0;
+        ba.hi[k] = INFINITY;
+        ba.open[k] = 1;
     }
-    const double s = block_sum(acc, red);
-    __syncthreads();
-    const double c = block_sum(cnt, red);
-    if (threadIdx.x == 0) {
-        psum[blockIdx.x] = s;
-        pcount[blockIdx.x] = c;
-    }
+    return ba;
 }
 
-// The same first half for declarative bounds on any rows (OptBayesExpt.set_parameter_bounds): mask_kernel's grid,
-// per-thread order and block reductions, so that everything behind it — fold2_kernel, mask_renorm_kernel,
-// mask_renorm_moments_kernel — is shared and a given set of violators leaves the same bits whichever kernel found it.
-// An HBM stream of 8 (bounded rows + 2) bytes per particle.
+// The first half: zero the weight of every particle that is outside_bounds() on any bounded row, and leave each
+// workgroup's partial sums {sum w, count} for the second half (fold2_kernel + mask_renorm_kernel, or
+// mask_renorm_moments_kernel).  The bounded gather of a resample (obe_resample.hip) leaves the same partial sums —
+// this grid, this per-thread order, these block reductions — so that a given set of violators leaves the same bits
+// whichever kernel found it.  An HBM stream of 8 (bounded rows + 2) bytes per particle.
 __global__ __launch_bounds__(kBlock) void mask_bounds_kernel(BoundsArg ba, const double* __restrict__ particles,
                                                              int64_t ld, int64_t n, double* __restrict__ weights,
                                                              double* __restrict__ psum, double* __restrict__ pcount) {
@@ -738,37 +728,32 @@ int obe_weight_sums(const double* d_weights, int64_t n_particles, void* d_ws, in
     return fold2_to_host(w.pa, w.pb, nb, w.scalars, h_out, st);
 }
 
-int obe_mask_nonpositive(const double* d_particles, int64_t ld_p, int64_t n_particles, const int32_t* h_rows,
-                         int32_t n_rows, double* d_weights, int64_t* h_changed, void* d_ws, int64_t ws_bytes,
-                         void* stream) {
-    if (!d_particles || !d_weights || !h_rows || n_rows < 1 || n_rows > OBE_MAX_DIMS || n_particles <= 0)
-        return bad_arg("obe_mask_nonpositive: bad pointer/size");
+// mask -> fold -> renormalise if anything was zeroed -> the count on the host (the caller has validated `ba`)
+static int mask_renorm_sync(const BoundsArg& ba, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                            double* d_weights, int64_t* h_count, void* d_ws, int64_t ws_bytes, hipStream_t st) {
     UpdateWs w;
     if (int rc = carve_update_ws(d_ws, ws_bytes, w)) return rc;
-    RowsArg ra;
-    if (!make_rows_arg(ra, h_rows, n_rows, OBE_CLOUD_MAX_DIMS)) return bad_arg("obe_mask_nonpositive: row index out of range");
-    hipStream_t st = as_stream(stream);
     const int nb = stream_blocks(n_particles, kBlock);
-    HostWords changed(h_changed, 1);
+    HostWords changed(h_count, 1);
     changed.arm();
-    mask_kernel<<<nb, kBlock, 0, st>>>(ra, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
-    OBE_CHECK_LAUNCH("mask_kernel");
+    mask_bounds_kernel<<<nb, kBlock, 0, st>>>(ba, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
+    OBE_CHECK_LAUNCH("mask_bounds_kernel");
     fold2_kernel<<<1, kBlock, 0, st>>>(w.pa, w.pb, nb, w.scalars, nullptr);
     OBE_CHECK_LAUNCH("fold2_kernel");
     mask_renorm_kernel<<<nb, kBlock, 0, st>>>(w.scalars, n_particles, d_weights, changed.view<int64_t>());
     OBE_CHECK_LAUNCH("mask_renorm_kernel");
     // (the count is the kernel's first store; the renormalisation that may still be running is ordered
     // before everything the caller enqueues next)
-    if (!h_changed || changed.view<int64_t>()) return changed.wait(st);
+    if (!h_count || changed.view<int64_t>()) return changed.wait(st);
     double sc[2];       // (pageable: the count is a double on the device, converted here)
     OBE_HIP_TRY(hipMemcpyAsync(sc, w.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     OBE_HIP_TRY(hipStreamSynchronize(st));
-    *h_changed = (int64_t)sc[1];
+    *h_count = (int64_t)sc[1];
     return 0;
 }
 
 // the second half: renormalise if anything was zeroed + the first moments of the constrained cloud, from the partial
-// sums {sum w, count} that mask_kernel — or the masked gather of a resample (obe_resample_particles_aos_masked) — left
+// sums {sum w, count} that mask_bounds_kernel — or the bounded gather of a resample (obe_resample.hip) — left
 static int mask_renorm_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
                                const double* psum, const double* pcount, int nb, double* d_weights, double* d_moments,
                                HostWords& moments, HostWords& changed, unsigned* counter, double* partials_mom,
@@ -784,6 +769,91 @@ static int mask_renorm_moments(const double* d_particles, int64_t ld_p, int32_t 
         OBE_CHECK_LAUNCH("mask_renorm_moments_kernel");
         return 0;
     });
+}
+
+// The fused second half needs an arrival counter for the stream, page-locked host outputs (or none) and a cloud no
+// wider than its kernels are compiled for
+static bool can_fuse_moments(const unsigned* counter, const HostWords& changed, const HostWords& moments, int n_dims) {
+    const auto delivered = [](const HostWords& h) { return !h.host<void>() || h.view<void>(); };
+    return counter && delivered(changed) && delivered(moments) && n_dims <= kFastDims;
+}
+
+// mask -> renormalise + first moments of the constrained cloud, armed and not waited for; where that cannot be fused:
+// the two separate calls, synchronously (the caller has validated `ba`)
+static int mask_then_moments(const BoundsArg& ba, const double* d_particles, int64_t ld_p, int32_t n_dims,
+                             int64_t n_particles, double* d_weights, double* d_moments, HostWords& moments,
+                             HostWords& changed, unsigned* counter, void* d_ws, int64_t ws_bytes, hipStream_t st) {
+    if (!can_fuse_moments(counter, changed, moments, n_dims)) {
+        if (int rc = mask_renorm_sync(ba, d_particles, ld_p, n_particles, d_weights, changed.host<int64_t>(), d_ws,
+                                      ws_bytes, st))
+            return rc;
+        return obe_moments(d_particles, ld_p, n_dims, n_particles, d_weights, 0, d_moments, moments.host<double>(), d_ws,
+                           ws_bytes, st);
+    }
+    UpdateWs w;
+    if (int rc = carve_update_ws(d_ws, ws_bytes, w, n_dims)) return rc;
+    const int nb = stream_blocks(n_particles, kBlock);
+    mask_bounds_kernel<<<nb, kBlock, 0, st>>>(ba, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
+    OBE_CHECK_LAUNCH("mask_bounds_kernel");
+    return mask_renorm_moments(d_particles, ld_p, n_dims, n_particles, w.pa, w.pb, nb, d_weights, d_moments, moments,
+                               changed, counter, w.mom, st);
+}
+
+// ---- the entry points: each validates its own arguments, states its constraint as bounds and takes one of the two
+// routes above.  obe_mask_nonpositive* are the bounds calls with (0, +inf) on the given rows.
+int obe_mask_nonpositive(const double* d_particles, int64_t ld_p, int64_t n_particles, const int32_t* h_rows,
+                         int32_t n_rows, double* d_weights, int64_t* h_changed, void* d_ws, int64_t ws_bytes,
+                         void* stream) {
+    if (!d_particles || !d_weights || !h_rows || n_rows < 1 || n_rows > OBE_MAX_DIMS || n_particles <= 0)
+        return bad_arg("obe_mask_nonpositive: bad pointer/size");
+    RowsArg ra;
+    if (!make_rows_arg(ra, h_rows, n_rows, OBE_CLOUD_MAX_DIMS)) return bad_arg("obe_mask_nonpositive: row index out of range");
+    return mask_renorm_sync(positive_rows(ra), d_particles, ld_p, n_particles, d_weights, h_changed, d_ws, ws_bytes,
+                            as_stream(stream));
+}
+
+int obe_mask_bounds(const double* d_particles, int64_t ld_p, int64_t n_particles, const int32_t* h_rows,
+                    const double* h_lower, const double* h_upper, const int32_t* h_open, int32_t n_rows,
+                    double* d_weights, int64_t* h_count, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_particles || !d_weights || n_particles <= 0 || ld_p < n_particles)
+        return bad_arg("obe_mask_bounds: bad pointer/size");
+    BoundsArg ba;
+    if (int rc = make_bounds_arg(ba, h_rows, h_lower, h_upper, h_open, n_rows, OBE_CLOUD_MAX_DIMS)) return rc;
+    return mask_renorm_sync(ba, d_particles, ld_p, n_particles, d_weights, h_count, d_ws, ws_bytes, as_stream(stream));
+}
+
+int obe_mask_nonpositive_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                                 const int32_t* h_rows, int32_t n_rows, double* d_weights, double* d_moments,
+                                 double* h_moments, int64_t* h_changed, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_particles || !d_weights || !h_rows || !d_moments || n_rows < 1 || n_rows > OBE_MAX_DIMS || n_particles <= 0)
+        return bad_arg("obe_mask_nonpositive_moments: bad pointer/size");
+    if (n_dims < 1 || n_dims > OBE_CLOUD_MAX_DIMS) return bad_arg("obe_mask_nonpositive_moments: n_dims must be 1..1024");
+    hipStream_t st = as_stream(stream);
+    unsigned* counter = stream_control_words(st);
+    HostWords changed(h_changed, 1), moments(h_moments, 2 + 4 * (int64_t)n_dims);
+    // (a call that takes the two separate calls has always had obe_mask_nonpositive's row check, and its message)
+    const bool fused = can_fuse_moments(counter, changed, moments, n_dims);
+    RowsArg ra;
+    if (!make_rows_arg(ra, h_rows, n_rows, fused ? n_dims : OBE_CLOUD_MAX_DIMS))
+        return bad_arg(fused ? "obe_mask_nonpositive_moments: row index out of range"
+                             : "obe_mask_nonpositive: row index out of range");
+    return mask_then_moments(positive_rows(ra), d_particles, ld_p, n_dims, n_particles, d_weights, d_moments, moments,
+                             changed, counter, d_ws, ws_bytes, st);
+}
+
+int obe_mask_bounds_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                            const int32_t* h_rows, const double* h_lower, const double* h_upper,
+                            const int32_t* h_open, int32_t n_rows, double* d_weights, double* d_moments,
+                            double* h_first_moments, int64_t* h_count, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_particles || !d_weights || !d_moments || n_particles <= 0 || ld_p < n_particles)
+        return bad_arg("obe_mask_bounds_moments: bad pointer/size");
+    if (n_dims < 1 || n_dims > OBE_CLOUD_MAX_DIMS) return bad_arg("obe_mask_bounds_moments: n_dims must be 1..1024");
+    BoundsArg ba;
+    if (int rc = make_bounds_arg(ba, h_rows, h_lower, h_upper, h_open, n_rows, n_dims)) return rc;
+    hipStream_t st = as_stream(stream);
+    HostWords changed(h_count, 1), moments(h_first_moments, 2 + 4 * (int64_t)n_dims);
+    return mask_then_moments(ba, d_particles, ld_p, n_dims, n_particles, d_weights, d_moments, moments, changed,
+                             stream_control_words(st), d_ws, ws_bytes, st);
 }
 
 int obe_mask_renorm_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
@@ -804,94 +874,6 @@ int obe_mask_renorm_moments(const double* d_particles, int64_t ld_p, int32_t n_d
     return mask_renorm_moments(d_particles, ld_p, n_dims, n_particles, d_mask_partials, d_mask_partials + kMaxBlocks,
                                stream_blocks(n_particles, kBlock), d_weights, d_moments, moments, changed, counter, w.mom,
                                st);
-}
-
-int obe_mask_nonpositive_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
-                                 const int32_t* h_rows, int32_t n_rows, double* d_weights, double* d_moments,
-                                 double* h_moments, int64_t* h_changed, void* d_ws, int64_t ws_bytes, void* stream) {
-    if (!d_particles || !d_weights || !h_rows || !d_moments || n_rows < 1 || n_rows > OBE_MAX_DIMS || n_particles <= 0)
-        return bad_arg("obe_mask_nonpositive_moments: bad pointer/size");
-    if (n_dims < 1 || n_dims > OBE_CLOUD_MAX_DIMS) return bad_arg("obe_mask_nonpositive_moments: n_dims must be 1..1024");
-    hipStream_t st = as_stream(stream);
-    unsigned* counter = stream_control_words(st);
-    HostWords changed(h_changed, 1), moments(h_moments, 2 + 4 * (int64_t)n_dims);
-    if (!counter || (h_changed && !changed.view<void>()) || (h_moments && !moments.view<void>()) || n_dims > kFastDims) {
-        // no arrival counter for this stream / pageable host buffers / a cloud wider than the fused kernels are
-        // compiled for: the two separate calls (synchronous)
-        if (int rc = obe_mask_nonpositive(d_particles, ld_p, n_particles, h_rows, n_rows, d_weights, h_changed, d_ws,
-                                          ws_bytes, stream))
-            return rc;
-        return obe_moments(d_particles, ld_p, n_dims, n_particles, d_weights, 0, d_moments, h_moments, d_ws, ws_bytes,
-                           stream);
-    }
-    UpdateWs w;
-    if (int rc = carve_update_ws(d_ws, ws_bytes, w, n_dims)) return rc;
-    RowsArg ra;
-    if (!make_rows_arg(ra, h_rows, n_rows, n_dims)) return bad_arg("obe_mask_nonpositive_moments: row index out of range");
-    const int nb = stream_blocks(n_particles, kBlock);
-    mask_kernel<<<nb, kBlock, 0, st>>>(ra, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
-    OBE_CHECK_LAUNCH("mask_kernel");
-    return mask_renorm_moments(d_particles, ld_p, n_dims, n_particles, w.pa, w.pb, nb, d_weights, d_moments, moments,
-                               changed, counter, w.mom, st);
-}
-
-// ---- declarative bounds on any parameter rows: obe_mask_nonpositive / obe_mask_nonpositive_moments with
-// mask_bounds_kernel in front of the same second halves
-int obe_mask_bounds(const double* d_particles, int64_t ld_p, int64_t n_particles, const int32_t* h_rows,
-                    const double* h_lower, const double* h_upper, const int32_t* h_open, int32_t n_rows,
-                    double* d_weights, int64_t* h_count, void* d_ws, int64_t ws_bytes, void* stream) {
-    if (!d_particles || !d_weights || n_particles <= 0 || ld_p < n_particles)
-        return bad_arg("obe_mask_bounds: bad pointer/size");
-    BoundsArg ba;
-    if (int rc = make_bounds_arg(ba, h_rows, h_lower, h_upper, h_open, n_rows, OBE_CLOUD_MAX_DIMS)) return rc;
-    UpdateWs w;
-    if (int rc = carve_update_ws(d_ws, ws_bytes, w)) return rc;
-    hipStream_t st = as_stream(stream);
-    const int nb = stream_blocks(n_particles, kBlock);
-    HostWords changed(h_count, 1);
-    changed.arm();
-    mask_bounds_kernel<<<nb, kBlock, 0, st>>>(ba, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
-    OBE_CHECK_LAUNCH("mask_bounds_kernel");
-    fold2_kernel<<<1, kBlock, 0, st>>>(w.pa, w.pb, nb, w.scalars, nullptr);
-    OBE_CHECK_LAUNCH("fold2_kernel");
-    mask_renorm_kernel<<<nb, kBlock, 0, st>>>(w.scalars, n_particles, d_weights, changed.view<int64_t>());
-    OBE_CHECK_LAUNCH("mask_renorm_kernel");
-    if (!h_count || changed.view<int64_t>()) return changed.wait(st);        // (as obe_mask_nonpositive)
-    double sc[2];
-    OBE_HIP_TRY(hipMemcpyAsync(sc, w.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-    OBE_HIP_TRY(hipStreamSynchronize(st));
-    *h_count = (int64_t)sc[1];
-    return 0;
-}
-
-int obe_mask_bounds_moments(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
-                            const int32_t* h_rows, const double* h_lower, const double* h_upper,
-                            const int32_t* h_open, int32_t n_rows, double* d_weights, double* d_moments,
-                            double* h_first_moments, int64_t* h_count, void* d_ws, int64_t ws_bytes, void* stream) {
-    if (!d_particles || !d_weights || !d_moments || n_particles <= 0 || ld_p < n_particles)
-        return bad_arg("obe_mask_bounds_moments: bad pointer/size");
-    if (n_dims < 1 || n_dims > OBE_CLOUD_MAX_DIMS) return bad_arg("obe_mask_bounds_moments: n_dims must be 1..1024");
-    BoundsArg ba;
-    if (int rc = make_bounds_arg(ba, h_rows, h_lower, h_upper, h_open, n_rows, n_dims)) return rc;
-    UpdateWs w;
-    if (int rc = carve_update_ws(d_ws, ws_bytes, w)) return rc;      // (what either route needs at least)
-    hipStream_t st = as_stream(stream);
-    unsigned* counter = stream_control_words(st);
-    HostWords changed(h_count, 1), moments(h_first_moments, 2 + 4 * (int64_t)n_dims);
-    if (!counter || (h_count && !changed.view<void>()) || (h_first_moments && !moments.view<void>()) || n_dims > kFastDims) {
-        // (as obe_mask_nonpositive_moments: the two separate calls, synchronous)
-        if (int rc = obe_mask_bounds(d_particles, ld_p, n_particles, h_rows, h_lower, h_upper, h_open, n_rows, d_weights,
-                                     h_count, d_ws, ws_bytes, stream))
-            return rc;
-        return obe_moments(d_particles, ld_p, n_dims, n_particles, d_weights, 0, d_moments, h_first_moments, d_ws, ws_bytes,
-                           stream);
-    }
-    if (int rc = carve_update_ws(d_ws, ws_bytes, w, n_dims)) return rc;
-    const int nb = stream_blocks(n_particles, kBlock);
-    mask_bounds_kernel<<<nb, kBlock, 0, st>>>(ba, d_particles, ld_p, n_particles, d_weights, w.pa, w.pb);
-    OBE_CHECK_LAUNCH("mask_bounds_kernel");
-    return mask_renorm_moments(d_particles, ld_p, n_dims, n_particles, w.pa, w.pb, nb, d_weights, d_moments, moments,
-                               changed, counter, w.mom, st);
 }
 
 int obe_power_normalize(const double* d_u, int64_t n, double exponent, double* d_p_out, void* d_ws,

@@ -259,7 +259,7 @@ def test_argument_errors_are_reported_not_crashed(lib):
     rc = lib.cdll.obe_resample_begin(dev, 16, 3, 16, dev, None, 0, 0, 0, 1 << 16, dev, dev, dev, dev, dev, dev, 1 << 20,
                                      dev, dev, dev, None, dev, 1 << 20, None)
     assert rc == -1 and lib.last_error() == "obe_resample_begin: bad pointer/size"
-    # a negative row index would make mask_kernel read in front of the cloud: refused before any launch
+    # a negative row index would make the mask kernel read in front of the cloud: refused before any launch
     rows = np.array([-1], dtype=np.int32)
     ws_bytes = lib.cdll.obe_workspace_bytes(16, 1, 1, 3)
     rc = lib.cdll.obe_mask_nonpositive(dev, 16, 16, _lib.host_ptr(rows), 1, dev, None, dev, ws_bytes, None)

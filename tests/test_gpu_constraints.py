@@ -1,8 +1,10 @@
 """Declarative parameter bounds on the device (GPU): the three entry points against the NumPy oracle and, bit for bit,
-against the noise-only calls they generalise; the mask inside the gather against the mask behind it; the classes
-against the oracle classes carrying the same constraint as a NumPy hook."""
+against the noise-only calls they generalise (adapters over them, pinned by the bits recorded before they were); the
+mask inside the gather against the mask behind it; the classes against the oracle classes carrying the same
+constraint as a NumPy hook."""
 import copy
 import ctypes
+import json
 import os
 import pickle
 import subprocess
@@ -13,6 +15,7 @@ import numpy as np
 import pytest
 from numpy.testing import assert_array_equal
 
+import _constraint_cases as cc
 import _constraint_oracle as co
 import _replay
 import oracle
@@ -269,6 +272,30 @@ def test_positive_noise_rows_through_the_new_entry_points_are_the_old_bits(hip, 
         for a, b, what in zip(out[0][:6], out[1][:6], ("new cloud", "masked weights", "partial sums", "weights",
                                                         "moments (device)", "moments (host)")):
             _same_bits(a, b, what)
+
+
+@pytest.fixture(scope="module")
+def parent_bits():
+    with open(os.path.join(ROOT, "tests", "golden", "constraint_parent_bits.json")) as f:
+        return json.load(f)["cases"]
+
+
+@pytest.mark.parametrize("case", cc.CASES, ids=cc.case_id)
+def test_sigma_positive_entry_points_leave_the_parent_commits_bits(hip, parent_bits, case):
+    """obe_mask_nonpositive, obe_mask_nonpositive_moments and obe_resample_particles_aos_masked (+ obe_mask_renorm_moments
+    on its partial sums) are the bounds calls with (0, +inf) on their rows: the comparisons above send one
+    implementation through two doors.  The independent pin is the fixture, recorded by the last commit that had a
+    sigma <= 0 kernel and a row-bitmask gather of their own (tests/_constraint_cases.py): counts, first moments on the
+    device and on the host, and the hashes of the weights, the new cloud and the partial sums, item by item."""
+    want = parent_bits[cc.case_id(case)]
+    got = cc.run(hip, case)
+    assert got["inputs"] == want["inputs"], "inputs differ: the case generator no longer makes the recorded arrays"
+    cc.check_condition(case, got)
+    assert sorted(got) == sorted(want)
+    for call in sorted(set(got) - {"inputs"}):
+        assert sorted(got[call]) == sorted(want[call]), call
+        for item in sorted(got[call]):
+            assert got[call][item] == want[call][item], f"{cc.case_id(case)}: {call}: {item}"
 
 
 def test_bounded_gather_is_the_oracle_on_any_rows(hip):

@@ -336,7 +336,7 @@ def test_cycles_on_alternating_streams(hip, sharded):
 
 def test_the_constraint_mask_inside_the_gather_is_the_mask_after_it(hip):
     """Round 5: inside pdf_update() the gather of a resample zeroes the weights of new particles with sigma <= 0 itself and
-    leaves mask_kernel's partial sums, so that enforce_parameter_constraints() (obe_noiseparam.py:57-79) is one launch
+    leaves the mask kernel's partial sums, so that enforce_parameter_constraints() (obe_noiseparam.py:57-79) is one launch
     instead of two.  Same particles masked, same weights, moments, counts, settings, generator — bit for bit — as with
     tuning_parameters['mask_in_gather'] = False; a resample() called on its own still leaves uniform weights."""
     import optbayesexpt_amd as obe
