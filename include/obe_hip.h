@@ -680,6 +680,40 @@ OBE_API int obe_predictive_quantiles(const obe_model* m, const double* d_setting
                              const double* h_q, int32_t n_q, double* d_quantiles, void* d_ws, int64_t ws_bytes,
                              void* stream);
 
+/* ---- posterior predictive of a MEASUREMENT: log-density and tail probabilities (extension) ----
+ * Is a reading plausible under what the cloud has learnt?  The summaries above describe the model curve alone; a
+ * reading carries its noise too: p(y | x, data) = sum_i w_i prod_c N(y_c; f_c(x; theta_i), sigma_c,i) / sum_i w_i, the
+ * mixture whose terms the update multiplies the weights by (obe_base.py:269-271, :451-461; obe_noiseparam.py:109-120
+ * with sigma from parameter rows) — without the choke, which tempers the update and is no density of y.  Taken for the
+ * record about to be used it is the one-step model evidence.  A record is a column: the setting point d_settings
+ * (n_setdims, n_records), the reading d_y_meas (C, n_records) — all C channels of the model — and its noise: exactly
+ * one of d_sigma (C, n_records), known and free to differ per record, and h_noise_rows (C rows of the cloud).  With
+ * f = what obe_eval_over_particles writes, bit for bit, and z_c = (f_c - y_c) / sigma_c:
+ * a particle enters only with a weight > 0 (NaN and negative weights count as zero, whatever f is then) and with every
+ * sigma of it > 0 (a NaN sigma fails; the update's nan_to_num zeroes such a particle's product).  n_records x
+ * n_particles evaluations stay on the chip; partial results are folded in a fixed order: the same bits from run to
+ * run.  All results land in the caller's DEVICE buffers, nothing is waited for.  d_ws:
+ * obe_predictive_score_workspace_bytes(n_particles, n_records, the model's channels) bytes, a buffer of its own; the
+ * size does not shrink when an argument grows. */
+OBE_API int64_t obe_predictive_score_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels);
+/* d_logpdf (n_records,) = log p(y | x, data), the joint density over the channels, as a running (max, scaled sum) pair
+ * with one exp per evaluation: l_i = sum_c [-z_c^2 / 2 - log sigma_c], log p = m + log sum_i w_i exp(l_i - m) -
+ * log sum w - (C / 2) log 2 pi.  A particle whose l_i is -inf or NaN contributes nothing; -inf if none contributed,
+ * NaN if sum w == 0. */
+OBE_API int obe_predictive_logpdf(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                          const double* d_y_meas, int64_t ld_y, const double* d_sigma, int64_t ld_sigma,
+                          const int32_t* h_noise_rows, const double* d_particles, int64_t ld_p,
+                          int64_t n_particles, const double* d_weights, double* d_logpdf,
+                          void* d_ws, int64_t ws_bytes, void* stream);
+/* d_lower, d_upper (C, n_records) = P(Y_c <= y_c) and P(Y_c >= y_c) per channel: sum_i w_i erfc(z_c / sqrt 2) / 2 and
+ * sum_i w_i erfc(-z_c / sqrt 2) / 2 over sum w.  Both are sums of positive terms (neither is 1 - the other), so a far
+ * tail keeps its relative accuracy.  A NaN z contributes to neither; 0 if nothing contributed, NaN if sum w == 0. */
+OBE_API int obe_predictive_tails(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                         const double* d_y_meas, int64_t ld_y, const double* d_sigma, int64_t ld_sigma,
+                         const int32_t* h_noise_rows, const double* d_particles, int64_t ld_p,
+                         int64_t n_particles, const double* d_weights, double* d_lower, double* d_upper,
+                         void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

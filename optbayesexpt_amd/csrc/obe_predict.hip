@@ -13,6 +13,8 @@
 //              passes of select_pass_kernel / select_choose_kernel.  Integer sums: the same bits under any grid and
 //              any permutation of the cloud.  (A fused select that recomputed the key in every pass instead of
 //              loading it was built and measured: slower at both benchmark clouds)
+// K11 — scoring a measurement against the posterior predictive (further down): the log-density of readings and their
+// per-channel tail probabilities, noise included.  The geometry of the moments with lane <-> record.
 #include <algorithm>
 
 #include "obe_models.h"
@@ -164,12 +166,289 @@ int enqueue_scale(const double* d_weights, int64_t n, const PredWs& ws, hipStrea
     return 0;
 }
 
+// ---- K11: scoring.  Lane = one record (a setting point, the reading y_meas[c], a known sigma[c]); the chunk's particles
+// one after the other, particle, weight and noise rows the same for all lanes.  z_c = (y_c - y_meas_c) / sigma_c with y
+// the model value.  A particle enters only with a weight > 0 and, ROWS, every noise row > 0 (NaN fails both).
+constexpr double kInf = __builtin_huge_val();
+constexpr double kHalfLog2Pi = 0.91893853320467274178;      // log(2 pi) / 2
+constexpr double kSqrtHalf = 0.70710678118654752440;
+
+struct ScoreRows {
+    int row[OBE_MAX_CHANNELS];
+};
+
+// (m, S) <- (m, S) + s exp(l): S exp(m) is the sum so far, m the largest exponent seen.  One exp; l finite, m finite or
+// -inf (never +inf), so no inf - inf is formed.
+__device__ __forceinline__ void lse_add(double& m, double& S, double l, double s) {
+    const bool up = l > m;
+    const double e = exp(up ? m - l : l - m);
+    S = up ? S * e + s : S + s * e;
+    m = up ? l : m;
+}
+
+// the record's reading and, known sigma, 1 / sigma and -sum log sigma; false: a sigma of the record is not > 0
+template <class M, bool ROWS>
+__device__ __forceinline__ bool load_record(int64_t sc, const double* __restrict__ y_meas, int64_t ld_y,
+                                            const double* __restrict__ sigma, int64_t ld_sg, double* ym, double* inv,
+                                            double& neg_log) {
+    bool ok = true;
+    neg_log = 0.0;
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        ym[c] = y_meas[(int64_t)c * ld_y + sc];
+        if (!ROWS) {
+            const double sg = sigma[(int64_t)c * ld_sg + sc];
+            ok = ok && sg > 0.0;
+            inv[c] = 1.0 / sg;
+            neg_log -= log(sg);
+        }
+    }
+    return ok;
+}
+
+// the particle's sigma rows (the same for all lanes); false: one of them is not > 0
+template <class M>
+__device__ __forceinline__ bool load_noise(const ScoreRows& rows, const double* __restrict__ particles, int64_t ld_p,
+                                           int64_t p, double* inv, double& neg_log) {
+    bool ok = true;
+    neg_log = 0.0;
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        const double sg = particles[(int64_t)rows.row[c] * ld_p + p];
+        ok = ok && sg > 0.0;
+        inv[c] = 1.0 / sg;
+        neg_log -= log(sg);
+    }
+    return ok;
+}
+
+// partials (chunk, 2, padded records): the chunk's (m, S) of sum_i w_i exp(l_i), l_i = sum_c [-z_c^2 / 2 - log sigma_c]
+template <class M, bool ROWS>
+__global__ __launch_bounds__(kWave) void score_logpdf_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                             int64_t n_r, const double* __restrict__ y_meas, int64_t ld_y,
+                                                             const double* __restrict__ sigma, int64_t ld_sg,
+                                                             ScoreRows rows, const double* __restrict__ particles,
+                                                             int64_t ld_p, int64_t n, const double* __restrict__ w,
+                                                             int64_t chunk_len, double* __restrict__ partials) {
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_r ? s : n_r - 1;                    // (the padding lanes repeat the last record)
+    double x[M::NS], ym[M::NC], inv[M::NC], neg_log;
+#pragma unroll
+    for (int k = 0; k < M::NS; ++k) x[k] = settings[(int64_t)k * ld_s + sc];
+    const bool rec_ok = load_record<M, ROWS>(sc, y_meas, ld_y, sigma, ld_sg, ym, inv, neg_log);
+    double top = -kInf, S = 0.0;
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p] and the particle are the same for all lanes)
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        if (ROWS && !load_noise<M>(rows, particles, ld_p, p, inv, neg_log)) continue;
+        double y[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+        double l = neg_log;
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const double z = (y[c] - ym[c]) * inv[c];
+            l -= 0.5 * (z * z);
+        }
+        if (rec_ok && fabs(l) < kInf) lse_add(top, S, l, wp);      // (NaN and -inf contribute nothing)
+    }
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+    partials[((int64_t)blockIdx.y * 2 + 0) * n_pad + s] = top;
+    partials[((int64_t)blockIdx.y * 2 + 1) * n_pad + s] = S;
+}
+
+// d_logpdf (n_records,) = m + log S - log sum w - (C / 2) log 2 pi, the chunks' (m_j, S_j) merged in chunk order
+__global__ __launch_bounds__(kBlock) void score_logpdf_fold_kernel(const double* __restrict__ partials, int chunks,
+                                                                   int n_channels, int64_t n_pad, int64_t n_r,
+                                                                   const u64* __restrict__ hdr, double* __restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_r) return;
+    const double sw = __longlong_as_double((long long)hdr[0]);
+    double top = -kInf, S = 0.0;
+    for (int j = 0; j < chunks; ++j) {
+        const double mj = partials[((int64_t)j * 2 + 0) * n_pad + s];
+        if (mj > -kInf) lse_add(top, S, mj, partials[((int64_t)j * 2 + 1) * n_pad + s]);
+    }
+    double r = __builtin_nan("");
+    if (sw > 0.0) r = top > -kInf ? top + log(S) - log(sw) - n_channels * kHalfLog2Pi : -kInf;
+    out[s] = r;
+}
+
+// partials (chunk, 2 C, padded records): sum w P(Y_c <= y_meas_c | particle), then sum w P(Y_c >= y_meas_c | particle).
+// The small one of the two is erfc(|z| / sqrt 2) / 2 itself, the large one 1 - that (>= 1/2: correctly rounded).
+template <class M, bool ROWS>
+__global__ __launch_bounds__(kWave) void score_tails_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                            int64_t n_r, const double* __restrict__ y_meas, int64_t ld_y,
+                                                            const double* __restrict__ sigma, int64_t ld_sg,
+                                                            ScoreRows rows, const double* __restrict__ particles,
+                                                            int64_t ld_p, int64_t n, const double* __restrict__ w,
+                                                            int64_t chunk_len, double* __restrict__ partials) {
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_r ? s : n_r - 1;
+    double x[M::NS], ym[M::NC], inv[M::NC], lo[M::NC], hi[M::NC], unused;
+#pragma unroll
+    for (int k = 0; k < M::NS; ++k) x[k] = settings[(int64_t)k * ld_s + sc];
+    const bool rec_ok = load_record<M, ROWS>(sc, y_meas, ld_y, sigma, ld_sg, ym, inv, unused);
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) lo[c] = hi[c] = 0.0;
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        if (ROWS && !load_noise<M>(rows, particles, ld_p, p, inv, unused)) continue;
+        double y[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const double z = (y[c] - ym[c]) * inv[c];            // > 0: the model lies above the reading
+            if (rec_ok && z == z) {
+                const double small = 0.5 * erfc(fabs(z) * kSqrtHalf), large = 1.0 - small;
+                lo[c] += wp * (z > 0.0 ? small : large);
+                hi[c] += wp * (z > 0.0 ? large : small);
+            }
+        }
+    }
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        partials[((int64_t)blockIdx.y * 2 * M::NC + c) * n_pad + s] = lo[c];
+        partials[((int64_t)blockIdx.y * 2 * M::NC + M::NC + c) * n_pad + s] = hi[c];
+    }
+}
+
+// d_lower, d_upper (C, n_records) = (the chunk partials, added in chunk order) / sum w
+__global__ __launch_bounds__(kBlock) void score_tails_fold_kernel(const double* __restrict__ partials, int chunks,
+                                                                  int n_channels, int64_t n_pad, int64_t n_r,
+                                                                  const u64* __restrict__ hdr, double* __restrict__ lower,
+                                                                  double* __restrict__ upper) {
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_r) return;
+    const double sw = __longlong_as_double((long long)hdr[0]);
+    for (int k = 0; k < 2 * n_channels; ++k) {
+        double acc = 0.0;
+        for (int j = 0; j < chunks; ++j) acc += partials[((int64_t)j * 2 * n_channels + k) * n_pad + s];
+        double* out = k < n_channels ? lower : upper;
+        out[(int64_t)(k % n_channels) * n_r + s] = acc / sw;
+    }
+}
+
+// What the two scoring entry points share: everything that can refuse the call, then the launch geometry.
+struct Score {
+    obe_model mm;
+    ScoreRows rows;
+    PredWs ws;
+    int64_t tiles, chunk_len;
+    int used;
+    int prepare(const char* who, const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                const double* d_y_meas, int64_t ld_y, const double* d_sigma, int64_t ld_sigma,
+                const int32_t* h_noise_rows, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                const double* d_weights, void* d_ws, int64_t ws_bytes) {
+        static thread_local std::string msg;
+        auto refuse = [&](const char* what) {
+            msg = std::string(who) + ": " + what;
+            return bad_arg(msg.c_str());
+        };
+        if (!d_y_meas) return refuse("null pointer");
+        if (int rc = check_inputs(who, m, d_settings, ld_s, n_records, d_particles, ld_p, n_particles, d_weights, d_ws))
+            return rc;
+        if ((d_sigma != nullptr) == (h_noise_rows != nullptr)) return refuse("exactly one of d_sigma and h_noise_rows");
+        if (ld_y < n_records || (d_sigma && ld_sigma < n_records)) return refuse("a row of y_meas or sigma shorter than n_records");
+        mm = *m;
+        if (int rc = obe_model_validate(&mm)) return rc;
+        for (int c = 0; c < OBE_MAX_CHANNELS; ++c) {
+            rows.row[c] = (h_noise_rows && c < mm.n_channels) ? h_noise_rows[c] : 0;
+            if (rows.row[c] && (rows.row[c] < 0 || rows.row[c] >= mm.n_params)) return refuse("noise row index out of range");
+        }
+        if (ws_bytes < obe_predictive_score_workspace_bytes(n_particles, n_records, mm.n_channels))
+            return refuse("workspace too small");
+        tiles = setting_tiles(n_records);
+        if (tiles > 0x7fffffff) return refuse("too many records for one call");
+        const int chunks = moment_chunks(n_particles, n_records);
+        chunk_len = ((n_particles + chunks - 1) / chunks + kWave - 1) / kWave * kWave;      // whole waves of particles
+        used = (int)((n_particles + chunk_len - 1) / chunk_len);
+        ws = carve(d_ws);
+        return 0;
+    }
+};
+
 }  // namespace
 }  // namespace obe
 
 using namespace obe;
 
 extern "C" {
+
+int64_t obe_predictive_score_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels) {
+    (void)n_particles;                                           // (the partials are per chunk: bounded whatever the cloud)
+    if (n_records < 1) n_records = 1;
+    if (n_channels < 1) n_channels = 1;
+    return (kPredHeadWords + moment_words(n_records, 2 * n_channels)) * (int64_t)sizeof(u64);
+}
+
+int obe_predictive_logpdf(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                          const double* d_y_meas, int64_t ld_y, const double* d_sigma, int64_t ld_sigma,
+                          const int32_t* h_noise_rows, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                          const double* d_weights, double* d_logpdf, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_logpdf) return bad_arg("obe_predictive_logpdf: null pointer");
+    Score sc;
+    if (int rc = sc.prepare("obe_predictive_logpdf", m, d_settings, ld_s, n_records, d_y_meas, ld_y, d_sigma, ld_sigma,
+                            h_noise_rows, d_particles, ld_p, n_particles, d_weights, d_ws, ws_bytes))
+        return rc;
+    hipStream_t st = as_stream(stream);
+    double* partials = reinterpret_cast<double*>(sc.ws.body);
+    if (int rc = enqueue_scale(d_weights, n_particles, sc.ws, st)) return rc;
+    return dispatch_model(sc.mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        const dim3 grid((unsigned)sc.tiles, (unsigned)sc.used);
+        if (h_noise_rows)
+            score_logpdf_kernel<Model, true><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_records, d_y_meas, ld_y,
+                                                                     nullptr, 0, sc.rows, d_particles, ld_p, n_particles,
+                                                                     d_weights, sc.chunk_len, partials);
+        else
+            score_logpdf_kernel<Model, false><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_records, d_y_meas, ld_y,
+                                                                      d_sigma, ld_sigma, sc.rows, d_particles, ld_p,
+                                                                      n_particles, d_weights, sc.chunk_len, partials);
+        OBE_CHECK_LAUNCH("score_logpdf_kernel");
+        score_logpdf_fold_kernel<<<(int)((n_records + kBlock - 1) / kBlock), kBlock, 0, st>>>(
+            partials, sc.used, Model::NC, sc.tiles * kWave, n_records, sc.ws.hdr, d_logpdf);
+        OBE_CHECK_LAUNCH("score_logpdf_fold_kernel");
+        return 0;
+    });
+}
+
+int obe_predictive_tails(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                         const double* d_y_meas, int64_t ld_y, const double* d_sigma, int64_t ld_sigma,
+                         const int32_t* h_noise_rows, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                         const double* d_weights, double* d_lower, double* d_upper, void* d_ws, int64_t ws_bytes,
+                         void* stream) {
+    if (!d_lower || !d_upper) return bad_arg("obe_predictive_tails: null pointer");
+    Score sc;
+    if (int rc = sc.prepare("obe_predictive_tails", m, d_settings, ld_s, n_records, d_y_meas, ld_y, d_sigma, ld_sigma,
+                            h_noise_rows, d_particles, ld_p, n_particles, d_weights, d_ws, ws_bytes))
+        return rc;
+    hipStream_t st = as_stream(stream);
+    double* partials = reinterpret_cast<double*>(sc.ws.body);
+    if (int rc = enqueue_scale(d_weights, n_particles, sc.ws, st)) return rc;
+    return dispatch_model(sc.mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        const dim3 grid((unsigned)sc.tiles, (unsigned)sc.used);
+        if (h_noise_rows)
+            score_tails_kernel<Model, true><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_records, d_y_meas, ld_y,
+                                                                    nullptr, 0, sc.rows, d_particles, ld_p, n_particles,
+                                                                    d_weights, sc.chunk_len, partials);
+        else
+            score_tails_kernel<Model, false><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_records, d_y_meas, ld_y,
+                                                                     d_sigma, ld_sigma, sc.rows, d_particles, ld_p,
+                                                                     n_particles, d_weights, sc.chunk_len, partials);
+        OBE_CHECK_LAUNCH("score_tails_kernel");
+        score_tails_fold_kernel<<<(int)((n_records + kBlock - 1) / kBlock), kBlock, 0, st>>>(
+            partials, sc.used, Model::NC, sc.tiles * kWave, n_records, sc.ws.hdr, d_lower, d_upper);
+        OBE_CHECK_LAUNCH("score_tails_fold_kernel");
+        return 0;
+    });
+}
 
 int64_t obe_predictive_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels, int32_t n_q) {
     if (n_settings < 1) n_settings = 1;

@@ -33,7 +33,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _bounds, _devrng, _lib, _predictive
+from . import _bounds, _devrng, _lib, _predictive, _scoring
 from ._sweepstate import Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
@@ -422,6 +422,28 @@ class OptBayesExpt(ParticlePDF):
         """Equal-tailed credible band ``(lo, hi)`` of the model output, each ``(n_channels, n_x)``: the quantiles at
         ``(1 - level) / 2`` and ``(1 + level) / 2``."""
         return _predictive.predictive_interval(self, level, settings)
+
+    # ------------------------------------------------ is a reading plausible?  (scoring a measurement)
+    # (extension: the summaries above describe the model curve alone — measurement noise is not in the band.  These score
+    # READINGS against the posterior predictive p(y | x, data) = sum_i w_i prod_c N(y_c; f_c(x; theta_i), sigma_c) /
+    # sum_i w_i on the device (_scoring.py, csrc/obe_predict.hip) and change nothing of the object.  ``settings``: points,
+    # as predict() takes them; ``y_meas``: a scalar or (n_r,) for one channel, (C,) for one record of a C-channel model,
+    # else (C, n_r); ``sigma``: a scalar, (C,) or (C, n_r), finite and > 0 — required here, and refused by
+    # OptBayesExptNoiseParameter, whose sigma is a parameter of every particle.  Everything broadcasts to n_r records.)
+    def predictive_logpdf(self, settings, y_meas, sigma=None):
+        """``log p(y_meas | settings, data)``, the joint density over the channels: ``(n_r,)``, or a float for one
+        record given as ``pdf_update`` takes it (``predictive_logpdf(*measurement_record)``).  Taken before the update
+        that uses the record, it is the one-step log evidence."""
+        return _scoring.predictive_logpdf(self, settings, y_meas, sigma)
+
+    def predictive_cdf(self, settings, y_meas, sigma=None, upper=False):
+        """``P(Y_c <= y_meas_c)`` per channel, ``(n_channels, n_r)``; ``upper``: ``P(Y_c >= y_meas_c)``, summed as such
+        (a far tail keeps its relative accuracy)."""
+        return _scoring.predictive_cdf(self, settings, y_meas, sigma, upper)
+
+    def predictive_pvalue(self, settings, y_meas, sigma=None):
+        """Two-sided p-value per channel, ``(n_channels, n_r)``: ``2 min(lower, upper)``, clipped to 1."""
+        return _scoring.predictive_pvalue(self, settings, y_meas, sigma)
 
     def _setting_array(self, onesettingset):
         """The setting of a record, zero-padded to OBE_MAX_SETDIMS — in this object's record buffer:
