@@ -714,6 +714,45 @@ OBE_API int obe_predictive_tails(const obe_model* m, const double* d_settings, i
                          int64_t n_particles, const double* d_weights, double* d_lower, double* d_upper,
                          void* d_ws, int64_t ws_bytes, void* stream);
 
+/* ---- design for parameters of interest: output-parameter covariance and the variance a reading removes (extension) ----
+ * Every utility of the reference scores a setting by how much the model output varies there, for any reason
+ * (obe_base.py:579-720: sum_c var_p / var_n); a user who wants ONE parameter and treats the others as nuisances needs
+ * the covariance, over the weighted cloud, between the model output and that parameter.  With y_c,i = what
+ * obe_eval_over_particles writes for the setting x, bit for bit, cleaned weights (NaN and negative weights count as
+ * zero, a particle of zero weight contributes nothing whatever its y or theta is) and W = sum w:
+ *   m_c(x)   = sum w y_c / W                               t_d = sum w theta_d / W
+ *   S_cc'(x) = sum w (y_c - m_c)(y_c' - m_c') / W          V_d = sum w (theta_d - t_d)^2 / W
+ *   K_dc(x)  = sum w (theta_d - t_d)(y_c - m_c) / W
+ * in two passes over the cloud (the second about the means the first one found); n_settings x n_particles evaluations
+ * stay on the chip.  Partial sums are folded in a fixed order: the same bits from run to run.  All results land in the
+ * caller's DEVICE buffers, nothing is waited for.  h_rows: the n_rows parameter rows of interest (1..8 per call, each in
+ * [0, n_dims), n_dims the rows of the cloud); d_ws: obe_output_covariance_workspace_bytes(n_particles, n_settings, the
+ * model's channels, n_rows) bytes, a buffer of its own, as for the posterior predictive summaries. */
+OBE_API int64_t obe_output_covariance_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels,
+                                              int32_t n_rows);
+/* d_mean (C, n_settings): obe_predictive_moments' mean, bit for bit (the same launches).  d_ycov (C (C + 1) / 2,
+ * n_settings): the lower triangle of S, packed row-major (00, 10, 11, 20, ...); may be NULL (a later tile of rows of the
+ * same request).  d_xcov (n_rows, C, n_settings): K.  d_pvar (n_rows,): V.  sum w == 0 gives NaN. */
+OBE_API int obe_output_covariance(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                          const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                          const double* d_weights, const int32_t* h_rows, int32_t n_rows, double* d_mean,
+                          double* d_ycov, double* d_xcov, double* d_pvar, void* d_ws, int64_t ws_bytes,
+                          void* stream);
+/* d_gain (n_rows, n_settings): G_d(x) = k_d^T (S(x) + diag nu(x))^-1 k_d with k_d = K_d.(x) — the variance of theta_d
+ * that the best LINEAR estimator of theta_d from one reading at x removes: exact for a model that is linear in its
+ * parameters with a Gaussian cloud, in general a lower bound on the expected reduction Var(E[theta_d | y]).  By a
+ * Cholesky factor L of S + diag nu (C <= 8, in registers, a lane per setting) and one forward solve per row, as the sum
+ * of squares |L^-1 k_d|^2; a pivot that is not > 0 gives NaN for that setting.  d_ycov, d_xcov, d_pvar: what
+ * obe_output_covariance left; d_noise_var: nu as (C,) with ld_noise == 0 or (C, n_settings) with row stride ld_noise.
+ * d_utility (n_settings,): U(x) = [sum_d h_weights[d] G_d(x) / V_d] / cost(x), a term with V_d == 0 being 0; h_weights
+ * NULL: 1 each; cost(x) = d_cost[x] if d_cost is given, else the scalar cost.  accumulate != 0: U is ADDED to what
+ * d_utility holds (a later tile of rows of the same request); 0: it is stored.  d_gain and d_utility may each be NULL
+ * (d_pvar is read for d_utility only).  n_rows 1..8, n_channels 1..OBE_MAX_CHANNELS.  Model-independent. */
+OBE_API int obe_variance_reduction(const double* d_ycov, const double* d_xcov, int32_t n_rows, int32_t n_channels,
+                           int64_t n_settings, const double* d_noise_var, int64_t ld_noise, const double* d_pvar,
+                           const double* h_weights, const double* d_cost, double cost, double* d_gain,
+                           double* d_utility, int32_t accumulate, void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

@@ -171,6 +171,8 @@ def snapshot(obj, on_device=False):
                   parameter_bounds=obj.parameter_bounds)
         if "_changed_pinned" in obj.__dict__:
             st["constraint_count"] = obj.last_constraint_count
+        if obj._interest is not None:            # (only when set: objects that never were write the snapshots they did)
+            st["parameters_of_interest"] = dict(dims=obj._interest[0], weights=np.array(obj._interest[1]))
         s = obj._sweeps
         # (the counters that decide the next sweep's form and shift; versions are kept as "is it this cloud")
         st["sweeps"] = dict(safe_streak=s.safe_streak, safe_run=s.safe_run, unshifted=s.unshifted, streak=s.streak,
@@ -279,6 +281,9 @@ def restore(state, device=None, settings_shard=None, into=None):
         s.updated_cloud = cloud if sw["updated_cloud"] else None
         # (a state written before there were bounds has none)
         obj._adopt_bounds(state.get("parameter_bounds"))
+        interest = state.get("parameters_of_interest")          # (absent: never set, or a state written before)
+        if interest is not None:
+            obj.set_parameters_of_interest(interest["dims"], interest["weights"])
     if "constraint_count" in state:
         changed = obj._changed_pinned = _lib.pinned_array(1, np.int64)
         changed[0] = state["constraint_count"]

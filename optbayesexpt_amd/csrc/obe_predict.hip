@@ -15,6 +15,9 @@
 //              loading it was built and measured: slower at both benchmark clouds)
 // K11 — scoring a measurement against the posterior predictive (further down): the log-density of readings and their
 // per-channel tail probabilities, noise included.  The geometry of the moments with lane <-> record.
+// K12 — design for parameters of interest (below K11): per setting the covariance of the model output with itself (S)
+// and with up to eight selected parameter rows (K), for obe_variance_reduction (obe_interest.hip).  The moments' two
+// passes and geometry; the second pass carries C (C + 1) / 2 + R C centred products per evaluation instead of C squares.
 #include <algorithm>
 
 #include "obe_models.h"
@@ -373,6 +376,143 @@ struct Score {
     }
 };
 
+// ---- K12: output-parameter covariance.  rows: the parameter rows of interest of one call, by value.
+constexpr int kCovRows = 8;                        // rows one call serves (R of predict_cov_kernel: 1, 4 or 8)
+constexpr int kCovStats = 2 * kCovRows;            // words: t_d (the rows' means), then V_d
+constexpr int kCovRowWords = kCovStats + 2 * kCovRows * kPostPartials;      // ... and the block partials of both
+
+struct CovRows {
+    int n;
+    int row[kCovRows];
+};
+constexpr int cov_pairs(int n_channels) { return n_channels * (n_channels + 1) / 2; }
+// the chunk partials of either pass: C means, then C (C + 1) / 2 + n_rows C products
+inline int64_t cov_words(int64_t n_particles, int64_t n_settings, int n_channels, int n_rows) {
+    const int slots = std::max(n_channels, cov_pairs(n_channels) + n_rows * n_channels);
+    return (int64_t)moment_chunks(n_particles, n_settings) * setting_tiles(n_settings) * kWave * slots;
+}
+
+// The cloud pass over the selected rows, grid (blocks, rows): partials (row, block) of sum w theta or, CENTRED, of
+// sum w (theta - t)^2 about t = (the first pass's partials, added as cov_rows_fold_kernel adds them) / sum w.
+template <bool CENTRED>
+__global__ __launch_bounds__(kBlock) void cov_rows_partial_kernel(const double* __restrict__ particles, int64_t ld_p,
+                                                                  int64_t n, const double* __restrict__ w, CovRows rows,
+                                                                  const double* __restrict__ first, const u64* __restrict__ hdr,
+                                                                  double* __restrict__ partials) {
+    __shared__ double red[kBlock / kWave];
+    const double* th = particles + (int64_t)rows.row[blockIdx.y] * ld_p;
+    double t = 0.0;
+    if (CENTRED) t = block_sum_array(first + (int64_t)blockIdx.y * gridDim.x, gridDim.x, red) / __longlong_as_double((long long)hdr[0]);
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const double wp = clean_weight(w[i]);
+        if (wp == 0.0) continue;                                 // (whatever theta is)
+        const double d = th[i] - t;
+        s += CENTRED ? wp * (d * d) : wp * th[i];
+    }
+    __syncthreads();
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) partials[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// stats[r] = t_r, stats[kCovRows + r] = pvar[r] = V_r; one workgroup per row
+__global__ __launch_bounds__(kBlock) void cov_rows_fold_kernel(const double* __restrict__ first, const double* __restrict__ second,
+                                                               int nb, const u64* __restrict__ hdr, double* __restrict__ stats,
+                                                               double* __restrict__ pvar) {
+    __shared__ double red[kBlock / kWave];
+    const double sw = __longlong_as_double((long long)hdr[0]);
+    const double t = block_sum_array(first + (int64_t)blockIdx.x * nb, nb, red) / sw;
+    __syncthreads();
+    const double v = block_sum_array(second + (int64_t)blockIdx.x * nb, nb, red) / sw;
+    if (threadIdx.x == 0) {
+        stats[blockIdx.x] = t;
+        stats[kCovRows + blockIdx.x] = v;
+        pvar[blockIdx.x] = v;
+    }
+}
+
+// The second pass of the moments with every centred product: per evaluation C (C + 1) / 2 FMAs for S and R C for K.
+// u_r = w (theta_r - t_r) is the same for all lanes and formed once per particle.  Rows beyond rows.n repeat row 0 and
+// are not written.  partials (chunk, C (C + 1) / 2 + rows.n C, padded settings).
+template <class M, int R>
+__global__ __launch_bounds__(kWave) void predict_cov_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                            int64_t n_s, const double* __restrict__ particles, int64_t ld_p,
+                                                            int64_t n, const double* __restrict__ w, int64_t chunk_len,
+                                                            const double* __restrict__ centre, CovRows rows,
+                                                            const double* __restrict__ stats, double* __restrict__ partials) {
+    constexpr int T = cov_pairs(M::NC);
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_s ? s : n_s - 1;                    // (the padding lanes repeat the last setting)
+    double x[M::NS], c0[M::NC], acc_s[T], acc_k[R][M::NC], t[R];
+    const double* th[R];
+#pragma unroll
+    for (int k = 0; k < M::NS; ++k) x[k] = settings[(int64_t)k * ld_s + sc];
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) c0[c] = centre[(int64_t)c * n_s + sc];
+#pragma unroll
+    for (int k = 0; k < T; ++k) acc_s[k] = 0.0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int rr = r < rows.n ? r : 0;
+        th[r] = particles + (int64_t)rows.row[rr] * ld_p;
+        t[r] = stats[rr];
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) acc_k[r][c] = 0.0;
+    }
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p] and the particle are the same for all lanes)
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        double y[M::NC], d[M::NC], u[R];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+#pragma unroll
+        for (int r = 0; r < R; ++r) u[r] = wp * (th[r][p] - t[r]);
+        int k = 0;
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            d[c] = y[c] - c0[c];
+            const double wd = wp * d[c];
+#pragma unroll
+            for (int c2 = 0; c2 <= c; ++c2) {
+                acc_s[k] = fma(wd, d[c2], acc_s[k]);
+                ++k;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc_k[r][c] = fma(u[r], d[c], acc_k[r][c]);
+        }
+    }
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+    const int64_t slots = T + (int64_t)rows.n * M::NC;
+    double* out = partials + (int64_t)blockIdx.y * slots * n_pad + s;
+#pragma unroll
+    for (int k = 0; k < T; ++k) out[k * n_pad] = acc_s[k];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (r < rows.n) {
+#pragma unroll
+            for (int c = 0; c < M::NC; ++c) out[(T + r * M::NC + c) * n_pad] = acc_k[r][c];
+        }
+    }
+}
+
+// ycov (pairs, n_settings; NULL: not wanted), xcov (slots - pairs, n_settings) = (the chunk partials, added in chunk
+// order) / sum w
+__global__ __launch_bounds__(kBlock) void predict_cov_fold_kernel(const double* __restrict__ partials, int chunks, int pairs,
+                                                                  int slots, int64_t n_pad, int64_t n_s,
+                                                                  const u64* __restrict__ hdr, double* __restrict__ ycov,
+                                                                  double* __restrict__ xcov) {
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_s) return;
+    const double sw = __longlong_as_double((long long)hdr[0]);
+    for (int k = ycov ? 0 : pairs; k < slots; ++k) {
+        double acc = 0.0;
+        for (int j = 0; j < chunks; ++j) acc += partials[((int64_t)j * slots + k) * n_pad + s];
+        double* out = k < pairs ? ycov + (int64_t)k * n_s : xcov + (int64_t)(k - pairs) * n_s;
+        out[s] = acc / sw;
+    }
+}
+
 }  // namespace
 }  // namespace obe
 
@@ -552,6 +692,83 @@ int obe_predictive_quantiles(const obe_model* m, const double* d_settings, int64
                                                                                     d_quantiles);
             OBE_CHECK_LAUNCH("predict_deliver_kernel");
         }
+        return 0;
+    });
+}
+
+int64_t obe_output_covariance_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels, int32_t n_rows) {
+    if (n_particles < 1) n_particles = 1;
+    if (n_settings < 1) n_settings = 1;
+    n_channels = std::min(std::max(n_channels, 1), OBE_MAX_CHANNELS);
+    n_rows = std::min(std::max(n_rows, 1), kCovRows);
+    return (kPredHeadWords + kCovRowWords + cov_words(n_particles, n_settings, n_channels, n_rows)) * (int64_t)sizeof(u64);
+}
+
+int obe_output_covariance(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                          const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                          const double* d_weights, const int32_t* h_rows, int32_t n_rows, double* d_mean, double* d_ycov,
+                          double* d_xcov, double* d_pvar, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!h_rows || !d_mean || !d_xcov || !d_pvar) return bad_arg("obe_output_covariance: null pointer");
+    if (n_rows < 1 || n_rows > kCovRows) return bad_arg("obe_output_covariance: 1..8 rows per call");
+    CovRows rows{};
+    rows.n = n_rows;
+    for (int r = 0; r < n_rows; ++r) {
+        if (h_rows[r] < 0 || h_rows[r] >= n_dims) return bad_arg("obe_output_covariance: row index out of range");
+        rows.row[r] = h_rows[r];
+    }
+    if (int rc = check_inputs("obe_output_covariance", m, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles,
+                              d_weights, d_ws))
+        return rc;
+    obe_model mm = *m;
+    if (int rc = obe_model_validate(&mm)) return rc;
+    if (n_dims > mm.n_params) return bad_arg("obe_output_covariance: n_dims beyond the model's parameter rows");
+    if (ws_bytes < obe_output_covariance_workspace_bytes(n_particles, n_settings, mm.n_channels, n_rows))
+        return bad_arg("obe_output_covariance: workspace too small");
+    hipStream_t st = as_stream(stream);
+    const PredWs ws = carve(d_ws);
+    const int64_t tiles = setting_tiles(n_settings);
+    if (tiles > 0x7fffffff) return bad_arg("obe_output_covariance: too many settings for one call");
+    // the chunks of obe_predictive_moments: its mean, bit for bit
+    const int chunks = moment_chunks(n_particles, n_settings);
+    const int64_t chunk_len = ((n_particles + chunks - 1) / chunks + kWave - 1) / kWave * kWave;
+    const int used = (int)((n_particles + chunk_len - 1) / chunk_len);
+    double* stats = reinterpret_cast<double*>(ws.body);
+    double* row_first = stats + kCovStats;
+    double* row_second = row_first + kCovRows * kPostPartials;
+    double* partials = stats + kCovRowWords;
+    if (int rc = enqueue_scale(d_weights, n_particles, ws, st)) return rc;
+    const int nb = std::min(stream_blocks(n_particles, kBlock * 8), kPostPartials);
+    cov_rows_partial_kernel<false><<<dim3(nb, n_rows), kBlock, 0, st>>>(d_particles, ld_p, n_particles, d_weights, rows,
+                                                                        nullptr, ws.hdr, row_first);
+    OBE_CHECK_LAUNCH("cov_rows_partial_kernel");
+    cov_rows_partial_kernel<true><<<dim3(nb, n_rows), kBlock, 0, st>>>(d_particles, ld_p, n_particles, d_weights, rows,
+                                                                       row_first, ws.hdr, row_second);
+    OBE_CHECK_LAUNCH("cov_rows_partial_kernel");
+    cov_rows_fold_kernel<<<n_rows, kBlock, 0, st>>>(row_first, row_second, nb, ws.hdr, stats, d_pvar);
+    OBE_CHECK_LAUNCH("cov_rows_fold_kernel");
+    return dispatch_model(mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        const dim3 grid((unsigned)tiles, (unsigned)used);
+        const int fold_blocks = (int)((n_settings + kBlock - 1) / kBlock);
+        predict_moment_kernel<Model, false><<<grid, kWave, 0, st>>>(mm, d_settings, ld_s, n_settings, d_particles, ld_p,
+                                                                    n_particles, d_weights, chunk_len, nullptr, partials);
+        OBE_CHECK_LAUNCH("predict_moment_kernel");
+        predict_fold_kernel<<<fold_blocks, kBlock, 0, st>>>(partials, used, Model::NC, tiles * kWave, n_settings, ws.hdr,
+                                                            d_mean);
+        OBE_CHECK_LAUNCH("predict_fold_kernel");
+        auto pass2 = [&](auto R) {
+            predict_cov_kernel<Model, decltype(R)::value><<<grid, kWave, 0, st>>>(
+                mm, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles, d_weights, chunk_len, d_mean, rows, stats,
+                partials);
+        };
+        if (n_rows == 1) pass2(std::integral_constant<int, 1>{});
+        else if (n_rows <= 4) pass2(std::integral_constant<int, 4>{});
+        else pass2(std::integral_constant<int, kCovRows>{});
+        OBE_CHECK_LAUNCH("predict_cov_kernel");
+        const int pairs = cov_pairs(Model::NC);
+        predict_cov_fold_kernel<<<fold_blocks, kBlock, 0, st>>>(partials, used, pairs, pairs + n_rows * Model::NC,
+                                                                tiles * kWave, n_settings, ws.hdr, d_ycov, d_xcov);
+        OBE_CHECK_LAUNCH("predict_cov_fold_kernel");
         return 0;
     });
 }

@@ -33,7 +33,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _bounds, _devrng, _lib, _predictive, _scoring
+from . import _bounds, _devrng, _interest, _lib, _predictive, _scoring
 from ._sweepstate import Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
@@ -45,7 +45,7 @@ MAX_ENTROPY_DRAWS = 2048        # csrc/obe_yspace.hip: kMaxDraws, the samples pe
 rng = np.random.default_rng()   # module-level generator of the reference (random_setting)
 
 UTILITY_METHODS = ["variance_approx", "pseudo_utility", "full_kld_utility", "max_min",
-                   "variance_full"]
+                   "variance_full", "parameter_variance"]
 SELECTION_METHODS = ["optimal", "good", "random"]
 
 
@@ -126,6 +126,10 @@ class OptBayesExpt(ParticlePDF):
         the full settings x particles sweep: every particle is a draw and the
         predicted variance is weighted by the particle weights (the N_DRAWS -> all
         limit of ``yvar_from_parameter_draws``).
+    ``utility_method='parameter_variance'``
+        design for the parameters of interest (``set_parameters_of_interest``): ``utility_parameter_variance``, the
+        expected fraction of each interesting parameter's variance that the best linear estimator from one reading
+        removes, per unit cost.  Needs a DeviceModel.
     ``settings_shard``
         a :class:`~optbayesexpt_amd.dist.SettingsShard`; this process then sweeps only
         its contiguous slice of the settings and ``opt_setting`` combines the per-rank
@@ -251,6 +255,7 @@ class OptBayesExpt(ParticlePDF):
         self._noise_src = None        # bytes of the default_noise_std the cached device value was made from
         self._alloc_scratch()
 
+        self._interest = None         # (rows, weights) of set_parameters_of_interest(); None: never set
         self.utility_y_space = np.array([])
         self.set_n_draws(n_draws)
         self.default_noise_std = np.ones((self.n_channels, 1)) * default_noise_std
@@ -267,6 +272,10 @@ class OptBayesExpt(ParticlePDF):
             _utility = self.utility_max_min
         elif utility_method == "full_kld_utility":
             _utility = self.utility_full_kld
+        elif utility_method == "parameter_variance":
+            if self._device_model is None:
+                raise ValueError("utility_method='parameter_variance' needs a DeviceModel")
+            _utility = self.utility_parameter_variance
         else:
             raise SyntaxError(f"Unknown utility method, {utility_method}. "
                               f"Valid utility methods are: {UTILITY_METHODS}")
@@ -444,6 +453,51 @@ class OptBayesExpt(ParticlePDF):
     def predictive_pvalue(self, settings, y_meas, sigma=None):
         """Two-sided p-value per channel, ``(n_channels, n_r)``: ``2 min(lower, upper)``, clipped to 1."""
         return _scoring.predictive_pvalue(self, settings, y_meas, sigma)
+
+    # ------------------------------------------------ which measurement teaches us about the parameter we care about?
+    # (extension: every utility of the reference scores a setting by how much the model output varies there, for any
+    # reason — obe_base.py:579-720 —; these look at the covariance, over the weighted cloud, between the model output
+    # and selected parameter rows, on the device (_interest.py, csrc/obe_predict.hip K12, csrc/obe_interest.hip), and
+    # change nothing of the cloud.  ``settings`` as predict() takes them; ``dims``: None = every parameter row, an int
+    # or a sequence of distinct row indices, the result rows in the order given.  Device models only.)
+    def output_covariance(self, settings=None, dims=None):
+        """``(mean (C, n_x), ycov (C, C, n_x), xcov (n_sel, C, n_x))`` over the cloud: ``predict()``'s mean, the
+        covariance of the model output's channels with one another, ``sum w (y_c - m_c)(y_c' - m_c') / sum w``, and of
+        each selected parameter with each channel, ``sum w (theta_d - t_d)(y_c - m_c) / sum w``."""
+        return _interest.output_covariance(self, settings, dims)
+
+    def expected_variance_reduction(self, settings=None, dims=None, sigma=None):
+        """``G (n_sel, n_x)``: ``G_d(x) = k_d^T (S(x) + diag nu(x))^-1 k_d`` with ``S``, ``k_d = xcov[d]`` of
+        ``output_covariance()`` and the noise variance ``nu`` — the variance of ``theta_d`` that the best LINEAR
+        estimator of ``theta_d`` from one reading at ``x`` removes.  It is exact for a model that is linear in its
+        parameters with a Gaussian cloud, and a lower bound on the expected posterior variance reduction
+        ``Var(E[theta_d | y])`` in general.  ``sigma``: the noise of a reading, a scalar, ``(C,)`` or ``(C, n_x)``;
+        None: ``yvar_noise_model()`` (per channel; per setting only with ``settings=None``).  NaN where
+        ``S + diag nu`` is not positive definite."""
+        return _interest.expected_variance_reduction(self, settings, dims, sigma)
+
+    def set_parameters_of_interest(self, dims=None, weights=None):
+        """The parameter rows that ``utility_parameter_variance()`` designs for (None: all rows) and their weights
+        ``a_d`` (finite, >= 0, not all zero; None: 1 each).  Travels with save / load / deepcopy."""
+        rows = _interest.check_dims(dims, self.n_dims)
+        self._interest = (rows, _interest.check_weights(weights, len(rows)))
+
+    @property
+    def parameters_of_interest(self):
+        """``(dims, weights)``: a tuple of parameter rows and their ``(n_sel,)`` weights (all rows, 1 each, until
+        ``set_parameters_of_interest()`` says otherwise)."""
+        if self._interest is None:
+            return tuple(range(self.n_dims)), np.ones(self.n_dims)
+        return self._interest[0], self._interest[1].copy()
+
+    def utility_parameter_variance(self):
+        """``U (N_s,)`` over the design grid: ``[sum_d a_d G_d(x) / V_d] / cost_estimate()`` over the parameters of
+        interest, ``G_d`` of ``expected_variance_reduction()`` under ``yvar_noise_model()`` and ``V_d`` the cloud's
+        variance of ``theta_d`` (a term with ``V_d == 0`` is 0) — the expected fraction of each interesting parameter's
+        variance that the best linear estimator from one reading removes, per unit cost (a lower bound on what the
+        full posterior removes on average, exact in the linear-Gaussian case).  On a sharded object every rank
+        computes the whole grid from its replica of the cloud."""
+        return _interest.utility_parameter_variance(self)
 
     def _setting_array(self, onesettingset):
         """The setting of a record, zero-padded to OBE_MAX_SETDIMS — in this object's record buffer:
