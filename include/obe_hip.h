@@ -753,6 +753,54 @@ OBE_API int obe_variance_reduction(const double* d_ycov, const double* d_xcov, i
                            const double* h_weights, const double* d_cost, double cost, double* d_gain,
                            double* d_utility, int32_t accumulate, void* stream);
 
+/* ---- assimilating a recorded data set: joint log-likelihood of many records, tempered update (extension) ----
+ * pdf_update() takes one reading at a time (obe_base.py:340-399); people with a recorded spectrum, yesterday's scan or
+ * a second model to compare evidences loop it R times.  The same work as one computation is n_records x n_particles
+ * model evaluations that stay on the chip: per particle the log of the product of the likelihoods the R updates would
+ * multiply the weights by (obe_base.py:451-461; obe_noiseparam.py:109-120 with sigma from parameter rows) — without the
+ * choke, which the caller applies as an exponent.  A record is a column, as for obe_predictive_logpdf: the setting point
+ * d_settings (n_setdims, n_records), the reading d_y_meas (C, n_records) and its noise: exactly one of d_sigma
+ * (C, n_records) and h_noise_rows (C rows of the cloud).  With f = what obe_eval_over_particles writes, bit for bit,
+ * and z_rc = (f_c(x_r; theta_i) - y_rc) / sigma_rc:
+ *   d_loglik[i] = sum_r sum_c [-z_rc^2 / 2 - log sigma_rc] - n_records (C / 2) log 2 pi
+ * for EVERY particle, whatever its weight.  NaN marks "contributes nothing": a particle with a noise row that is not
+ * > 0 (NaN included), a record with a sigma that is not > 0 (then every particle), a model output that is NaN or +-inf
+ * (or a sum of z^2 that overflows).  accumulate != 0: the result is ADDED to what d_loglik holds (a later tile of
+ * records of the same request, added in tile order); 0: it is stored.
+ * Lane <-> particle, its rows in registers; the records are packed once per call into a table (setting, reading, 1 /
+ * sigma) that is read with wave-uniform indices; sum log sigma is formed once per chunk of records (known sigma) or
+ * once per particle (noise rows).  Per record and channel: z = (f - y) (1 / sigma), q = fma(z, z, q), in record order;
+ * the chunk's term is -q / 2 - sum log sigma.  Grid = particle tiles x record chunks, the chunks' partial results are
+ * added in chunk order: no atomics, the same bits from run to run.  Nothing is waited for.  d_ws:
+ * obe_records_loglik_workspace_bytes(n_particles, n_records, the model's channels) bytes, a buffer of its own; the size
+ * does not shrink when an argument grows. */
+OBE_API int64_t obe_records_loglik_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels);
+OBE_API int obe_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                       const double* d_y_meas, int64_t ld_y, const double* d_sigma, int64_t ld_sigma,
+                       const int32_t* h_noise_rows, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                       int32_t accumulate, double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream);
+/* The sums a tempered update chooses its step from: w'_i = w_i exp(a (l_i - m)) for up to OBE_TEMPERED_MAX_TRIALS
+ * trial exponents a (each finite and >= 0) in one pass over the cloud (particlepdf.py:136-139 is w l / sum(w l), :236-258
+ * tests 1 / sum(w'^2)).  NaN and negative weights count as zero; a particle whose l is not finite is skipped.
+ *   h_sums[0] = m, the largest finite l over the particles whose weight is > 0 (-inf if there is none)
+ *   h_sums[1] = sum w over those particles
+ *   h_sums[2 + 2 t], h_sums[3 + 2 t] = S1 = sum w exp(a_t (l - m)), S2 = sum (w exp(a_t (l - m)))^2
+ * so that N_eff at exponent a_t is S1^2 / S2 and the evidence of the step log(S1 / sum w) + a_t m.  Block partials are
+ * folded in a fixed order, as obe_weight_sums folds its own.  (sync): the 2 + 2 n_trials words reach the host as
+ * obe_weight_sums' two do (h_sums page-locked: written by the last kernel and watched; else copied).  d_ws: at least
+ * OBE_TEMPERED_WS_BYTES bytes.  Model-independent.  (h_sums is obe_weight_sums' h_out: the delivery audit keeps the
+ * rule of this call in a table of its own, _audit._BATCH_RULES, and reads the arguments by these names.) */
+#define OBE_TEMPERED_MAX_TRIALS 16
+#define OBE_TEMPERED_WS_BYTES 131072
+OBE_API int obe_tempered_sums(const double* d_loglik, const double* d_weights, int64_t n_particles,
+                      const double* h_exponents, int32_t n_trials, void* d_ws, int64_t ws_bytes, double* h_sums,
+                      void* stream);
+/* d_lik_out[i] = exp(exponent (d_loglik[i] - shift)), and 0 where d_loglik[i] is not finite (NaN: nan_to_num's 0 of
+ * particlepdf.py:136-139; +inf as well — a stated deviation: nan_to_num would make it 1.8e308).  What
+ * obe_bayes_update_lik then multiplies the weights by.  No sync.  Model-independent. */
+OBE_API int obe_tempered_likelihood(const double* d_loglik, int64_t n_particles, double exponent, double shift,
+                            double* d_lik_out, void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

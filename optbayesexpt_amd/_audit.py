@@ -99,7 +99,7 @@ class _Audit(_NoAudit):
         self.violations = []
         self.counts = dict(zones=0, armed=0, waited=0, reads=0, syncs=0)
         self.rules = {}           # entry point -> (rule, the argument positions of the parameters it reads)
-        for fn, (rule, *names) in {**_RULES, **_BOUNDS_RULES}.items():
+        for fn, (rule, *names) in {**_RULES, **_BOUNDS_RULES, **_BATCH_RULES}.items():
             params = [name for _, name in PROTOTYPES[fn][1]]
             self.rules[fn] = (rule, tuple(params.index(name) for name in names))
 
@@ -282,6 +282,16 @@ _RULES = {
 _BOUNDS_RULES = {
     "obe_mask_bounds_moments": (_mask_moments, "n_dims", "h_first_moments", "h_count"),
     "obe_mask_bounds": (_delivered(words=1), "h_count"),
+}
+
+def _tempered_sums(a, n_trials, h_sums):
+    a._mark(_addr(h_sums), 2 + 2 * _int(n_trials), False)       # (waited for before it returned, as obe_weight_sums' two)
+
+
+# the sums of a tempered batch update (include/obe_hip.h: assimilating a recorded data set): obe_weight_sums' rule
+# for as many words as the call has trials, under the parameter names of its own prototype
+_BATCH_RULES = {
+    "obe_tempered_sums": (_tempered_sums, "n_trials", "h_sums"),
 }
 
 audit = _Audit() if os.environ.get("OBE_CHECK_DELIVERY") == "1" else _NoAudit()

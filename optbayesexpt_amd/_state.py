@@ -38,7 +38,7 @@ LIBRARY_ATTRIBUTES = frozenset((
     # OptBayesExpt
     "model_function", "setting_values", "allsettings", "setting_indices", "cons", "choke", "N_DRAWS", "pickiness",
     "measurement_results", "last_setting_index", "n_channels", "utility_y_space", "default_noise_std",
-    "utility_method", "utility", "get_setting", "last_sweep", "last_utility",
+    "utility_method", "utility", "get_setting", "last_sweep", "last_utility", "last_batch_update",
     # OptBayesExptNoiseParameter
     "noise_parameter_index",
     # OptBayesExptSweeper

@@ -513,6 +513,115 @@ __global__ __launch_bounds__(kBlock) void predict_cov_fold_kernel(const double* 
     }
 }
 
+// ---- K13a: the joint log-likelihood of a set of records, per particle.  Lane = one particle, its rows in registers;
+// the chunk's records one after the other from the packed table (the same record for all lanes: scalar loads).
+constexpr int kRecMinChunk = 32;                   // records per chunk at least
+
+// words of one record of the table: the setting point, the reading and, known sigma, 1 / sigma per channel
+template <class M, bool ROWS>
+constexpr int rec_words() { return M::NS + M::NC + (ROWS ? 0 : M::NC); }
+inline int rec_words_bound(int n_channels) { return OBE_MAX_SETDIMS + 2 * n_channels; }
+
+inline int64_t particle_tiles(int64_t n_particles) { return (n_particles + kWave - 1) / kWave; }
+inline int record_chunks(int64_t n_records, int64_t n_particles) {
+    const int64_t by_size = (n_records + kRecMinChunk - 1) / kRecMinChunk;
+    const int64_t by_grid = std::max<int64_t>(1, kMomentWaves / particle_tiles(n_particles));
+    return (int)std::max<int64_t>(1, std::min(by_size, by_grid));
+}
+
+// table (n_records, rec_words) and chunk_log[chunk] = sum over the chunk's records and channels of log sigma (NaN if
+// one of them is not > 0; ROWS: not written).  One workgroup per chunk; the block sum has a fixed order.
+template <class M, bool ROWS>
+__global__ __launch_bounds__(kBlock) void records_pack_kernel(const double* __restrict__ settings, int64_t ld_s, int64_t n_r,
+                                                              const double* __restrict__ y_meas, int64_t ld_y,
+                                                              const double* __restrict__ sigma, int64_t ld_sg,
+                                                              int64_t chunk_len, double* __restrict__ table,
+                                                              double* __restrict__ chunk_log) {
+    __shared__ double red[kBlock / kWave];
+    constexpr int W = rec_words<M, ROWS>();
+    const int64_t r0 = (int64_t)blockIdx.x * chunk_len;
+    const int64_t r1 = r0 + chunk_len < n_r ? r0 + chunk_len : n_r;
+    double logs = 0.0;
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += kBlock) {
+        double* rec = table + r * W;
+#pragma unroll
+        for (int k = 0; k < M::NS; ++k) rec[k] = settings[(int64_t)k * ld_s + r];
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            rec[M::NS + c] = y_meas[(int64_t)c * ld_y + r];
+            if (!ROWS) {
+                const double sg = sigma[(int64_t)c * ld_sg + r];
+                rec[M::NS + M::NC + c] = 1.0 / sg;
+                logs += sg > 0.0 ? log(sg) : __builtin_nan("");
+            }
+        }
+    }
+    if (!ROWS) {
+        const double s = block_sum(logs, red);
+        if (threadIdx.x == 0) chunk_log[blockIdx.x] = s;
+    }
+}
+
+// A particle's rows held in registers behind the interface of ParamRef: M::eval reads th(i) with constant i
+template <class M>
+struct HeldParticle {
+    double v[M::NREAD];
+    __device__ __forceinline__ void load(const double* __restrict__ particles, int64_t ld_p, int64_t p) {
+#pragma unroll
+        for (int k = 0; k < M::NREAD; ++k) v[k] = particles[(int64_t)k * ld_p + p];
+    }
+    __device__ __forceinline__ ParamRef ref() const { return ParamRef{v, 1}; }
+};
+
+// partials (chunk, padded particles): -q / 2 - sum log sigma over the chunk's records, q = sum_r sum_c z_rc^2 in record
+// order; NaN where the particle contributes nothing
+template <class M, bool ROWS>
+__global__ __launch_bounds__(kWave) void records_loglik_kernel(obe_model m, const double* __restrict__ table, int64_t n_r,
+                                                               int64_t chunk_len, const double* __restrict__ chunk_log,
+                                                               ScoreRows rows, const double* __restrict__ particles,
+                                                               int64_t ld_p, int64_t n, double* __restrict__ partials) {
+    constexpr int W = rec_words<M, ROWS>();
+    const int64_t i = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t p = i < n ? i : n - 1;                         // (the padding lanes repeat the last particle)
+    HeldParticle<M> held;
+    held.load(particles, ld_p, p);
+    double inv[M::NC], neg_log = 0.0;
+    bool ok = true;
+    if (ROWS) ok = load_noise<M>(rows, particles, ld_p, p, inv, neg_log);
+    const int64_t r0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t r1 = r0 + chunk_len < n_r ? r0 + chunk_len : n_r;
+    double q = 0.0;
+    for (int64_t r = r0; r < r1; ++r) {                          // (r and the record are the same for all lanes)
+        const double* rec = table + r * W;
+        double x[M::NS], y[M::NC];
+#pragma unroll
+        for (int k = 0; k < M::NS; ++k) x[k] = rec[k];
+        M::eval(x, held.ref(), m, y);
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const double z = (y[c] - rec[M::NS + c]) * (ROWS ? inv[c] : rec[M::NS + M::NC + c]);
+            q = fma(z, z, q);
+        }
+    }
+    // sum log sigma: once per chunk (known sigma), R times the particle's own (noise rows)
+    const double logs = ROWS ? -neg_log * (double)(r1 - r0) : chunk_log[blockIdx.y];
+    double l = -0.5 * q - logs;
+    if (!ok || !(q < kInf)) l = __builtin_nan("");               // (a NaN or +-inf model output leaves q NaN or +inf)
+    partials[(int64_t)blockIdx.y * ((int64_t)gridDim.x * kWave) + i] = l;
+}
+
+// d_loglik (n,) [+]= (the chunk partials, added in chunk order) - n_records (C / 2) log 2 pi
+__global__ __launch_bounds__(kBlock) void records_fold_kernel(const double* __restrict__ partials, int chunks, int64_t n_pad,
+                                                              int64_t n, double constant, int accumulate,
+                                                              double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    double acc = 0.0;
+    for (int j = 0; j < chunks; ++j) acc += partials[(int64_t)j * n_pad + i];
+    acc -= constant;
+    out[i] = accumulate ? out[i] + acc : acc;
+}
+
 }  // namespace
 }  // namespace obe
 
@@ -692,6 +801,70 @@ int obe_predictive_quantiles(const obe_model* m, const double* d_settings, int64
                                                                                     d_quantiles);
             OBE_CHECK_LAUNCH("predict_deliver_kernel");
         }
+        return 0;
+    });
+}
+
+// the table, the chunks' sum log sigma, the chunk partials: chunks x padded particles <= kMomentWaves x 64 + the padded
+// particles, whatever the number of records
+int64_t obe_records_loglik_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels) {
+    if (n_particles < 1) n_particles = 1;
+    if (n_records < 1) n_records = 1;
+    n_channels = std::min(std::max(n_channels, 1), OBE_MAX_CHANNELS);
+    return (n_records * rec_words_bound(n_channels) + kMomentWaves
+            + ((int64_t)kMomentWaves + particle_tiles(n_particles)) * kWave) * (int64_t)sizeof(double);
+}
+
+int obe_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                       const double* d_y_meas, int64_t ld_y, const double* d_sigma, int64_t ld_sigma,
+                       const int32_t* h_noise_rows, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                       int32_t accumulate, double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!m || !d_settings || !d_y_meas || !d_particles || !d_loglik || !d_ws)
+        return bad_arg("obe_records_loglik: null pointer");
+    if (n_records < 1 || ld_s < n_records || ld_y < n_records || (d_sigma && ld_sigma < n_records))
+        return bad_arg("obe_records_loglik: n_records < 1 or a row of settings, y_meas or sigma shorter than that");
+    if (n_particles < 1 || ld_p < n_particles) return bad_arg("obe_records_loglik: bad cloud size");
+    if ((d_sigma != nullptr) == (h_noise_rows != nullptr))
+        return bad_arg("obe_records_loglik: exactly one of d_sigma and h_noise_rows");
+    obe_model mm = *m;
+    if (int rc = obe_model_validate(&mm)) return rc;
+    ScoreRows rows;
+    for (int c = 0; c < OBE_MAX_CHANNELS; ++c) {
+        rows.row[c] = (h_noise_rows && c < mm.n_channels) ? h_noise_rows[c] : 0;
+        if (rows.row[c] < 0 || rows.row[c] >= mm.n_params) return bad_arg("obe_records_loglik: noise row index out of range");
+    }
+    if (ws_bytes < obe_records_loglik_workspace_bytes(n_particles, n_records, mm.n_channels))
+        return bad_arg("obe_records_loglik: workspace too small");
+    const int64_t tiles = particle_tiles(n_particles);
+    if (tiles > 0x7fffffff) return bad_arg("obe_records_loglik: too many particles for one call");
+    const int chunks = record_chunks(n_records, n_particles);
+    const int64_t chunk_len = (n_records + chunks - 1) / chunks;
+    const int used = (int)((n_records + chunk_len - 1) / chunk_len);
+    hipStream_t st = as_stream(stream);
+    double* table = static_cast<double*>(d_ws);
+    double* chunk_log = table + n_records * rec_words_bound(mm.n_channels);
+    double* partials = chunk_log + kMomentWaves;
+    return dispatch_model(mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        const dim3 grid((unsigned)tiles, (unsigned)used);
+        if (h_noise_rows) {
+            records_pack_kernel<Model, true><<<used, kBlock, 0, st>>>(d_settings, ld_s, n_records, d_y_meas, ld_y, nullptr, 0,
+                                                                      chunk_len, table, chunk_log);
+            OBE_CHECK_LAUNCH("records_pack_kernel");
+            records_loglik_kernel<Model, true><<<grid, kWave, 0, st>>>(mm, table, n_records, chunk_len, chunk_log, rows,
+                                                                       d_particles, ld_p, n_particles, partials);
+        } else {
+            records_pack_kernel<Model, false><<<used, kBlock, 0, st>>>(d_settings, ld_s, n_records, d_y_meas, ld_y, d_sigma,
+                                                                       ld_sigma, chunk_len, table, chunk_log);
+            OBE_CHECK_LAUNCH("records_pack_kernel");
+            records_loglik_kernel<Model, false><<<grid, kWave, 0, st>>>(mm, table, n_records, chunk_len, chunk_log, rows,
+                                                                        d_particles, ld_p, n_particles, partials);
+        }
+        OBE_CHECK_LAUNCH("records_loglik_kernel");
+        records_fold_kernel<<<(int)((n_particles + kBlock - 1) / kBlock), kBlock, 0, st>>>(
+            partials, used, tiles * kWave, n_particles, (double)n_records * (Model::NC * kHalfLog2Pi), accumulate != 0,
+            d_loglik);
+        OBE_CHECK_LAUNCH("records_fold_kernel");
         return 0;
     });
 }

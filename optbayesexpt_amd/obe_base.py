@@ -33,7 +33,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _bounds, _devrng, _interest, _lib, _predictive, _scoring
+from . import _batch, _bounds, _devrng, _interest, _lib, _predictive, _scoring
 from ._sweepstate import Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
@@ -256,6 +256,8 @@ class OptBayesExpt(ParticlePDF):
         self._alloc_scratch()
 
         self._interest = None         # (rows, weights) of set_parameters_of_interest(); None: never set
+        #: dict of the most recent pdf_update_batch(): stages, n_eff, resamples, log_evidence (None: there was none)
+        self.last_batch_update = None
         self.utility_y_space = np.array([])
         self.set_n_draws(n_draws)
         self.default_noise_std = np.ones((self.n_channels, 1)) * default_noise_std
@@ -453,6 +455,38 @@ class OptBayesExpt(ParticlePDF):
     def predictive_pvalue(self, settings, y_meas, sigma=None):
         """Two-sided p-value per channel, ``(n_channels, n_r)``: ``2 min(lower, upper)``, clipped to 1."""
         return _scoring.predictive_pvalue(self, settings, y_meas, sigma)
+
+    # ------------------------------------------------ a recorded data set in one call
+    # (extension: pdf_update() takes one reading at a time — obe_base.py:340-399 —; a recorded spectrum, yesterday's
+    # scan or a data set re-analysed under a second model meant a loop of R calls.  These take R records at once, as
+    # the scoring methods above take them (``settings`` points, ``y_meas``, ``sigma`` — required here, refused by
+    # OptBayesExptNoiseParameter —, everything broadcast to n_r records): records x particles model evaluations on the
+    # device (_batch.py; csrc/obe_predict.hip K13a, csrc/obe_batch.hip K13b).  Device models only.)
+    def records_loglik(self, settings, y_meas, sigma=None):
+        """``(N_p,)`` float64: per particle the joint log-likelihood of the records, ``l_i = sum_r sum_c [-z_rc^2 / 2 -
+        log sigma_rc] - n_r (C / 2) log 2 pi`` with ``z = (model - y_meas) / sigma`` — the log of the product of the
+        factors R ``pdf_update()`` calls would multiply the weights by (without the choke).  For every particle,
+        whatever its weight; NaN where a particle contributes nothing (a noise parameter that is not > 0, a model
+        output that is not finite).  Changes nothing of the object."""
+        return _batch.records_loglik(self, settings, y_meas, sigma)
+
+    def pdf_update_batch(self, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None):
+        """Bayesian update from all the records at once; returns ``(particles, particle_weights)`` as ``pdf_update()``
+        does.  ``tempered=False``: one stage, ``w' ~ w exp(kappa l)`` (kappa = ``choke``, or 1), then the ordinary
+        resample test once — the reference's R sequential ``pdf_update()`` calls with ``auto_resample=False``
+        followed by one ``resample_test()``.  ``tempered=True`` (default): a joint update of many records collapses
+        the cloud (N_eff -> 1 in one step), so the exponent goes from 0 to 1 in stages, each the largest step
+        ``delta`` (to ``delta_max 2^-32``) that keeps ``N_eff / N`` at ``resample_threshold``, with ``resample()`` and
+        ``enforce_parameter_constraints()`` between stages and ``l`` recomputed on the new cloud; the last stage ends
+        like ``pdf_update()``.  A stage that cannot keep the threshold takes the smallest step and warns (once); after
+        ``max_stages`` the remainder is applied at once, with a warning.  ``on_stage(info)`` is called after every
+        stage's weights are in place, before its resample: ``info`` has ``stage``, ``delta``, ``beta`` (the exponent
+        reached), ``n_eff``, ``resamples`` and ``log_evidence`` so far.  ``last_batch_update`` keeps ``stages`` (the
+        deltas), ``n_eff`` (after each stage, before any resample), ``resamples`` and ``log_evidence`` = sum over the
+        stages of ``log(sum w exp(delta (l - m)) / sum w) + delta m``, the 2 pi constant included — for one stage
+        ``log p(y_1..R | data so far)``, the chain of ``predictive_logpdf()`` values; None when ``choke`` is set.  On a
+        settings-sharded object every replica computes the same update."""
+        return _batch.pdf_update_batch(self, settings, y_meas, sigma, tempered, max_stages, on_stage)
 
     # ------------------------------------------------ which measurement teaches us about the parameter we care about?
     # (extension: every utility of the reference scores a setting by how much the model output varies there, for any
