@@ -801,6 +801,51 @@ OBE_API int obe_tempered_sums(const double* d_loglik, const double* d_weights, i
 OBE_API int obe_tempered_likelihood(const double* d_loglik, int64_t n_particles, double exponent, double shift,
                             double* d_lik_out, void* stream);
 
+/* ---- design of a batch of measurements: output-output covariance and greedy conditioning (extension) ----
+ * opt_setting() answers "which ONE setting next"; an instrument that takes several points per round trip needs n
+ * settings that are jointly informative: the second must account for what the first will already have taught.  The
+ * quantity that needs is the covariance, over the weighted cloud, between the model output at every setting x and the
+ * output at an already chosen "pivot" point p.  With y, the cleaned weights, W and m_c(x) as for obe_output_covariance:
+ *   X_c'c(p, x) = sum w (y_c'(p) - m_c'(p)) (y_c(x) - m_c(x)) / W                     (X(x, x) is S(x))
+ * d_pivots (n_setdims, n_pivots) with row stride ld_pivots; n_pivots x C <= 8 rows per call.  d_mean (C, n_settings):
+ * mean_given != 0: an input, what obe_predictive_moments left for these settings; 0: computed here by the same launches
+ * (the same bits) and left there.  The pivots' means are formed inside the call, as a request of their own.
+ * d_cross (n_pivots, C, C, n_settings): [j, c', c, s] = X_c'c(p_j, x_s).  A table u_r,i = w_i (y_r(p; theta_i) - m_r) of
+ * the rows is written once per call (lane <-> particle; a particle of zero weight is never evaluated); the pass has
+ * obe_output_covariance's geometry and per evaluation the exact model, C subtractions and rows x C FMAs.  Chunk partials
+ * are folded in chunk order: no atomics, the same bits from run to run, for the pivots in any order and for any prefix
+ * of them.  sum w == 0 gives NaN.  Nothing is waited for.  d_ws: obe_output_cross_covariance_workspace_bytes(n_particles,
+ * n_settings, the model's channels, n_pivots) bytes, a buffer of its own; the size does not shrink when an argument
+ * grows. */
+OBE_API int64_t obe_output_cross_covariance_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels,
+                                                    int32_t n_pivots);
+OBE_API int obe_output_cross_covariance(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                                const double* d_pivots, int64_t ld_pivots, int32_t n_pivots,
+                                const double* d_particles, int64_t ld_p, int64_t n_particles,
+                                const double* d_weights, double* d_mean, int32_t mean_given, double* d_cross,
+                                void* d_ws, int64_t ws_bytes, void* stream);
+/* One step of the greedy design under the linear-Gaussian reading of obe_variance_reduction: conditions the output
+ * variance of every setting on one more planned reading, at the setting pivot_index, and scores what is left.  A
+ * reading is C scalar readings with noise nu_c'(p), taken in channel order; row m = rows_done + c':
+ *   a(c, x)   = X_c'c(p, x) - sum_{m' < m} L_m'(c, x) L_m'(c', p)         g = a(c', p) + nu_c'(p)
+ *   L_m(c, x) = a(c, x) / sqrt(g)        v_c(x) -= L_m(c, x)^2            *d_info += log(g / nu_c'(p)) / 2
+ *   U(x)      = [sum_c v_c(x) / nu_c(x)] / cost(x)
+ * d_cross (C, C, n_settings): the pivot's block of obe_output_cross_covariance; NULL: nothing is conditioned on, U is
+ * formed from d_cvar as it is (with d_cvar = the variance of obe_predictive_moments: the variance utility).  d_factors
+ * (max_rows, C, n_settings): rows [0, rows_done) are read, rows [rows_done, rows_done + C) written.  d_cvar (C,
+ * n_settings): v, in and out.  d_noise_var, ld_noise, d_cost, cost: as for obe_variance_reduction.  d_taken (n_settings,)
+ * bytes or NULL: a setting with a non-zero entry is never chosen.  d_utility (n_settings,): U.  d_best: 16 bytes, the
+ * largest FINITE utility (a double) and the first index that has it (an int64) — a NaN or infinite utility is never
+ * chosen, unlike np.argmax; NaN and -1 if there is none.  A g that is not > 0 or not finite makes its row NaN, and with
+ * it everything that follows.  Every thread forms the pivot column's values itself: nothing written by a launch is read
+ * by that launch.  After all rows *d_info = log det(I + N^-1/2 K_AA N^-1/2) / 2 in nats.  Exact for a model that is
+ * linear in its parameters with a Gaussian cloud, an approximation otherwise.  Everything stays in DEVICE memory, nothing
+ * is waited for.  Model-independent. */
+OBE_API int obe_design_step(const double* d_cross, int64_t pivot_index, double* d_factors, int32_t rows_done,
+                    int32_t max_rows, double* d_cvar, int32_t n_channels, int64_t n_settings,
+                    const double* d_noise_var, int64_t ld_noise, const double* d_cost, double cost,
+                    const uint8_t* d_taken, double* d_utility, double* d_best, double* d_info, void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

@@ -39,6 +39,7 @@ LIBRARY_ATTRIBUTES = frozenset((
     "model_function", "setting_values", "allsettings", "setting_indices", "cons", "choke", "N_DRAWS", "pickiness",
     "measurement_results", "last_setting_index", "n_channels", "utility_y_space", "default_noise_std",
     "utility_method", "utility", "get_setting", "last_sweep", "last_utility", "last_batch_update",
+    "last_batch_design",
     # OptBayesExptNoiseParameter
     "noise_parameter_index",
     # OptBayesExptSweeper

@@ -1,0 +1,174 @@
+// Design of a batch of measurements, the model-independent half: greedy conditioning of the output variance of every
+// setting on the readings already planned, from the blocks obe_output_cross_covariance (K14, obe_predict.hip) left.
+// A reading at the pivot p is C scalar readings, conditioned on one after the other; row m = rows_done + c':
+//   a(c, x)   = X_c'c(p, x) - sum_{m' < m} L_m'(c, x) L_m'(c', p)
+//   g         = a(c', p) + nu_c'(p)
+//   L_m(c, x) = a(c, x) / sqrt(g),   v_c(x) -= L_m(c, x)^2,   info += log(g / nu_c'(p)) / 2
+//   U(x)      = [sum_c v_c(x) / nu_c(x)] / cost(x)
+// Lane <-> setting.  Row m + 1 needs L_m at the pivot's column, which belongs to another workgroup: every thread forms the
+// pivot column's C x C values itself, from the inputs and the rows of earlier calls, by the same statements as its own
+// column (the thread of the pivot's setting finds the same bits twice).  Nothing a launch wrote is read by that launch.
+// The arg-max is a launch of its own, one workgroup, a fixed order.
+#include "obe_common.h"
+
+namespace obe {
+namespace {
+
+constexpr double kNaN = __builtin_nan("");
+constexpr double kHuge = __builtin_huge_val();
+
+struct DesignNoise {
+    const double* nu;            // (C,) with ld == 0, else (C, n_settings) with row stride ld
+    int64_t ld;
+    __device__ __forceinline__ double at(int c, int64_t s) const { return ld ? nu[(int64_t)c * ld + s] : nu[c]; }
+};
+
+// The rows of this pick at the column `col`: l[c'][c] = L_{m0 + c'}(c, col).  lp: the same at the pivot's column (PIVOT:
+// l itself, and rs[c'] = sqrt(g) and g[c'] are formed here; a g that is not > 0 or not finite gives NaN).
+template <int C, bool PIVOT>
+__device__ __forceinline__ void design_column(const double* __restrict__ cross, const double* __restrict__ factors, int m0,
+                                              int64_t n_s, int64_t col, int64_t p, const DesignNoise& noise,
+                                              double (&lp)[C][C], double (&g)[C], double (&rs)[C], double (&l)[C][C]) {
+#pragma unroll
+    for (int cp = 0; cp < C; ++cp) {
+        double a[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) a[c] = cross[((int64_t)cp * C + c) * n_s + col];
+        for (int mm = 0; mm < m0; ++mm) {
+            const double at_pivot = factors[((int64_t)mm * C + cp) * n_s + p];
+#pragma unroll
+            for (int c = 0; c < C; ++c) a[c] -= factors[((int64_t)mm * C + c) * n_s + col] * at_pivot;
+        }
+#pragma unroll
+        for (int k = 0; k < C; ++k) {
+            if (k < cp) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) a[c] -= l[k][c] * (PIVOT ? l[k][cp] : lp[k][cp]);
+            }
+        }
+        if (PIVOT) {
+            const double gg = a[cp] + noise.at(cp, p);
+            g[cp] = gg > 0.0 && gg < kHuge ? gg : kNaN;
+            rs[cp] = sqrt(g[cp]);
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) l[cp][c] = a[c] / rs[cp];
+    }
+}
+
+// cross NULL: nothing is conditioned on, U is formed from cvar as it is.
+template <int C>
+__global__ __launch_bounds__(kBlock) void design_step_kernel(const double* __restrict__ cross, int64_t p,
+                                                             double* __restrict__ factors, int m0,
+                                                             double* __restrict__ cvar, int64_t n_s, DesignNoise noise,
+                                                             const double* __restrict__ d_cost, double cost,
+                                                             double* __restrict__ utility, double* __restrict__ info) {
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_s) return;
+    double v[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = cvar[(int64_t)c * n_s + s];
+    if (cross) {
+        double lp[C][C], l[C][C], g[C], rs[C];
+        design_column<C, true>(cross, factors, m0, n_s, p, p, noise, lp, g, rs, lp);
+        design_column<C, false>(cross, factors, m0, n_s, s, p, noise, lp, g, rs, l);
+#pragma unroll
+        for (int cp = 0; cp < C; ++cp) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                v[c] -= l[cp][c] * l[cp][c];
+                factors[((int64_t)(m0 + cp) * C + c) * n_s + s] = l[cp][c];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) cvar[(int64_t)c * n_s + s] = v[c];
+        if (s == 0) {
+            double add = 0.0;
+#pragma unroll
+            for (int cp = 0; cp < C; ++cp) add += 0.5 * log(g[cp] / noise.at(cp, p));
+            *info += add;
+        }
+    }
+    double u = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) u += v[c] / noise.at(c, s);
+    utility[s] = u / (d_cost ? d_cost[s] : cost);
+}
+
+// best[0] = the largest finite utility of a setting that is not taken, best[1] (an int64) = the first index that has it;
+// NaN and -1 if there is none.  One workgroup; thread t scans t, t + 256, ... upwards, the threads are folded in order.
+__global__ __launch_bounds__(kBlock) void design_best_kernel(const double* __restrict__ utility, int64_t n_s,
+                                                             const unsigned char* __restrict__ taken,
+                                                             double* __restrict__ best) {
+    __shared__ double val[kBlock];
+    __shared__ int64_t idx[kBlock];
+    double bv = 0.0;
+    int64_t bi = -1;
+    for (int64_t s = threadIdx.x; s < n_s; s += kBlock) {
+        const double u = utility[s];
+        if (!(fabs(u) < kHuge) || (taken && taken[s])) continue;      // (NaN fails the comparison)
+        if (bi < 0 || u > bv) {
+            bv = u;
+            bi = s;
+        }
+    }
+    val[threadIdx.x] = bv;
+    idx[threadIdx.x] = bi;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int t = 1; t < kBlock; ++t) {
+            if (idx[t] >= 0 && (bi < 0 || val[t] > bv || (val[t] == bv && idx[t] < bi))) {
+                bv = val[t];
+                bi = idx[t];
+            }
+        }
+        best[0] = bi < 0 ? kNaN : bv;
+        reinterpret_cast<int64_t*>(best)[1] = bi;
+    }
+}
+
+template <int... C>
+int launch_step(int n_channels, std::integer_sequence<int, C...>, int blocks, hipStream_t st, const double* cross, int64_t p,
+                double* factors, int m0, double* cvar, int64_t n_s, const DesignNoise& noise, const double* d_cost, double cost,
+                double* utility, double* info) {
+    ((n_channels == C + 1 && (design_step_kernel<C + 1><<<blocks, kBlock, 0, st>>>(cross, p, factors, m0, cvar, n_s, noise,
+                                                                                 d_cost, cost, utility, info),
+                              true)) || ...);
+    OBE_CHECK_LAUNCH("design_step_kernel");
+    return 0;
+}
+
+}  // namespace
+}  // namespace obe
+
+using namespace obe;
+
+extern "C" {
+
+int obe_design_step(const double* d_cross, int64_t pivot_index, double* d_factors, int32_t rows_done, int32_t max_rows,
+                    double* d_cvar, int32_t n_channels, int64_t n_settings, const double* d_noise_var, int64_t ld_noise,
+                    const double* d_cost, double cost, const uint8_t* d_taken, double* d_utility, double* d_best,
+                    double* d_info, void* stream) {
+    if (!d_cvar || !d_noise_var || !d_utility || !d_best) return bad_arg("obe_design_step: null pointer");
+    if (n_channels < 1 || n_channels > OBE_MAX_CHANNELS) return bad_arg("obe_design_step: 1..8 channels");
+    if (n_settings < 1 || (ld_noise != 0 && ld_noise < n_settings))
+        return bad_arg("obe_design_step: n_settings < 1 or a row of the noise variance shorter than that");
+    if (d_cross) {
+        if (!d_factors || !d_info) return bad_arg("obe_design_step: null pointer");
+        if (pivot_index < 0 || pivot_index >= n_settings) return bad_arg("obe_design_step: pivot index outside the settings");
+        if (rows_done < 0 || (int64_t)rows_done + n_channels > max_rows)
+            return bad_arg("obe_design_step: the factor store has no room for this pivot's rows");
+    }
+    const int64_t blocks = (n_settings + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffff) return bad_arg("obe_design_step: too many settings for one call");
+    hipStream_t st = as_stream(stream);
+    const DesignNoise noise{d_noise_var, ld_noise};
+    if (int rc = launch_step(n_channels, std::make_integer_sequence<int, OBE_MAX_CHANNELS>{}, (int)blocks, st, d_cross,
+                             pivot_index, d_factors, rows_done, d_cvar, n_settings, noise, d_cost, cost, d_utility, d_info))
+        return rc;
+    design_best_kernel<<<1, kBlock, 0, st>>>(d_utility, n_settings, d_taken, d_best);
+    OBE_CHECK_LAUNCH("design_best_kernel");
+    return 0;
+}
+
+}  // extern "C"

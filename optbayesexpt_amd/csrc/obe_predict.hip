@@ -18,6 +18,9 @@
 // K12 — design for parameters of interest (below K11): per setting the covariance of the model output with itself (S)
 // and with up to eight selected parameter rows (K), for obe_variance_reduction (obe_interest.hip).  The moments' two
 // passes and geometry; the second pass carries C (C + 1) / 2 + R C centred products per evaluation instead of C squares.
+// K14 — design of a batch of measurements (below K13a): the covariance of the model output at every setting with the
+// output at up to eight "pivot" rows (a pivot point's channels), for obe_design_step (obe_design.hip).  K12's second pass
+// with a table row u_r,i = w_i (y_r(pivot; theta_i) - m_r) in theta's place and without the S products.
 #include <algorithm>
 
 #include "obe_models.h"
@@ -622,6 +625,83 @@ __global__ __launch_bounds__(kBlock) void records_fold_kernel(const double* __re
     out[i] = accumulate ? out[i] + acc : acc;
 }
 
+// ---- K14: output-output covariance.  Row r = pivot j * C + channel c' of the call's pivots, R = the rows padded to 1, 4
+// or 8.  table (n, R), one particle after the other: u_r = w (y_c'(p_j; theta) - m_c'(p_j)), 0 in the padding rows and
+// for a particle of zero weight (never evaluated: whatever its theta is).  pivot_mean (C, n_pivots).
+constexpr int kCrossRows = 8;                      // rows one call serves (R of predict_cross_kernel: 1, 4 or 8)
+
+template <class M, int R>
+__global__ __launch_bounds__(kBlock) void cross_table_kernel(obe_model m, const double* __restrict__ pivots, int64_t ld_piv,
+                                                             int n_pivots, const double* __restrict__ particles, int64_t ld_p,
+                                                             int64_t n, const double* __restrict__ w,
+                                                             const double* __restrict__ pivot_mean, double* __restrict__ table) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        double* row = table + i * R;
+        const double wp = clean_weight(w[i]);
+        int filled = 0;
+        if (wp != 0.0) {
+            for (int j = 0; j < n_pivots; ++j) {                 // (n_pivots * NC <= R: the host checked)
+                double x[M::NS], y[M::NC];
+#pragma unroll
+                for (int k = 0; k < M::NS; ++k) x[k] = pivots[(int64_t)k * ld_piv + j];
+                M::eval(x, ParamRef{particles + i, ld_p}, m, y);
+#pragma unroll
+                for (int c = 0; c < M::NC; ++c) row[j * M::NC + c] = wp * (y[c] - pivot_mean[c * n_pivots + j]);
+            }
+            filled = n_pivots * M::NC;
+        }
+        for (int r = filled; r < R; ++r) row[r] = 0.0;
+    }
+}
+
+// K12's second pass without S: per evaluation the exact model, C subtractions and R C FMAs.  The particle's weight and
+// its table row are the same for all lanes.  Rows beyond n_rows are zero in the table and are not written.  partials
+// (chunk, n_rows C, padded settings).
+template <class M, int R>
+__global__ __launch_bounds__(kWave) void predict_cross_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                              int64_t n_s, const double* __restrict__ particles, int64_t ld_p,
+                                                              int64_t n, const double* __restrict__ w, int64_t chunk_len,
+                                                              const double* __restrict__ centre,
+                                                              const double* __restrict__ table, int n_rows,
+                                                              double* __restrict__ partials) {
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_s ? s : n_s - 1;                    // (the padding lanes repeat the last setting)
+    double x[M::NS], c0[M::NC], acc[R][M::NC];
+#pragma unroll
+    for (int k = 0; k < M::NS; ++k) x[k] = settings[(int64_t)k * ld_s + sc];
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) c0[c] = centre[(int64_t)c * n_s + sc];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) acc[r][c] = 0.0;
+    }
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p], the particle and its row: the same for all lanes)
+        if (clean_weight(w[p]) == 0.0) continue;
+        double y[M::NC], u[R];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+#pragma unroll
+        for (int r = 0; r < R; ++r) u[r] = table[p * R + r];
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const double d = y[c] - c0[c];
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[r][c] = fma(u[r], d, acc[r][c]);
+        }
+    }
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+    double* out = partials + (int64_t)blockIdx.y * n_rows * M::NC * n_pad + s;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (r < n_rows) {
+#pragma unroll
+            for (int c = 0; c < M::NC; ++c) out[(r * M::NC + c) * n_pad] = acc[r][c];
+        }
+    }
+}
+
 }  // namespace
 }  // namespace obe
 
@@ -941,6 +1021,88 @@ int obe_output_covariance(const obe_model* m, const double* d_settings, int64_t 
         const int pairs = cov_pairs(Model::NC);
         predict_cov_fold_kernel<<<fold_blocks, kBlock, 0, st>>>(partials, used, pairs, pairs + n_rows * Model::NC,
                                                                 tiles * kWave, n_settings, ws.hdr, d_ycov, d_xcov);
+        OBE_CHECK_LAUNCH("predict_cov_fold_kernel");
+        return 0;
+    });
+}
+
+// the header, the pivots' means, the table (8 words a particle whatever R is), the chunk partials of the widest pass:
+// (kMomentWaves + setting tiles) x 64 x max(C, rows C) words bound chunks x padded settings whatever the cloud
+int64_t obe_output_cross_covariance_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels,
+                                                    int32_t n_pivots) {
+    if (n_particles < 1) n_particles = 1;
+    if (n_settings < 1) n_settings = 1;
+    n_channels = std::min(std::max(n_channels, 1), OBE_MAX_CHANNELS);
+    n_pivots = std::min(std::max(n_pivots, 1), kCrossRows);
+    const int rows = std::min(n_pivots * n_channels, kCrossRows);
+    return (kPredHeadWords + kCrossRows + n_particles * kCrossRows + moment_words(n_settings, rows * n_channels))
+           * (int64_t)sizeof(u64);
+}
+
+int obe_output_cross_covariance(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                                const double* d_pivots, int64_t ld_pivots, int32_t n_pivots, const double* d_particles,
+                                int64_t ld_p, int64_t n_particles, const double* d_weights, double* d_mean,
+                                int32_t mean_given, double* d_cross, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_pivots || !d_mean || !d_cross) return bad_arg("obe_output_cross_covariance: null pointer");
+    if (int rc = check_inputs("obe_output_cross_covariance", m, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles,
+                              d_weights, d_ws))
+        return rc;
+    obe_model mm = *m;
+    if (int rc = obe_model_validate(&mm)) return rc;
+    if (n_pivots < 1 || ld_pivots < n_pivots || (int64_t)n_pivots * mm.n_channels > kCrossRows)
+        return bad_arg("obe_output_cross_covariance: 1..8 rows (pivots x channels) per call, a row of pivots no shorter");
+    if (ws_bytes < obe_output_cross_covariance_workspace_bytes(n_particles, n_settings, mm.n_channels, n_pivots))
+        return bad_arg("obe_output_cross_covariance: workspace too small");
+    hipStream_t st = as_stream(stream);
+    const PredWs ws = carve(d_ws);
+    const int64_t tiles = setting_tiles(n_settings);
+    if (tiles > 0x7fffffff) return bad_arg("obe_output_cross_covariance: too many settings for one call");
+    // the chunks of obe_predictive_moments: its mean, bit for bit — for the settings and, a request of their own, the pivots
+    auto plan = [&](int64_t n_x, int64_t& chunk_len) {
+        const int chunks = moment_chunks(n_particles, n_x);
+        chunk_len = ((n_particles + chunks - 1) / chunks + kWave - 1) / kWave * kWave;
+        return (int)((n_particles + chunk_len - 1) / chunk_len);
+    };
+    int64_t chunk_len = 0, piv_chunk_len = 0;
+    const int used = plan(n_settings, chunk_len), piv_used = plan(n_pivots, piv_chunk_len);
+    double* pivot_mean = reinterpret_cast<double*>(ws.body);
+    double* table = pivot_mean + kCrossRows;
+    double* partials = table + n_particles * kCrossRows;
+    if (int rc = enqueue_scale(d_weights, n_particles, ws, st)) return rc;
+    return dispatch_model(mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        const dim3 grid((unsigned)tiles, (unsigned)used);
+        const int fold_blocks = (int)((n_settings + kBlock - 1) / kBlock);
+        const int n_rows = n_pivots * Model::NC;
+        predict_moment_kernel<Model, false><<<dim3(1, (unsigned)piv_used), kWave, 0, st>>>(
+            mm, d_pivots, ld_pivots, n_pivots, d_particles, ld_p, n_particles, d_weights, piv_chunk_len, nullptr, partials);
+        OBE_CHECK_LAUNCH("predict_moment_kernel");
+        predict_fold_kernel<<<1, kBlock, 0, st>>>(partials, piv_used, Model::NC, kWave, n_pivots, ws.hdr, pivot_mean);
+        OBE_CHECK_LAUNCH("predict_fold_kernel");
+        if (!mean_given) {
+            predict_moment_kernel<Model, false><<<grid, kWave, 0, st>>>(mm, d_settings, ld_s, n_settings, d_particles, ld_p,
+                                                                        n_particles, d_weights, chunk_len, nullptr, partials);
+            OBE_CHECK_LAUNCH("predict_moment_kernel");
+            predict_fold_kernel<<<fold_blocks, kBlock, 0, st>>>(partials, used, Model::NC, tiles * kWave, n_settings, ws.hdr,
+                                                                d_mean);
+            OBE_CHECK_LAUNCH("predict_fold_kernel");
+        }
+        auto pass = [&](auto R) {
+            constexpr int kR = decltype(R)::value;
+            if constexpr (kR >= Model::NC) {                     // (a call has at least one pivot: C rows)
+                cross_table_kernel<Model, kR><<<stream_blocks(n_particles, kBlock), kBlock, 0, st>>>(
+                    mm, d_pivots, ld_pivots, n_pivots, d_particles, ld_p, n_particles, d_weights, pivot_mean, table);
+                predict_cross_kernel<Model, kR><<<grid, kWave, 0, st>>>(mm, d_settings, ld_s, n_settings, d_particles, ld_p,
+                                                                        n_particles, d_weights, chunk_len, d_mean, table,
+                                                                        n_rows, partials);
+            }
+        };
+        if (n_rows == 1) pass(std::integral_constant<int, 1>{});
+        else if (n_rows <= 4) pass(std::integral_constant<int, 4>{});
+        else pass(std::integral_constant<int, kCrossRows>{});
+        OBE_CHECK_LAUNCH("predict_cross_kernel");
+        predict_cov_fold_kernel<<<fold_blocks, kBlock, 0, st>>>(partials, used, 0, n_rows * Model::NC, tiles * kWave,
+                                                                n_settings, ws.hdr, nullptr, d_cross);
         OBE_CHECK_LAUNCH("predict_cov_fold_kernel");
         return 0;
     });

@@ -33,7 +33,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _batch, _bounds, _devrng, _interest, _lib, _predictive, _scoring
+from . import _batch, _bounds, _design, _devrng, _interest, _lib, _predictive, _scoring
 from ._sweepstate import Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
@@ -258,6 +258,7 @@ class OptBayesExpt(ParticlePDF):
         self._interest = None         # (rows, weights) of set_parameters_of_interest(); None: never set
         #: dict of the most recent pdf_update_batch(): stages, n_eff, resamples, log_evidence (None: there was none)
         self.last_batch_update = None
+        self.last_batch_design = None
         self.utility_y_space = np.array([])
         self.set_n_draws(n_draws)
         self.default_noise_std = np.ones((self.n_channels, 1)) * default_noise_std
@@ -532,6 +533,35 @@ class OptBayesExpt(ParticlePDF):
         full posterior removes on average, exact in the linear-Gaussian case).  On a sharded object every rank
         computes the whole grid from its replica of the cloud."""
         return _interest.utility_parameter_variance(self)
+
+    # ------------------------------------------------ which n measurements, taken together, teach the most?
+    # (extension: opt_setting() answers "which one setting next" — obe_base.py:733-756 — and returns the same setting
+    # n times when called n times without an update; an instrument that takes several points per round trip needs n
+    # settings that are jointly informative.  Greedy conditioning of the output variance on the readings already
+    # planned, under the linear-Gaussian reading expected_variance_reduction() uses: exact for a model that is linear
+    # in its parameters with a Gaussian cloud, an approximation otherwise, and greedy, not optimal.  On the device
+    # (_design.py; csrc/obe_predict.hip K14, csrc/obe_design.hip); changes nothing of the cloud, the weights, the
+    # generator, last_setting_index or a sweep enqueued ahead.  Device models only.)
+    def output_cross_covariance(self, points, settings=None):
+        """``X (n_points, C, C, n_x)`` over the cloud: ``X[j, c', c, s] = sum w (y_c'(p_j) - m_c'(p_j)) (y_c(x_s) -
+        m_c(x_s)) / sum w``, the covariance of the model output at the setting ``x_s`` with the output at the point
+        ``p_j``.  ``points`` and ``settings`` as ``predict()`` takes settings; ``settings=None``: the design grid."""
+        return _design.output_cross_covariance(self, points, settings)
+
+    def opt_setting_batch(self, n, sigma=None, distinct=False):
+        """The next ``n`` settings of the design grid, chosen one after the other: a tuple of ``n_setdims`` arrays of
+        length ``n`` in pick order, which ``pdf_update_batch(xs, y, sigma)`` takes as they are.  Pick 0 maximises
+        ``[sum_c var_c(x) / nu_c(x)] / cost_estimate()``, the ``variance_full`` utility; every later pick maximises the
+        same with ``var_c(x)`` conditioned on noisy readings at the picks before it (linear-Gaussian: an
+        approximation for a model that is not linear in its parameters; greedy, not the optimal set).  ``sigma``: the
+        noise of a reading, a scalar, ``(C,)`` or ``(C, N_s)``; None: ``yvar_noise_model()``; it must be finite and
+        > 0.  A setting may be picked twice (a noisy reading leaves variance) unless ``distinct``.  First maximum; a
+        utility that is NaN or infinite is never chosen (``np.argmax`` would choose a NaN).  ``n * n_channels <= 128``.
+        Independent of ``utility_method``; ``last_setting_index`` stays.  ``last_batch_design`` keeps ``indices``
+        (into the design grid), ``utility`` (of each pick when it was made) and ``information`` (nats the first j + 1
+        readings are expected to deliver, ``log det(I + N^-1/2 K N^-1/2) / 2``).  On a settings-sharded object every
+        rank computes the whole grid from its replica and reaches the same picks."""
+        return _design.opt_setting_batch(self, n, sigma, distinct)
 
     def _setting_array(self, onesettingset):
         """The setting of a record, zero-padded to OBE_MAX_SETDIMS — in this object's record buffer:

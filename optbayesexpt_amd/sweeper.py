@@ -199,6 +199,11 @@ class OptBayesExptSweeper(OptBayesExptNoiseParameter):
         self.last_setting_index = index
         return self.start_stop_indices[index]
 
+    def opt_setting_batch(self, n, sigma=None, distinct=False):
+        """Refused: a sweeper's settings are (start, stop) intervals, and a batch design picks points."""
+        raise TypeError("opt_setting_batch() designs a batch of point measurements; the settings of an "
+                        "OptBayesExptSweeper are (start, stop) intervals")
+
     def good_setting(self):
         """A (start, stop) pair drawn with probability ~ utility**pickiness
         (obe_sweeper.py:169-193); consumes one uniform of this module's ``rng`` (rank 0's value on a
