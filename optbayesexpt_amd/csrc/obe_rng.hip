@@ -12,7 +12,7 @@
 //                        stores, no serial dependence between threads.
 //   uniform              (raw >> 11) * 2^-53, numpy's next_double.
 //   normals              numpy's ziggurat consumes a *variable* number of raw values per
-//                        normal (1 for 98.8 % of them), so "which raw value starts the k-th
+//                        normal (1 for about 98.5 % of them), so "which raw value starts the k-th
 //                        normal" is a serial question.  It is answered in parallel:
 //                          classify  every raw position i as if a normal started there:
 //                                    value[i] and length[i] (raw values consumed);
@@ -22,6 +22,20 @@
 //                                    skip (an anchor) and follows the chain from there;
 //                          compact   prefix sum over the start flags = index of the normal;
 //                                    scatter value[i] to out[rank[i]].
+//   Contract of the raw stream (what `starts` relies on; stated here once, tests/_ziggurat_oracle.py checks it on
+//   every stream the tests build):
+//     * a draw consumes at most kMaxLen = 32 raw values.  A longer one, or one that runs off the buffer, gets
+//       length 0 and ends the chain there; obe_ziggurat_check therefore only accepts an n-th normal that ends
+//       2 * kMaxLen values before the end of the buffer, and the caller regenerates a longer buffer otherwise;
+//     * anchors — positions a that no jump q -> q + length[q] from the 32 positions before them passes — lie at
+//       most 32 positions apart, so a thread finds one within the 31 positions before its own.  The step-back
+//       loop of zig_starts_kernel stops there without a test (`a <= kMaxLen`): on a stream that breaks this the
+//       start flags are silently wrong, not an error.
+//   A stream of a random generator keeps both with room to spare: about 1.5 % of the raw values leave their
+//   rectangle as a first value and about half of those are then rejected, so a draw of more than 32 values needs
+//   16 rejections in a row, and 32 positions without an anchor need a run of about 16 consecutive positions that
+//   each start such a draw: an estimate, not a measurement, of 0.015^16 < 1e-28 per position.  (The longest draw
+//   in 200 000 normals is 5.)
 //   The ziggurat tables (ki, wi, fi) are data supplied by the host
 //   (optbayesexpt_amd/data/ziggurat_tables.npz, see tools/make_ziggurat_tables.py).
 #include <cstdlib>
@@ -133,7 +147,7 @@ __device__ __forceinline__ double zig_classify_one(Next&& next, int64_t left, co
         const uint64_t rabs = (r >> 1) & 0x000fffffffffffffULL;
         x = (double)rabs * t.wi[idx];
         if (sign) x = -x;
-        if (rabs < t.ki[idx]) break;                       // 99.3 %: inside the rectangle
+        if (rabs < t.ki[idx]) break;                       // ~98.5 %: inside the rectangle
         if (idx == 0) {                                    // tail of the base strip
             for (;;) {
                 if (used + 1 >= left || used + 2 > kMaxLen) { bad = true; break; }
@@ -176,10 +190,10 @@ __global__ __launch_bounds__(kBlock) void zig_classify_kernel(const uint64_t* __
 // classified, indexed from n_uniform.  One launch instead of three (raw values, uniforms, classify), and 8 B
 // per position less written and twice less read.
 //
-// The classification is split in two: 99.3 % of the draws end inside their ziggurat rectangle after one
+// The classification is split in two: about 98.5 % of the draws end inside their ziggurat rectangle after one
 // table look-up — this kernel finishes those — and the others (wedge: a second raw value and an exp; tail:
 // log1p pairs) are only QUEUED here, {relative position, 128-bit generator state}, in the workgroup's own
-// segment of a list, for zig_slow_kernel.  With 1.2 % of the lanes taking those branches, half of all
+// segment of a list, for zig_slow_kernel.  With about 1.5 % of the lanes taking those branches, half of all
 // wavefront trips used to pay for them (49 us for 5.8 M positions; the fast part alone is bound by its 9 B
 // of stores per position).  A segment that is full (128 entries for ~40 expected) makes the lane take the
 // branches in place, as before.
@@ -431,7 +445,7 @@ __device__ __forceinline__ uint32_t flag_tile_scan(uint32_t (&v)[kFlagItems], ui
 // The tile of candidate values is staged through LDS: a thread needs the flags of 8 CONSECUTIVE
 // positions for the scan, but reading val[] and writing out[] that way makes every load / store
 // instruction of a wave touch 64 different cache lines; instead the tile is read with lane-contiguous
-// loads, compacted inside LDS (98.8 % of the positions are starts) and written out lane-contiguously.
+// loads, compacted inside LDS (about 98 % of the positions are starts) and written out lane-contiguously.
 // (host: the device view of the caller's page-locked {consumed, found}, with `counter` the stream's arrival
 // counter — then the workgroup that finishes last stores both there, `found` behind a system-scope fence:
 // the host watches that word instead of waiting for a copy and a stream synchronisation)
