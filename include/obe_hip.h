@@ -461,8 +461,8 @@ OBE_API int obe_power_normalize(const double* d_u, int64_t n, double exponent, d
  *                        ddof=0 variance (np.var over utility_y_space, obe_base.py:488)
  * d_moments: output of obe_moments for the same particles/weights (mean parameters are
  * used as the variance shift, sum w as the normaliser).
- * `shifted` is a bit set: OBE_SWEEP_SHIFTED (1) and, for expression (plugin) models,
- * OBE_SWEEP_SAFE (2).
+ * `shifted` is a bit set: OBE_SWEEP_SHIFTED (1), for expression (plugin) models
+ * OBE_SWEEP_SAFE (2), and for the one-peak Lorentzian OBE_SWEEP_CELLS (4).
  * OBE_SWEEP_SHIFTED set: moments are accumulated about a per-setting shift (always accurate).
  * OBE_SWEEP_SHIFTED clear: one instruction fewer per evaluation, accurate only while the predicted
  * mean does not dominate the spread; *h_kappa (nullable) returns the worst
@@ -523,6 +523,25 @@ OBE_API int obe_power_normalize(const double* d_u, int64_t n, double exponent, d
  * unconditional — the caller knows the cloud is final (after a resample) and collects the page-locked
  * result words later with obe_host_words_wait(). */
 #define OBE_SWEEP_NOWAIT 16
+/* OBE_SWEEP_CELLS: the one-peak Lorentzian's unshifted sweep summed by cell expansions (csrc/obe_models.h:
+ * LorentzCells) instead of pair by pair — the setting axis x/d is cut into cells of half-width
+ * 1 / OBE_CELL_RHO_INV, every particle adds OBE_CELL_ORDER Taylor coefficients of the two moments to each cell,
+ * and a setting evaluates its cell's two polynomials.  The same moments to rounding (not the same bits), whatever
+ * the order of the settings.  Ignored for every other model, with OBE_SWEEP_SHIFTED or OBE_SWEEP_SAFE, and for
+ * the one-workgroup sweeps.  A call whose settings span more than OBE_CELL_MAX cells, hold a non-finite value, or
+ * whose d is not finite and positive returns *h_kappa = NaN and NaN variances: the caller repeats it without the
+ * bit.  obe_sweep_cells_plan() says beforehand whether a grid fits and whether the form pays. */
+#define OBE_SWEEP_CELLS 4
+#define OBE_CELL_RHO_INV 4
+#define OBE_CELL_ORDER 28
+#define OBE_CELL_MAX 128
+/* the cell form is worth taking when the direct form's FP64 issue slots are at least this many times its own */
+#define OBE_CELL_MIN_GAIN 2
+/* Host only, nothing is launched: bit 0 — the cell form is valid for settings within [x_min, x_max] and the width d
+ * (the span is within OBE_CELL_MAX cells, everything finite, d > 0); bit 1 — it is also worthwhile: n_settings
+ * direct evaluations per particle cost at least OBE_CELL_MIN_GAIN times the issue slots of the cells' expansions,
+ * and the sweep's n_draws draws (the particles, for a full sweep) are enough to fill the expansion kernel's grid. */
+OBE_API int obe_sweep_cells_plan(double x_min, double x_max, double d, int64_t n_settings, int64_t n_draws);
 /* Settings one lane of the sweep kernel owns at most for a grid of n_settings (1, 2, 4 or 8; a sweep of
  * few draws may use fewer): the number of denominators a model's fast form inverts together, which a
  * caller that predicts whether a settings grid stays inside that form's range needs

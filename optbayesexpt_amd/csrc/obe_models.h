@@ -508,6 +508,89 @@ struct Lorentz {
     }
 };
 
+// ---- the one-peak Lorentzian's unshifted moments by cell expansions (OBE_SWEEP_CELLS) ----
+// With tau = x/d, tau0 = x0/d, b' = b - bbar and r = 1 / ((tau - tau0)^2 + 1), the two moments of a setting are
+//   S1(tau) = sum_p w (a r + b'),   S2(tau) = sum_p w (a r + b')^2 = sum_p w a^2 r^2 + 2 w a b' r + w b'^2:
+// sums of rational functions of tau whose poles, tau0 +- i, are never closer than 1 to the real axis.  About the
+// centre tau_c of a cell of half-width rho < 1 every particle, near or far, has a Taylor series in
+// delta = tau - tau_c that converges with ratio <= rho, so the particles need not meet the settings one by one:
+// per (cell, particle), with s = tau_c - tau0, q0 = s^2 + 1, B = -1/q0, A = 2 s B,
+//   r_0 = 1/q0,   r_{-1} = 0,   r_{k+1} = A r_k + B r_{k-1}                                   (series of r)
+//   f_0 = r_0^2,  f_{-1} = 0,   f_{k+1} = (k+2)/(k+1) A f_k + (k+3)/(k+1) B f_{k-1}           (series of r^2)
+//   R_k += (w a) r_k,           H_k += (2 w a b') r_k + (w a^2) f_k
+// and per setting  S1 = C1 + sum_k R_k delta^k,  S2 = C2 + sum_k H_k delta^k  (Horner), C1 = sum w b',
+// C2 = sum w b'^2.  The recurrences are real and three-term: |r_k| <= 1, |f_k| <= k + 1, nothing cancels (the
+// 1/(tau - z) moments of the complex form cancel by tau^2) and nothing is inverted in a batch, so there is no
+// overflow range short of s^2 itself.  The code carries g_k = f_k / (k + 1), whose recurrence
+//   g_{k+1} = A g_k + m_k B g_{k-1},   m_k = k (k + 3) / ((k + 1)(k + 2)),
+// has one constant instead of two, and sums G_k = sum (w a^2) g_k and Q_k = sum (2 w a b') r_k apart:
+// H_k = Q_k + (k + 1) G_k once per chunk.  8 FP64 issue slots per order instead of 9.
+// Truncation: the neglected tail of r^2 is below (P + 1) rho^P / (1 - rho)  (P = kOrder terms); rho = 1/4, P = 28
+// gives 29 * 2^-56 * 4/3 = 5e-16 ("Cell expansions").
+struct LorentzCells {
+    static constexpr int kOrder = OBE_CELL_ORDER;
+    static constexpr int kMaxCells = OBE_CELL_MAX;
+    static constexpr double kWidth = 2.0 / OBE_CELL_RHO_INV;         // of a cell: 2 rho
+    static constexpr int kCoefs = 2 * kOrder + 2;                    // R_k, H_k, C1, C2 of one cell
+    static_assert((OBE_CELL_RHO_INV & (OBE_CELL_RHO_INV - 1)) == 0 && OBE_CELL_RHO_INV >= 2, "rho: a power of 1/2");
+
+    // centre of cell c of a plan that starts at `origin` (the same expression wherever a centre is needed)
+    __device__ __forceinline__ static double centre(double origin, int c) {
+        return fma((double)c + 0.5, kWidth, origin);
+    }
+    static constexpr double m_of(int k) { return (double)k * (k + 3) / ((double)(k + 1) * (k + 2)); }
+
+    // running sums of one cell (one lane): three per order, and C1, C2
+    struct Sums {
+        double R[kOrder], Q[kOrder], G[kOrder], c1, c2;
+        __device__ __forceinline__ void clear() {
+#pragma unroll
+            for (int k = 0; k < kOrder; ++k) R[k] = Q[k] = G[k] = 0.0;
+            c1 = c2 = 0.0;
+        }
+        __device__ __forceinline__ double h(int k) const { return fma((double)(k + 1), G[k], Q[k]); }
+    };
+    // one packed particle (tau0, sw a, sw b', sw: Lorentz<1>::pack) into the sums of the cell centred at tc
+    __device__ __forceinline__ static void add_particle(double tc, const double* pk, Sums& z) {
+        const double s = tc - pk[0];
+        const double r0 = exact_rcp(fma(s, s, 1.0));       // q0 >= 1
+        const double B = -r0, A = (s + s) * B;
+        const double wa = pk[1] * pk[3], waa = pk[1] * pk[1], wab2 = (pk[1] + pk[1]) * pk[2];
+        z.c1 = fma(pk[2], pk[3], z.c1);
+        z.c2 = fma(pk[2], pk[2], z.c2);
+        double r = r0, g = r0 * r0, Brp = 0.0, Bgp = 0.0;   // B r_{k-1}, B g_{k-1}
+#pragma unroll
+        for (int k = 0; k < kOrder; ++k) {
+            z.R[k] = fma(wa, r, z.R[k]);
+            z.Q[k] = fma(wab2, r, z.Q[k]);
+            z.G[k] = fma(waa, g, z.G[k]);
+            if (k + 1 < kOrder) {
+                const double rn = fma(A, r, Brp), gn = fma(A, g, m_of(k) * Bgp);
+                Brp = B * r;
+                Bgp = B * g;
+                r = rn;
+                g = gn;
+            }
+        }
+    }
+    // a setting's two moments from its cell's coefficients coef[j * stride], j = 0 .. kCoefs-1 (R_k at k, H_k at
+    // kOrder + k, C1, C2 last), delta = tau - centre
+    __device__ __forceinline__ static void evaluate(const double* coef, int64_t stride, double delta, double& S1,
+                                                    double& S2) {
+        double c[kCoefs];
+#pragma unroll
+        for (int j = 0; j < kCoefs; ++j) c[j] = coef[j * stride];
+        double p1 = c[kOrder - 1], p2 = c[2 * kOrder - 1];
+#pragma unroll
+        for (int k = kOrder - 2; k >= 0; --k) {
+            p1 = fma(p1, delta, c[k]);
+            p2 = fma(p2, delta, c[kOrder + k]);
+        }
+        S1 = p1 + c[2 * kOrder];
+        S2 = p2 + c[2 * kOrder + 1];
+    }
+};
+
 // y = p0 + p1 * x        tests/test_optbayesexpt.py:11-14
 struct LineAB {
     static constexpr int NS = 1, NC = 1, NREAD = 2, NXS = 1, NPK = 2, NCONST = 0;

@@ -27,6 +27,7 @@
 // Variance numerics: moments are accumulated about a per-setting shift
 // c_s = model(x_s; mean parameters), so  var = (S2 - S1^2/W)/W  does not cancel
 // catastrophically (np.var is two-pass; the shift plays the role of its first pass).
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -369,6 +370,248 @@ __global__ __launch_bounds__(kBlock) void sweep_kernel(SweepArgs a) {
         }
     }
 }
+
+// ---- the cell form of the one-peak Lorentzian's unshifted sweep (OBE_SWEEP_CELLS; obe_models.h: LorentzCells) ----
+// Three launches in place of sweep_kernel, behind cell_plan_kernel:
+//   cell_moments_kernel  lane <-> cell, the packed particles streamed through the scalar path exactly as in
+//                        sweep_kernel (no cross-lane reduction); a workgroup is 4 waves that own the same 64 cells
+//                        and a quarter each of one particle chunk, added in wave order through LDS: partial
+//                        coefficients (chunk, coefficient, cell).
+//   cell_fold_kernel     the chunks of one coefficient row summed by 16 wavefronts in a fixed order.
+//   cell_eval_kernel     setting -> cell -> Horner; writes part1 / part2 as ONE chunk of sweep_kernel's layout and
+//                        cs_out = 0, so that sweep_finalize, argmax_fold and the result record are what they were.
+// No floating-point atomics; every sum has a fixed association, so two calls on the same inputs give the same bits.
+struct CellPlan {          // written by cell_plan_kernel
+    double origin;         // x/d of the left edge of cell 0: the smallest setting of the call
+    int ncells;            // 0 when poisoned
+    unsigned poison;       // a non-finite setting, more than kMaxCells cells, or d not finite and positive
+};
+struct CellChunks {
+    int nchunks;
+    int64_t chunk;         // particles per chunk: whole groups of 4 per wave
+    int nchunks_bound;     // >= nchunks of every sweep of fewer draws (workspace sizing)
+};
+constexpr int kCellWaves = LorentzCells::kMaxCells / kWave;      // wavefronts of cells
+constexpr int kCellMaxChunks = 512;      // x 4 waves: two per SIMD of the chip when one wavefront of cells is in use
+constexpr int kCellPlanThreads = 1024;
+constexpr int kCellFoldGroups = 16;
+// FP64 issue slots per (cell, particle) the plan rule reckons with: 8 per order and 16 of set-up (v_rcp_f64 = 4);
+// tools/count_isa.py counts 234 in cell_moments_kernel's loop at 28 orders
+constexpr double kCellSlots = 8.0 * LorentzCells::kOrder + 16.0;
+constexpr double kDirectSlots = 7.3125;                           // sweep_kernel<Lorentz<1>, 8, unshifted> per evaluation
+constexpr int64_t kCellFullGridDraws = (int64_t)kCellMaxChunks * 64;     // draws from which every chunk exists
+
+static CellChunks plan_cell_chunks(int64_t nd) {
+    CellChunks c;
+    c.nchunks_bound = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(kCellMaxChunks, nd / 64)));
+    c.chunk = (nd + c.nchunks_bound - 1) / c.nchunks_bound;
+    c.chunk = (c.chunk + 15) / 16 * 16;
+    c.nchunks = static_cast<int>((nd + c.chunk - 1) / c.chunk);
+    return c;
+}
+// the plan, the folded coefficients and the chunk partials of any cell sweep of AT MOST nd draws
+static int64_t cell_ws_doubles(int64_t nd) {
+    return 4 + (int64_t)(plan_cell_chunks(nd).nchunks_bound + 1) * LorentzCells::kCoefs * LorentzCells::kMaxCells;
+}
+
+#ifndef OBE_PLUGIN_MODEL_HEADER
+__global__ __launch_bounds__(kCellPlanThreads) void cell_plan_kernel(SweepArgs a, CellPlan* __restrict__ plan) {
+    constexpr int NW = kCellPlanThreads / kWave;
+    __shared__ double slo[NW], shi[NW];
+    __shared__ int sbad[NW];
+    if (sweep_aborted(a.abort)) return;
+    double lo = INFINITY, hi = -INFINITY;
+    int bad = 0;
+    for (int64_t s0 = threadIdx.x; s0 < a.ns; s0 += 8 * kCellPlanThreads) {
+        double x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int64_t s = s0 + (int64_t)u * kCellPlanThreads;
+            x[u] = a.settings[s < a.ns ? s : s0];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            bad |= !(fabs(x[u]) <= kDblMax);
+            lo = fmin(lo, x[u]);
+            hi = fmax(hi, x[u]);
+        }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        lo = fmin(lo, __shfl_down(lo, o, kWave));
+        hi = fmax(hi, __shfl_down(hi, o, kWave));
+        bad |= __shfl_down(bad, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        slo[threadIdx.x / kWave] = lo;
+        shi[threadIdx.x / kWave] = hi;
+        sbad[threadIdx.x / kWave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int g = 1; g < NW; ++g) {
+        lo = fmin(lo, slo[g]);
+        hi = fmax(hi, shi[g]);
+        bad |= sbad[g];
+    }
+    const double d = a.m.consts[0];
+    const double origin = lo / d, top = hi / d;             // (x / d as Lorentz::prep_setting forms it: monotone in x)
+    const double n = floor((top - origin) * (1.0 / LorentzCells::kWidth)) + 1.0;
+    const bool ok = !bad && d > 0.0 && d <= kDblMax && fabs(origin) <= kDblMax && fabs(top) <= kDblMax
+                    && n <= (double)LorentzCells::kMaxCells;             // (a NaN fails every comparison)
+    plan->origin = origin;
+    plan->ncells = ok ? static_cast<int>(n) : 0;
+    plan->poison = ok ? 0u : 1u;
+}
+
+__global__ __launch_bounds__(kBlock) void cell_moments_kernel(SweepArgs a, const CellPlan* __restrict__ plan,
+                                                              double* __restrict__ part) {
+    using LC = LorentzCells;
+    constexpr int NPKW = packed_width<Lorentz<1>>(), G = 4;
+    static_assert(NPKW == 4, "packed one-peak particle: tau0, sw a, sw b', sw");
+    __shared__ double red[kSweepWaves][2][kWave];
+    // (the wavefront of cells is the SLOW index: a grid of up to 64 cells leaves the second half of the blocks without
+    // work, and workgroups are dealt round robin over the XCDs — interleaved, every other XCD would sit idle)
+    const int cw = blockIdx.x / a.nchunks, chunk_id = blockIdx.x % a.nchunks;
+    if (sweep_aborted(a.abort)) return;
+    const int ncells = __builtin_amdgcn_readfirstlane(plan->ncells);
+    if (cw * kWave >= ncells) return;                     // (poisoned: no cells at all)
+    const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+    const int cell = cw * kWave + lane;                   // (< kMaxCells; beyond ncells: computed, never stored)
+    const double tc = LC::centre(plan->origin, cell);
+
+    // this wave's quarter of the chunk
+    const int64_t c_begin = (int64_t)chunk_id * a.chunk;
+    const int64_t c_end = c_begin + a.chunk < a.nd ? c_begin + a.chunk : a.nd;
+    const int64_t per = ((c_end - c_begin + 4 * kSweepWaves - 1) / (4 * kSweepWaves)) * 4;
+    int64_t p_begin = c_begin + wid * per;
+    if (p_begin > c_end) p_begin = c_end;
+    const int64_t p_end = p_begin + per < c_end ? p_begin + per : c_end;
+    const int n = static_cast<int>(wave_uniform(p_end - p_begin));
+    const double* __restrict__ pk = a.packed + wave_uniform(p_begin * NPKW);   // uniform address: scalar loads
+
+    LC::Sums z;
+    z.clear();
+    auto load_group = [&](int i0, double (&g)[G][NPKW]) {
+#pragma unroll
+        for (int e = 0; e < G; ++e)
+#pragma unroll
+            for (int k = 0; k < NPKW; ++k) g[e][k] = pk[(i0 + e) * NPKW + k];
+    };
+    int i = 0;
+    if (n >= G) {
+        // the software pipeline of sweep_kernel: the next group's scalar loads are in flight while this one is expanded
+        double cur[G][NPKW];
+        load_group(0, cur);
+        asm("" : "+s"(cur[0][0]));
+        for (; i + G <= n; i += G) {
+            double nxt[G][NPKW];
+            load_group(i + 2 * G <= n ? i + G * a.one : i, nxt);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int e = 0; e < G; ++e) LC::add_particle(tc, cur[e], z);
+#pragma unroll
+            for (int e = 0; e < G; ++e)
+#pragma unroll
+                for (int k = 0; k < NPKW; ++k) cur[e][k] = nxt[e][k];
+        }
+    }
+    for (; i < n; ++i) {
+        double g[NPKW];
+#pragma unroll
+        for (int k = 0; k < NPKW; ++k) g[k] = pk[i * NPKW + k];
+        LC::add_particle(tc, g, z);
+    }
+
+    // (global stores only after the streaming loop, as in sweep_kernel)
+    // the four waves' coefficients, two at a time, added in wave order; wave j % 4 writes pair j
+    auto fold_pair = [&](int j, double v0, double v1, int co0, int co1) {
+        __syncthreads();
+        red[wid][0][lane] = v0;
+        red[wid][1][lane] = v1;
+        __syncthreads();
+        if (wid == (j & (kSweepWaves - 1)) && cell < ncells) {
+            double t0 = red[0][0][lane], t1 = red[0][1][lane];
+#pragma unroll
+            for (int g = 1; g < kSweepWaves; ++g) {
+                t0 += red[g][0][lane];
+                t1 += red[g][1][lane];
+            }
+            part[((int64_t)chunk_id * LC::kCoefs + co0) * LC::kMaxCells + cell] = t0;
+            part[((int64_t)chunk_id * LC::kCoefs + co1) * LC::kMaxCells + cell] = t1;
+        }
+    };
+#pragma unroll
+    for (int k = 0; k < LC::kOrder; ++k) fold_pair(k, z.R[k], z.h(k), k, LC::kOrder + k);
+    fold_pair(LC::kOrder, z.c1, z.c2, 2 * LC::kOrder, 2 * LC::kOrder + 1);
+}
+
+// coef[co][cell] = sum over the chunks of part[chunk][co][cell]: wavefront g sums the chunks g, g + 16, ... (8
+// loads in flight), the 16 sums are added in wavefront order
+__global__ __launch_bounds__(kCellFoldGroups * kWave) void cell_fold_kernel(const double* __restrict__ part, int nchunks,
+                                                                            const CellPlan* __restrict__ plan,
+                                                                            double* __restrict__ coef,
+                                                                            const unsigned* abort) {
+    using LC = LorentzCells;
+    constexpr int FG = kCellFoldGroups;
+    __shared__ double acc[FG][kWave];
+    const int cw = blockIdx.x / LC::kCoefs, co = blockIdx.x % LC::kCoefs;
+    if (sweep_aborted(abort)) return;
+    const int ncells = __builtin_amdgcn_readfirstlane(plan->ncells);
+    if (cw * kWave >= ncells) return;
+    const int lane = threadIdx.x & (kWave - 1), grp = threadIdx.x / kWave;
+    const int cell = cw * kWave + lane;
+    double sum = 0.0;
+    if (cell < ncells) {
+        for (int k0 = grp; k0 < nchunks; k0 += 8 * FG) {
+            double t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int k = k0 + u * FG;
+                t[u] = part[((int64_t)(k < nchunks ? k : k0) * LC::kCoefs + co) * LC::kMaxCells + cell];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const double n = sum + t[u];
+                sum = k0 + u * FG < nchunks ? n : sum;
+            }
+        }
+    }
+    acc[grp][lane] = sum;
+    __syncthreads();
+    if (grp == 0 && cell < ncells) {
+        double t = acc[0][lane];
+#pragma unroll
+        for (int g = 1; g < FG; ++g) t += acc[g][lane];
+        coef[(int64_t)co * LC::kMaxCells + cell] = t;
+    }
+}
+
+// `ran` (next to the plan in the workspace) receives `seq`: how obe_sweep_timing tells a speculative cell sweep that
+// ran from one whose three launches returned at once (their durations are too close to tell by the clock)
+__global__ __launch_bounds__(kBlock) void cell_eval_kernel(SweepArgs a, const CellPlan* __restrict__ plan,
+                                                           const double* __restrict__ coef, unsigned* __restrict__ ran,
+                                                           unsigned seq) {
+    using LC = LorentzCells;
+    if (sweep_aborted(a.abort)) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *ran = seq;
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= a.ns) return;
+    double S1 = __builtin_nan(""), S2 = __builtin_nan("");        // poisoned: kappa = NaN, the caller repeats directly
+    const int ncells = plan->ncells;
+    if (ncells > 0) {
+        double tau;
+        Lorentz<1>::prep_setting(a.settings + s, a.m, &tau);
+        const double origin = plan->origin;
+        int c = static_cast<int>((tau - origin) * (1.0 / LC::kWidth));
+        c = c < 0 ? 0 : (c >= ncells ? ncells - 1 : c);
+        LC::evaluate(coef + c, LC::kMaxCells, tau - LC::centre(origin, c), S1, S2);
+    }
+    a.part1[s] = S1;
+    a.part2[s] = S2;
+    a.cs_out[s] = 0.0;
+}
+#endif  // !OBE_PLUGIN_MODEL_HEADER
 
 struct UtilArgs {
     const double* noise_var;
@@ -811,6 +1054,8 @@ struct SweepTiming {
     int64_t launches = 0;
     bool pending = false;      // a speculative call's events have not been read yet
     double pending_min_ms = 0.0;
+    const unsigned* pending_ran = nullptr;     // a speculative CELL sweep: the marker its last kernel writes if it runs ...
+    unsigned pending_seq = 0, seq = 0;         // ... and the value to find there
 };
 static SweepTiming g_timing;
 
@@ -830,7 +1075,14 @@ static void count_timed_sweep(double min_ms = 0.0) {
 static void resolve_pending_timing() {
     if (!g_timing.pending) return;
     g_timing.pending = false;
-    if (hipEventSynchronize(g_timing.e1) == hipSuccess) count_timed_sweep(g_timing.pending_min_ms);
+    if (hipEventSynchronize(g_timing.e1) != hipSuccess) return;
+    if (g_timing.pending_ran) {        // (the cell form: three launches that return at once are not told apart by the clock)
+        unsigned ran = 0;
+        const bool read = hipMemcpy(&ran, g_timing.pending_ran, sizeof ran, hipMemcpyDeviceToHost) == hipSuccess;
+        if (read && ran == g_timing.pending_seq) count_timed_sweep();
+        return;
+    }
+    count_timed_sweep(g_timing.pending_min_ms);
 }
 
 struct SweepWs {
@@ -845,6 +1097,15 @@ struct SweepWs {
     double* packed;
 };
 
+// what a cell sweep (OBE_SWEEP_CELLS) keeps behind the packed draws, with the slack that aligns it; a library built
+// for one generated model has no cell form
+static int64_t cell_form_doubles(int64_t nd) {
+#ifdef OBE_PLUGIN_MODEL_HEADER
+    return 0;
+#else
+    return cell_ws_doubles(nd) + 2;
+#endif
+}
 static int64_t sweep_ws_bytes(int64_t part_doubles, int64_t cs_doubles, int64_t slots, int64_t packed_doubles) {
     return (2 * part_doubles + cs_doubles + 3 * slots + 16 + packed_doubles + 2) * (int64_t)sizeof(double);
 }
@@ -853,7 +1114,8 @@ static int64_t sweep_ws_bytes_bound(int64_t ns, int64_t nd, int nc, int packed_w
     const SweepPlan p = plan_sweep(ns, nd, 1 << 20);       // (the grid of the costliest model: the most chunks)
     // (sized by the monotone bound: the chunk count itself is not monotone in nd after the rounding
     // of the chunk length, and a sweep of N_DRAWS < n_particles draws runs in the same workspace)
-    return sweep_ws_bytes((int64_t)p.nchunks_bound * nc * ns, (int64_t)nc * ns, argmax_slots(ns), nd * packed_w);
+    return sweep_ws_bytes((int64_t)p.nchunks_bound * nc * ns, (int64_t)nc * ns, argmax_slots(ns),
+                          nd * packed_w + cell_form_doubles(nd));
 }
 static int carve_sweep_ws(void* d_ws, int64_t ws_bytes, int64_t part_doubles, int64_t cs_doubles, SweepWs& w,
                           int64_t slots = kMaxBlocks, int64_t packed_doubles = 0) {
@@ -960,10 +1222,62 @@ static int launch_sweep(const SweepPlan& p, SweepArgs& a, int flags, hipStream_t
     return 0;
 }
 
+// the cell form of one call: whether it is taken, and where its pieces live in the workspace
+struct CellSweep {
+    bool on = false;
+    CellPlan* plan = nullptr;
+    double* coef = nullptr;
+    double* part = nullptr;
+    unsigned* ran = nullptr;       // cell_eval_kernel's marker
+    unsigned seq = 0;              // ... and what this call's launch writes there
+    CellChunks chunks{};
+};
+
+// OBE_SWEEP_CELLS is honoured where today's unshifted, non-SAFE sweep_kernel<Lorentz<1>> would run
+static bool cell_form_selected(const obe_model& m, int flags, int64_t ns, const int64_t* d_draw_idx, int64_t n_draws) {
+#ifdef OBE_PLUGIN_MODEL_HEADER
+    return false;
+#else
+    return (flags & OBE_SWEEP_CELLS) && !(flags & (OBE_SWEEP_SHIFTED | OBE_SWEEP_SAFE)) && m.id == OBE_MODEL_LORENTZ
+           && m.aux == 1 && !(d_draw_idx && one_workgroup_sweep(ns, n_draws));
+#endif
+}
+
+#ifndef OBE_PLUGIN_MODEL_HEADER
+// once per call, with the pack: the cells of this call's settings
+static int launch_cell_plan(const SweepArgs& a, const CellSweep& c, hipStream_t st) {
+    cell_plan_kernel<<<1, kCellPlanThreads, 0, st>>>(a, c.plan);
+    OBE_CHECK_LAUNCH("cell_plan_kernel");
+    return 0;
+}
+// in place of launch_sweep: one chunk of moments in part1 / part2, cs_out = 0
+static int launch_cell_sweep(SweepPlan& p, SweepArgs& a, const CellSweep& c, hipStream_t st) {
+    using LC = LorentzCells;
+    p.nchunks = 1;
+    a.tiles_x = p.tiles_x;
+    a.one = 1;
+    a.xcd_map = 0;
+    a.chunk = c.chunks.chunk;
+    a.nchunks = c.chunks.nchunks;          // (of the expansion; sweep_finalize is told p.nchunks = 1)
+    cell_moments_kernel<<<(unsigned)c.chunks.nchunks * kCellWaves, kBlock, 0, st>>>(a, c.plan, c.part);
+    OBE_CHECK_LAUNCH("cell_moments_kernel");
+    cell_fold_kernel<<<LC::kCoefs * kCellWaves, kCellFoldGroups * kWave, 0, st>>>(c.part, c.chunks.nchunks, c.plan, c.coef,
+                                                                                 a.abort);
+    OBE_CHECK_LAUNCH("cell_fold_kernel");
+    cell_eval_kernel<<<(unsigned)((a.ns + kBlock - 1) / kBlock), kBlock, 0, st>>>(a, c.plan, c.coef, c.ran, c.seq);
+    OBE_CHECK_LAUNCH("cell_eval_kernel");
+    return 0;
+}
+#else
+static int launch_cell_plan(const SweepArgs&, const CellSweep&, hipStream_t) { return 0; }
+static int launch_cell_sweep(SweepPlan&, SweepArgs&, const CellSweep&, hipStream_t) { return 0; }
+#endif
+
 static int prepare_sweep(const obe_model* m, obe_model& mm, const double* d_settings, int64_t ld_s, int64_t ns,
                          const double* d_particles, int64_t ld_p, int64_t np, const double* d_weights,
                          const int64_t* d_draw_idx, int64_t n_draws, const double* d_moments, void* d_ws,
-                         int64_t ws_bytes, SweepPlan& plan, SweepArgs& a, SweepWs& w, int64_t* ws_need = nullptr) {
+                         int64_t ws_bytes, SweepPlan& plan, SweepArgs& a, SweepWs& w, int64_t* ws_need = nullptr,
+                         int flags = 0, CellSweep* cells = nullptr) {
     if (!m || !d_settings || !d_particles || !d_moments || ns <= 0 || np <= 0) return bad_arg("sweep: bad pointer/size");
     if (!d_draw_idx && !d_weights) return bad_arg("sweep: full mode needs weights");
     mm = *m;
@@ -979,9 +1293,23 @@ static int prepare_sweep(const obe_model* m, obe_model& mm, const double* d_sett
         return rc;
     plan = plan_sweep(ns, nd, cost, mm.n_channels > 4 ? 2 : 8);
     const int64_t part = (int64_t)plan.nchunks * mm.n_channels * ns;
-    if (int rc = carve_sweep_ws(d_ws, ws_bytes, part, (int64_t)mm.n_channels * ns, w, argmax_slots(ns), nd * packed_w))
+    const bool cell_form = cells && cell_form_selected(mm, flags, ns, d_draw_idx, n_draws);
+    const int64_t behind_parts = nd * packed_w + (cell_form ? cell_form_doubles(nd) : 0);
+    if (int rc = carve_sweep_ws(d_ws, ws_bytes, part, (int64_t)mm.n_channels * ns, w, argmax_slots(ns), behind_parts))
         return rc;
-    if (ws_need) *ws_need = sweep_ws_bytes(part, (int64_t)mm.n_channels * ns, argmax_slots(ns), nd * packed_w);
+    if (ws_need) *ws_need = sweep_ws_bytes(part, (int64_t)mm.n_channels * ns, argmax_slots(ns), behind_parts);
+    if (cells) {
+        cells->on = cell_form;
+        if (cell_form) {        // (16-byte aligned behind the packed draws: plan, folded coefficients, chunk partials)
+            double* base = w.packed + nd * packed_w;
+            base = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(base) + 15) & ~uintptr_t(15));
+            cells->plan = reinterpret_cast<CellPlan*>(base);
+            cells->ran = reinterpret_cast<unsigned*>(base + 3);
+            cells->coef = base + 4;
+            cells->part = cells->coef + (int64_t)LorentzCells::kCoefs * LorentzCells::kMaxCells;
+            cells->chunks = plan_cell_chunks(nd);
+        }
+    }
     a.cs_out = w.cs;
     a.packed = w.packed;
     a.m = mm;
@@ -1010,6 +1338,22 @@ extern "C" {
 
 int obe_sweep_settings_per_lane(int64_t n_settings) {
     return plan_sweep(n_settings < 1 ? 1 : n_settings, (int64_t)1 << 40).spt;      // the most any draw count gets
+}
+
+int obe_sweep_cells_plan(double x_min, double x_max, double d, int64_t n_settings, int64_t n_draws) {
+    using LC = LorentzCells;
+    if (!(d > 0.0 && d <= kDblMax) || !(x_min <= x_max) || !(fabs(x_min) <= kDblMax && fabs(x_max) <= kDblMax)
+        || n_settings < 1 || n_draws < 1)
+        return 0;
+    const double lo = x_min / d, hi = x_max / d;
+    if (!(fabs(lo) <= kDblMax && fabs(hi) <= kDblMax)) return 0;
+    const double ncells = std::floor((hi - lo) * (1.0 / LC::kWidth)) + 1.0;       // as cell_plan_kernel counts them
+    if (!(ncells <= (double)LC::kMaxCells)) return 0;
+    // issue slots per particle: every lane of the cells' wavefronts expands it, against one evaluation per setting;
+    // and draws enough for the whole chunk grid, without which the expansion kernel does not fill the chip
+    const double cell_slots = std::ceil(ncells / kWave) * kWave * kCellSlots;
+    const bool worthwhile = (double)n_settings * kDirectSlots >= OBE_CELL_MIN_GAIN * cell_slots && n_draws >= kCellFullGridDraws;
+    return worthwhile ? 3 : 1;
 }
 
 int obe_sweep_settings_per_lane_for(int64_t n_settings, int64_t n_draws) {
@@ -1050,8 +1394,9 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     SweepArgs a{};
     SweepWs w;
     int64_t sweep_ws_need = 0;
+    CellSweep cells;
     if (int rc = prepare_sweep(m, mm, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles, d_weights,
-                               d_draw_idx, n_draws, d_moments, d_ws, ws_bytes, plan, a, w, &sweep_ws_need))
+                               d_draw_idx, n_draws, d_moments, d_ws, ws_bytes, plan, a, w, &sweep_ws_need, shifted, &cells))
         return rc;
     hipStream_t st = as_stream(stream);
     UtilArgs ua;
@@ -1105,8 +1450,12 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     }
     int rc = dispatch_model(mm, [&](auto M) -> int {
         if (int e = launch_pack<decltype(M)>(a, st)) return e;
+        if (cells.on) {
+            if (timed && nowait) cells.seq = ++g_timing.seq ? g_timing.seq : ++g_timing.seq;      // (never 0)
+            if (int e = launch_cell_plan(a, cells, st)) return e;
+        }
         if (timed) (void)hipEventRecord(g_timing.e0, st);
-        const int e = launch_sweep<decltype(M)>(plan, a, shifted, st);
+        const int e = cells.on ? launch_cell_sweep(plan, a, cells, st) : launch_sweep<decltype(M)>(plan, a, shifted, st);
         if (timed) (void)hipEventRecord(g_timing.e1, st);
         return e;
     });
@@ -1134,6 +1483,8 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
         if (timed) {
             g_timing.pending = true;
             g_timing.pending_min_ms = 0.5 * (double)n_settings * (double)n_particles / 8e9;
+            g_timing.pending_ran = cells.on ? cells.ran : nullptr;
+            g_timing.pending_seq = cells.seq;
         }
         return 0;
     }
@@ -1164,17 +1515,20 @@ int obe_sweep_kernel_time(const obe_model* m, const double* d_settings, int64_t 
     SweepPlan plan;
     SweepArgs a{};
     SweepWs w;
+    CellSweep cells;
     if (int rc = prepare_sweep(m, mm, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles, d_weights,
-                               nullptr, 0, d_moments, d_ws, ws_bytes, plan, a, w))
+                               nullptr, 0, d_moments, d_ws, ws_bytes, plan, a, w, nullptr, shifted, &cells))
         return rc;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0, e1;
     OBE_HIP_TRY(hipEventCreate(&e0));
     OBE_HIP_TRY(hipEventCreate(&e1));
     auto sweep_once = [&]() -> int {
+        if (cells.on) return launch_cell_sweep(plan, a, cells, st);
         return dispatch_model(mm, [&](auto M) -> int { return launch_sweep<decltype(M)>(plan, a, shifted, st); });
     };
     int rc = dispatch_model(mm, [&](auto M) -> int { return launch_pack<decltype(M)>(a, st); });
+    if (!rc && cells.on) rc = launch_cell_plan(a, cells, st);
     if (rc) {
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);

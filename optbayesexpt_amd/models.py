@@ -65,6 +65,8 @@ class DeviceModel:
         self.n_channels = n_channels
         self.n_consts = n_consts
         self._numpy_form = numpy_form
+        #: the model's unshifted sweep has a cell-expansion form (include/obe_hip.h: OBE_SWEEP_CELLS)
+        self.cell_sweep = False
         self.__name__ = name
         #: how to build this model again (see ``spec()``): set by the factories of this module
         self._recipe = None
@@ -145,9 +147,10 @@ def lorentzian(n_peaks=1):
     # the fast sweep forms (3 and more peaks: the peaks of an evaluation combined into one fraction, range-checked;
     # 1 or 2 peaks: two particles per reciprocal, poisoned by overflow) have an always-IEEE twin for the repeat:
     # the pair form with a per-batch branch to element-by-element reciprocals (csrc/obe_models.h, Lorentz<K>)
-    return _made(DeviceModel(f"lorentzian[{n_peaks}]", MODEL_LORENTZ, n_peaks, n_peaks + 2, 1, 1, 1, form,
-                             safe_sweep=True, range_hint=in_range, safe_sweep_min_spt=2 if n_peaks < 3 else 1),
-                 "lorentzian", n_peaks)
+    model = DeviceModel(f"lorentzian[{n_peaks}]", MODEL_LORENTZ, n_peaks, n_peaks + 2, 1, 1, 1, form,
+                        safe_sweep=True, range_hint=in_range, safe_sweep_min_spt=2 if n_peaks < 3 else 1)
+    model.cell_sweep = n_peaks == 1
+    return _made(model, "lorentzian", n_peaks)
 
 
 def line_ab():

@@ -148,7 +148,8 @@ class OptBayesExpt(ParticlePDF):
     ``tuning_parameters['speculative_sweep']`` (``'auto'``, ``True``, ``False``; ``variance_full`` only)
         ``pdf_update()`` enqueues the sweep of the next ``opt_setting()`` behind its update (see
         ``_speculation_wanted``): the same results, one host round trip per cycle less.
-    ``tuning_parameters['sweep_shift']`` (``'auto'``, ``'always'``, ``'never'``), ``['fused_moments']``,
+    ``tuning_parameters['sweep_shift']`` (``'auto'``, ``'always'``, ``'never'``), ``['sweep_cells']`` (``'auto'``,
+    ``'always'``, ``'never'``: the one-peak Lorentzian's unshifted sweep by cell expansions), ``['fused_moments']``,
     ``['replica_check_every']``
         see ``_sweep_device``, ``pdf_update``, ``check_replicas``.
     """
@@ -808,6 +809,7 @@ class OptBayesExpt(ParticlePDF):
         """Everything the result of a full sweep of this object depends on besides the kernels: compared
         between the sweep enqueued ahead and the one being asked for (both must read the same)."""
         return dict(cloud=(self._particles.version, self._weights.version), shifted=bool(shifted),
+                    cells=bool(not shifted and self._cell_form_wanted()),
                     noise=self._noise_token(), settings=(self._s_begin, self._s_end),
                     alias=self._parameters is self._particles,
                     cost_hook=_overridden(self, "cost_estimate", OptBayesExpt))
@@ -1084,7 +1086,12 @@ class OptBayesExpt(ParticlePDF):
         # which the update calls between a sweep enqueued ahead and its collection do not touch)
         tail = self._ws[-6:-2] if sharded else None
 
+        def cells_for(shifted, safe=False):
+            # the cell form stands in for the unshifted direct kernel only: every repeat (shifted, safe) is direct
+            return full and not shifted and not safe and self._cell_form_wanted()
+
         def launch(shifted, safe=False, speculative=False):
+            result["cells"] = cells_for(shifted, safe)
             # sharded: no host read here — the 32-byte result record is all-gathered from
             # device memory and read back once, together with the other ranks' records
             p, w = self._pw_tensors()
@@ -1099,6 +1106,7 @@ class OptBayesExpt(ParticlePDF):
                            _ptr(p), p.shape[1], self.n_particles, _ptr(w),
                            None if idx is None else _ptr(idx), n_draws, _ptr(mom),
                            (_lib.OBE_SWEEP_SHIFTED if shifted else 0) | (_lib.OBE_SWEEP_SAFE if safe else 0)
+                           | (_lib.OBE_SWEEP_CELLS if cells_for(shifted, safe) else 0)
                            | (0 if not speculative else _lib.OBE_SWEEP_NOWAIT if speculative == "after_resample"
                               else _lib.OBE_SWEEP_SPECULATIVE),
                            _ptr(noise), noise_ld, None if cost_t is None else _ptr(cost_t), cost_s,
@@ -1144,13 +1152,14 @@ class OptBayesExpt(ParticlePDF):
         form = state.form_for_next_sweep()
         if lazy:
             launch(True)
-            self.last_sweep = dict(shifted=True, kappa=float("nan"), safe=False)     # kappa was not read back
+            self.last_sweep = dict(shifted=True, kappa=float("nan"), safe=False, cells=False)     # kappa was not read back
             return None
         if form is Form.FAST:
             taken = self._take_speculative_sweep(shifted) if full else None
             if taken is None:
                 launch(shifted)
             else:
+                result["cells"] = cells_for(shifted)       # (part of the ticket's inputs: what was enqueued ahead)
                 deliver(taken if sharded else None)
             self._check_pending_total()
             poisoned = checked and bool(np.isnan(kappa[0]))
@@ -1175,10 +1184,29 @@ class OptBayesExpt(ParticlePDF):
             safe = shifted = True
             launch(True, safe=True)
             self._check_pending_total()
-        self.last_sweep = dict(shifted=shifted, kappa=float(kappa[0]), safe=safe)
+        self.last_sweep = dict(shifted=shifted, kappa=float(kappa[0]), safe=safe, cells=bool(result["cells"]))
         if want_best:
             return result["best"]
         return None
+
+    def _cell_form_wanted(self):
+        """Whether an unshifted full sweep of this object's settings slice runs as cell expansions
+        (include/obe_hip.h: OBE_SWEEP_CELLS; one-peak Lorentzian only).  ``tuning_parameters['sweep_cells']``:
+        ``'auto'`` (default) — where obe_sweep_cells_plan() finds the grid within the cap AND the form worthwhile;
+        ``'always'`` — wherever it is valid; ``'never'``.  The helper is asked once per settings grid."""
+        mode = self.tuning_parameters.get("sweep_cells", "auto")
+        dm = self._device_model
+        if mode == "never" or dm is None or not dm.cell_sweep or self._s_end <= self._s_begin:
+            return False
+        key = (self._s_begin, self._s_end, self.n_particles)
+        plan = self.__dict__.get("_cells_plan")
+        if plan is None or plan[0] != key:
+            x = self.allsettings[0, self._s_begin:self._s_end]
+            with np.errstate(all="ignore"):
+                lo, hi = float(np.min(x)), float(np.max(x))
+            plan = self._cells_plan = (key, int(self._mlib.cdll.obe_sweep_cells_plan(
+                lo, hi, float(self.cons[0]), self._s_end - self._s_begin, self.n_particles)))
+        return bool(plan[1] & 1) and (mode == "always" or bool(plan[1] & 2))
 
     def _settings_per_lane(self, n_draws=0):
         """Settings one lane of the sweep kernel owns on a slice of this job: at most (n_draws = 0, what a full
