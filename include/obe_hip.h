@@ -462,7 +462,7 @@ OBE_API int obe_power_normalize(const double* d_u, int64_t n, double exponent, d
  * d_moments: output of obe_moments for the same particles/weights (mean parameters are
  * used as the variance shift, sum w as the normaliser).
  * `shifted` is a bit set: OBE_SWEEP_SHIFTED (1), for expression (plugin) models
- * OBE_SWEEP_SAFE (2), and for the one-peak Lorentzian OBE_SWEEP_CELLS (4).
+ * OBE_SWEEP_SAFE (2), and for the one-peak Lorentzian OBE_SWEEP_CELLS (4) and OBE_SWEEP_BINS (32).
  * OBE_SWEEP_SHIFTED set: moments are accumulated about a per-setting shift (always accurate).
  * OBE_SWEEP_SHIFTED clear: one instruction fewer per evaluation, accurate only while the predicted
  * mean does not dominate the spread; *h_kappa (nullable) returns the worst
@@ -542,6 +542,22 @@ OBE_API int obe_power_normalize(const double* d_u, int64_t n, double exponent, d
  * direct evaluations per particle cost at least OBE_CELL_MIN_GAIN times the issue slots of the cells' expansions,
  * and the sweep's n_draws draws (the particles, for a full sweep) are enough to fill the expansion kernel's grid. */
 OBE_API int obe_sweep_cells_plan(double x_min, double x_max, double d, int64_t n_settings, int64_t n_draws);
+/* OBE_SWEEP_BINS: the same sweep with the PARTICLES summarised instead of the settings (csrc/obe_models.h:
+ * LorentzBins) — the packed positions x0/d are cut into bins of half-width 1 / OBE_CELL_RHO_INV, the draws are
+ * grouped by bin (the order of a stable sort, so every sum has a fixed order: the same bits from call to call), each
+ * bin keeps 3 OBE_CELL_ORDER moments of its draws about its centre, and a setting meets the occupied bins instead of
+ * the draws.  Honoured where OBE_SWEEP_CELLS would be (it goes before that bit where both are set) for up to 2^30
+ * draws; the same moments to rounding.  A call whose x0/d span more than OBE_BIN_MAX bins (zero-weight draws
+ * included), hold a non-finite value, or whose d is not finite and positive returns *h_kappa = NaN and NaN
+ * variances: the caller repeats it without the bit.  The span depends on the particles alone, so a caller need not
+ * ask again before the cloud changes. */
+#define OBE_SWEEP_BINS 32
+#define OBE_BIN_MAX 128
+/* Host only, nothing is launched: bit 0 — the inputs are finite and d > 0 (whether the cloud fits OBE_BIN_MAX bins
+ * only the call itself finds out); bit 1 — the form is also worthwhile: priced at OBE_BIN_MAX occupied bins plus the
+ * pass over the draws plus the fixed cost of its launches, the form it would replace (the cells where
+ * obe_sweep_cells_plan() takes them, otherwise the direct kernel) costs at least OBE_CELL_MIN_GAIN times as much. */
+OBE_API int obe_sweep_bins_plan(double x_min, double x_max, double d, int64_t n_settings, int64_t n_draws);
 /* Settings one lane of the sweep kernel owns at most for a grid of n_settings (1, 2, 4 or 8; a sweep of
  * few draws may use fewer): the number of denominators a model's fast form inverts together, which a
  * caller that predicts whether a settings grid stays inside that form's range needs

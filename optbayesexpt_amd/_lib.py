@@ -39,6 +39,8 @@ OBE_SWEEP_CELLS = _H["OBE_SWEEP_CELLS"]
 # the cell form: half-width 1 / OBE_CELL_RHO_INV, OBE_CELL_ORDER coefficients per moment, at most OBE_CELL_MAX cells
 OBE_CELL_RHO_INV, OBE_CELL_ORDER, OBE_CELL_MAX = _H["OBE_CELL_RHO_INV"], _H["OBE_CELL_ORDER"], _H["OBE_CELL_MAX"]
 OBE_CELL_MIN_GAIN = _H["OBE_CELL_MIN_GAIN"]
+# the bin form: the same half-width and order on the particles' axis, at most OBE_BIN_MAX bins
+OBE_SWEEP_BINS, OBE_BIN_MAX = _H["OBE_SWEEP_BINS"], _H["OBE_BIN_MAX"]
 HOST_SENTINEL = 0x7ff8c0dec0dec0de     # the value of an armed host result word (csrc/obe_common.h: kHostSentinel)
 
 c_void_p, c_int, c_int32, c_int64, c_double = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int32,

@@ -527,7 +527,28 @@ struct Lorentz {
 // H_k = Q_k + (k + 1) G_k once per chunk.  8 FP64 issue slots per order instead of 9.
 // Truncation: the neglected tail of r^2 is below (P + 1) rho^P / (1 - rho)  (P = kOrder terms); rho = 1/4, P = 28
 // gives 29 * 2^-56 * 4/3 = 5e-16 ("Cell expansions").
-struct LorentzCells {
+// the two series in one place: how they start at a distance s and the step from order k to k + 1 (the cell form
+// expands about a cell's centre, s = tau_c - tau0; the bin form about a bin's centre, s = tau_b - tau: the kernel
+// depends on tau - tau0 alone, so the recurrences are the same)
+struct LorentzSeries {
+    static constexpr double m_of(int k) { return (double)k * (k + 3) / ((double)(k + 1) * (k + 2)); }
+    __device__ __forceinline__ static void start(double s, double& r0, double& A, double& B) {
+        r0 = exact_rcp(fma(s, s, 1.0));       // q0 >= 1
+        B = -r0;
+        A = (s + s) * B;
+    }
+    // r = r_k, g = g_k, Brp = B r_{k-1}, Bgp = B g_{k-1}  ->  the same of k + 1
+    __device__ __forceinline__ static void step(int k, double A, double B, double& r, double& g, double& Brp,
+                                                double& Bgp) {
+        const double rn = fma(A, r, Brp), gn = fma(A, g, m_of(k) * Bgp);
+        Brp = B * r;
+        Bgp = B * g;
+        r = rn;
+        g = gn;
+    }
+};
+
+struct LorentzCells : LorentzSeries {
     static constexpr int kOrder = OBE_CELL_ORDER;
     static constexpr int kMaxCells = OBE_CELL_MAX;
     static constexpr double kWidth = 2.0 / OBE_CELL_RHO_INV;         // of a cell: 2 rho
@@ -538,7 +559,6 @@ struct LorentzCells {
     __device__ __forceinline__ static double centre(double origin, int c) {
         return fma((double)c + 0.5, kWidth, origin);
     }
-    static constexpr double m_of(int k) { return (double)k * (k + 3) / ((double)(k + 1) * (k + 2)); }
 
     // running sums of one cell (one lane): three per order, and C1, C2
     struct Sums {
@@ -552,9 +572,8 @@ struct LorentzCells {
     };
     // one packed particle (tau0, sw a, sw b', sw: Lorentz<1>::pack) into the sums of the cell centred at tc
     __device__ __forceinline__ static void add_particle(double tc, const double* pk, Sums& z) {
-        const double s = tc - pk[0];
-        const double r0 = exact_rcp(fma(s, s, 1.0));       // q0 >= 1
-        const double B = -r0, A = (s + s) * B;
+        double r0, A, B;
+        start(tc - pk[0], r0, A, B);
         const double wa = pk[1] * pk[3], waa = pk[1] * pk[1], wab2 = (pk[1] + pk[1]) * pk[2];
         z.c1 = fma(pk[2], pk[3], z.c1);
         z.c2 = fma(pk[2], pk[2], z.c2);
@@ -564,13 +583,7 @@ struct LorentzCells {
             z.R[k] = fma(wa, r, z.R[k]);
             z.Q[k] = fma(wab2, r, z.Q[k]);
             z.G[k] = fma(waa, g, z.G[k]);
-            if (k + 1 < kOrder) {
-                const double rn = fma(A, r, Brp), gn = fma(A, g, m_of(k) * Bgp);
-                Brp = B * r;
-                Bgp = B * g;
-                r = rn;
-                g = gn;
-            }
+            if (k + 1 < kOrder) step(k, A, B, r, g, Brp, Bgp);
         }
     }
     // a setting's two moments from its cell's coefficients coef[j * stride], j = 0 .. kCoefs-1 (R_k at k, H_k at
@@ -588,6 +601,78 @@ struct LorentzCells {
         }
         S1 = p1 + c[2 * kOrder];
         S2 = p2 + c[2 * kOrder + 1];
+    }
+};
+
+// ---- ... and by bin expansions (OBE_SWEEP_BINS): the same series with the roles exchanged ----
+// r depends on tau - tau0 alone, so the particles can be summarised instead of the settings: the tau0 axis is cut
+// into bins of half-width rho, and with eps = tau0 - tau_b (|eps| <= rho) and s = tau_b - tau
+//   r = 1 / ((s + eps)^2 + 1) = sum_k r_k(s) eps^k,   r^2 = sum_k (k + 1) g_k(s) eps^k
+// (r is even, so the sign of tau - tau0 does not matter).  Per bin, once per sweep,
+//   M1_k = sum (w a) eps^k,   M2_k = sum (2 w a b') eps^k,   H3_k = (k + 1) sum (w a^2) eps^k,
+// and per setting  S1 = C1 + sum_bins sum_k M1_k r_k(s),  S2 = C2 + sum_bins sum_k [M2_k r_k(s) + H3_k g_k(s)].
+// The ratio, the order and the truncation bound are those of the cells; |r_k| <= 1, |g_k| <= 1.
+struct LorentzBins : LorentzSeries {
+    static constexpr int kOrder = OBE_CELL_ORDER;
+    static constexpr int kMaxBins = OBE_BIN_MAX;
+    static constexpr double kWidth = 2.0 / OBE_CELL_RHO_INV;         // of a bin: 2 rho
+    static constexpr int kCoefs = 3 * kOrder + 2;                    // M1_k, M2_k, H3_k, C1, C2 of one bin
+    static constexpr int kRow = (kCoefs + 1) & ~1;                   // doubles between two bins' (or items') rows
+
+    // centre of bin b of a plan that starts at `origin` (the same expression wherever a centre is needed)
+    __device__ __forceinline__ static double centre(double origin, int b) {
+        return fma((double)b + 0.5, kWidth, origin);
+    }
+    // the bin of a packed tau0 (finite, >= origin) in a plan of nbins bins
+    __device__ __forceinline__ static int bin_of(double origin, double tau0, int nbins) {
+        const int b = static_cast<int>((tau0 - origin) * (1.0 / kWidth));
+        return b < 0 ? 0 : (b >= nbins ? nbins - 1 : b);
+    }
+    // running sums of one lane's draws of one bin
+    struct Sums {
+        double M1[kOrder], M2[kOrder], M3[kOrder], c1, c2;
+        __device__ __forceinline__ void clear() {
+#pragma unroll
+            for (int k = 0; k < kOrder; ++k) M1[k] = M2[k] = M3[k] = 0.0;
+            c1 = c2 = 0.0;
+        }
+    };
+    // one packed draw (tau0, sw a, sw b', sw: Lorentz<1>::pack) of the bin centred at tb
+    __device__ __forceinline__ static void add_draw(double tb, const double* pk, Sums& z) {
+        const double eps = pk[0] - tb;
+        const double wa = pk[1] * pk[3], waa = pk[1] * pk[1], wab2 = (pk[1] + pk[1]) * pk[2];
+        z.c1 = fma(pk[2], pk[3], z.c1);
+        z.c2 = fma(pk[2], pk[2], z.c2);
+        double e = 1.0;                                             // eps^k
+#pragma unroll
+        for (int k = 0; k < kOrder; ++k) {
+            z.M1[k] = fma(wa, e, z.M1[k]);
+            z.M2[k] = fma(wab2, e, z.M2[k]);
+            z.M3[k] = fma(waa, e, z.M3[k]);
+            if (k + 1 < kOrder) e *= eps;
+        }
+    }
+    // one bin's share of a setting's two moments from its folded row (M1_k at k, M2_k at kOrder + k, H3_k at
+    // 2 kOrder + k), s = tau_b - tau: each series summed from the highest order down
+    __device__ __forceinline__ static void evaluate(const double* __restrict__ row, double s, double& t1, double& t2) {
+        double r[kOrder], g[kOrder];
+        double A, B, Brp = 0.0, Bgp = 0.0;
+        start(s, r[0], A, B);
+        g[0] = r[0] * r[0];
+#pragma unroll
+        for (int k = 0; k + 1 < kOrder; ++k) {
+            r[k + 1] = r[k];
+            g[k + 1] = g[k];
+            step(k, A, B, r[k + 1], g[k + 1], Brp, Bgp);
+        }
+        t1 = 0.0;
+        t2 = 0.0;
+#pragma unroll
+        for (int k = kOrder - 1; k >= 0; --k) {
+            t1 = fma(row[k], r[k], t1);
+            t2 = fma(row[kOrder + k], r[k], t2);
+            t2 = fma(row[2 * kOrder + k], g[k], t2);
+        }
     }
 };
 

@@ -414,6 +414,54 @@ static int64_t cell_ws_doubles(int64_t nd) {
     return 4 + (int64_t)(plan_cell_chunks(nd).nchunks_bound + 1) * LorentzCells::kCoefs * LorentzCells::kMaxCells;
 }
 
+// ---- the bin form of the same sweep (OBE_SWEEP_BINS): its plan, its sizes and where its pieces live ----
+struct BinPlan {           // written by bin_plan_kernel
+    double origin;         // the smallest packed tau0: the left edge of bin 0
+    int nbins;             // 0 when poisoned
+    unsigned poison;       // a non-finite tau0, more than kMaxBins bins, or d not finite and positive
+};
+constexpr int kBinMinmaxBlocks = 256;
+constexpr int kBinMaxUnits = 2048;        // wavefronts of the grouping passes
+constexpr int kBinChunk = 1024;           // draws per item of bin_moments_kernel
+constexpr int kBinFoldGroups = 16;
+constexpr int kBinScanPer = kBinMaxUnits / kBlock;
+// FP64 issue slots the plan rule reckons with (tools/count_isa.py): per (setting, bin) in
+// bin_eval_kernel, per draw in bin_moments_kernel
+constexpr double kBinEvalSlots = 8.0 * LorentzBins::kOrder + 16.0;
+constexpr double kBinDrawSlots = 4.0 * LorentzBins::kOrder + 8.0;
+// the pipeline's eight launches on a cloud of 64 draws and 64 settings, in lane issue slots: 80 microseconds on one
+// MI355X, each sweep launched into a drained stream as a cycle does (obe_sweep_kernel_time: 78-80 us; 61 us back
+// to back; DESIGN.md, "K1 by bin expansions"), at the chip's 3.9e7 FP64 lane slots per microsecond (the cell form's
+// 1.57e10 lane-instructions in 0.52 ms at 0.77 of the issue rate)
+constexpr double kBinFixedSlots = 80.0 * 3.9e7;
+
+struct BinUnits {
+    int nunits;
+    int64_t per;           // draws per unit: whole wavefronts
+};
+static BinUnits plan_bin_units(int64_t nd) {
+    BinUnits u;
+    u.per = (nd + kBinMaxUnits - 1) / kBinMaxUnits;
+    u.per = std::max<int64_t>(kWave, (u.per + kWave - 1) / kWave * kWave);
+    u.nunits = static_cast<int>((nd + u.per - 1) / u.per);
+    return u;
+}
+static int64_t bin_max_items(int64_t nd) { return (nd + kBinChunk - 1) / kBinChunk + LorentzBins::kMaxBins; }
+// where the pieces live, in doubles from a 16-byte aligned base behind the packed draws
+struct BinLayout {
+    static constexpr int64_t kPlan = 0, kRan = 3, kStarts = 4;                           // plan; marker; 2 x 130 ints
+    static constexpr int64_t kMinmax = kStarts + 132;                                   // lo, hi, bad per workgroup
+    static constexpr int64_t kTotals = kMinmax + 3 * kBinMinmaxBlocks;                  // 128 ints
+    static constexpr int64_t kCounts = kTotals + LorentzBins::kMaxBins / 2;             // bins x units ints
+    static constexpr int64_t kCoef = kCounts + (int64_t)LorentzBins::kMaxBins * kBinMaxUnits / 2;
+    static constexpr int64_t kPart = kCoef + (int64_t)LorentzBins::kMaxBins * LorentzBins::kRow;
+    static int64_t sorted(int64_t nd) { return kPart + bin_max_items(nd) * LorentzBins::kRow; }
+    static int64_t doubles(int64_t nd) { return sorted(nd) + 4 * nd; }
+};
+static_assert(BinLayout::kPart % 2 == 0 && LorentzBins::kRow % 2 == 0, "the sorted records are 16-byte aligned");
+// the plan, the tables and the sorted records of any bin sweep of AT MOST nd draws
+static int64_t bin_ws_doubles(int64_t nd) { return BinLayout::doubles(nd); }
+
 #ifndef OBE_PLUGIN_MODEL_HEADER
 __global__ __launch_bounds__(kCellPlanThreads) void cell_plan_kernel(SweepArgs a, CellPlan* __restrict__ plan) {
     constexpr int NW = kCellPlanThreads / kWave;
@@ -546,45 +594,54 @@ __global__ __launch_bounds__(kBlock) void cell_moments_kernel(SweepArgs a, const
     fold_pair(LC::kOrder, z.c1, z.c2, 2 * LC::kOrder, 2 * LC::kOrder + 1);
 }
 
-// coef[co][cell] = sum over the chunks of part[chunk][co][cell]: wavefront g sums the chunks g, g + 16, ... (8
-// loads in flight), the 16 sums are added in wavefront order
-__global__ __launch_bounds__(kCellFoldGroups * kWave) void cell_fold_kernel(const double* __restrict__ part, int nchunks,
-                                                                            const CellPlan* __restrict__ plan,
-                                                                            double* __restrict__ coef,
-                                                                            const unsigned* abort) {
-    using LC = LorentzCells;
-    constexpr int FG = kCellFoldGroups;
-    __shared__ double acc[FG][kWave];
-    const int cw = blockIdx.x / LC::kCoefs, co = blockIdx.x % LC::kCoefs;
-    if (sweep_aborted(abort)) return;
-    const int ncells = __builtin_amdgcn_readfirstlane(plan->ncells);
-    if (cw * kWave >= ncells) return;
+// The sum of p[k * stride], k = 0 .. n - 1, for this lane (`live`: it has one): wavefront g of the FG sums the terms
+// g, g + FG, ... (8 loads in flight), the FG sums are added in wavefront order.  Wavefront 0 holds the result.
+template <int FG>
+__device__ __forceinline__ double fold_in_order(const double* __restrict__ p, int n, int64_t stride, bool live,
+                                                double (&acc)[FG][kWave]) {
     const int lane = threadIdx.x & (kWave - 1), grp = threadIdx.x / kWave;
-    const int cell = cw * kWave + lane;
     double sum = 0.0;
-    if (cell < ncells) {
-        for (int k0 = grp; k0 < nchunks; k0 += 8 * FG) {
+    if (live) {
+        for (int k0 = grp; k0 < n; k0 += 8 * FG) {
             double t[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int k = k0 + u * FG;
-                t[u] = part[((int64_t)(k < nchunks ? k : k0) * LC::kCoefs + co) * LC::kMaxCells + cell];
+                t[u] = p[(int64_t)(k < n ? k : k0) * stride];
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const double n = sum + t[u];
-                sum = k0 + u * FG < nchunks ? n : sum;
+                const double nx = sum + t[u];
+                sum = k0 + u * FG < n ? nx : sum;
             }
         }
     }
     acc[grp][lane] = sum;
     __syncthreads();
-    if (grp == 0 && cell < ncells) {
-        double t = acc[0][lane];
+    double t = acc[0][lane];
+    if (grp == 0) {
 #pragma unroll
         for (int g = 1; g < FG; ++g) t += acc[g][lane];
-        coef[(int64_t)co * LC::kMaxCells + cell] = t;
     }
+    return t;
+}
+
+// coef[co][cell] = sum over the chunks of part[chunk][co][cell]
+__global__ __launch_bounds__(kCellFoldGroups * kWave) void cell_fold_kernel(const double* __restrict__ part, int nchunks,
+                                                                            const CellPlan* __restrict__ plan,
+                                                                            double* __restrict__ coef,
+                                                                            const unsigned* abort) {
+    using LC = LorentzCells;
+    __shared__ double acc[kCellFoldGroups][kWave];
+    const int cw = blockIdx.x / LC::kCoefs, co = blockIdx.x % LC::kCoefs;
+    if (sweep_aborted(abort)) return;
+    const int ncells = __builtin_amdgcn_readfirstlane(plan->ncells);
+    if (cw * kWave >= ncells) return;
+    const int cell = cw * kWave + (threadIdx.x & (kWave - 1));
+    const bool live = cell < ncells;
+    const double t = fold_in_order<kCellFoldGroups>(part + (int64_t)co * LC::kMaxCells + cell, nchunks,
+                                                    (int64_t)LC::kCoefs * LC::kMaxCells, live, acc);
+    if (threadIdx.x < kWave && live) coef[(int64_t)co * LC::kMaxCells + cell] = t;
 }
 
 // `ran` (next to the plan in the workspace) receives `seq`: how obe_sweep_timing tells a speculative cell sweep that
@@ -607,6 +664,356 @@ __global__ __launch_bounds__(kBlock) void cell_eval_kernel(SweepArgs a, const Ce
         c = c < 0 ? 0 : (c >= ncells ? ncells - 1 : c);
         LC::evaluate(coef + c, LC::kMaxCells, tau - LC::centre(origin, c), S1, S2);
     }
+    a.part1[s] = S1;
+    a.part2[s] = S2;
+    a.cs_out[s] = 0.0;
+}
+// ---- the bin form of the same sweep (OBE_SWEEP_BINS; obe_models.h: LorentzBins) ----
+// The particles are summarised instead of the settings.  Behind sweep_pack_kernel:
+//   bin_minmax_kernel    min / max of the packed tau0 (zero-weight draws included), one partial per workgroup.
+//   bin_plan_kernel      -> origin, bin count, poison word.
+//   bin_group_kernel<0>  a wavefront owns a contiguous unit of draws and counts them by bin (integers, no atomics).
+//   bin_scan_kernel      exclusive scan of the counts over the units, bin by bin, and each bin's total.
+//   bin_group_kernel<1>  the same walk again: a draw goes to (start of its bin) + (draws of that bin in earlier
+//                        units) + (earlier draws of that bin in this unit) — the order of a stable sort by bin.
+//   bin_moments_kernel   lane <-> draw within one item (kBinChunk consecutive draws of ONE bin), 3 P + 2 running sums
+//                        per lane, a butterfly over the lanes once per item.
+//   bin_fold_kernel      a bin's items summed in a fixed order (fold_in_order).
+//   bin_eval_kernel      lane <-> setting, the bins' rows through LDS, bins in order; writes part1 / part2 as ONE
+//                        chunk and cs_out = 0, as cell_eval_kernel does.
+// No floating-point atomics; every sum has a fixed association, so two calls on the same inputs give the same bits.
+struct BinSweepPtrs {
+    BinPlan* plan;
+    unsigned* ran;
+    int* binstart;         // [kMaxBins + 1] first sorted draw of each bin
+    int* itemstart;        // [kMaxBins + 1] first item of each bin
+    double* minmax;
+    int* totals;
+    int* counts;           // [bin * kBinMaxUnits + unit]
+    double* coef;
+    double* part;
+    double* sorted;
+};
+
+__global__ __launch_bounds__(kBlock) void bin_minmax_kernel(SweepArgs a, double* __restrict__ minmax) {
+    constexpr int NW = kBlock / kWave;
+    __shared__ double slo[NW], shi[NW];
+    __shared__ int sbad[NW];
+    if (sweep_aborted(a.abort)) return;
+    double lo = INFINITY, hi = -INFINITY;
+    int bad = 0;
+    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < a.nd; p += (int64_t)gridDim.x * kBlock) {
+        const double t = a.packed[4 * p];
+        bad |= !(fabs(t) <= kDblMax);
+        lo = fmin(lo, t);
+        hi = fmax(hi, t);
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        lo = fmin(lo, __shfl_down(lo, o, kWave));
+        hi = fmax(hi, __shfl_down(hi, o, kWave));
+        bad |= __shfl_down(bad, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        slo[threadIdx.x / kWave] = lo;
+        shi[threadIdx.x / kWave] = hi;
+        sbad[threadIdx.x / kWave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int g = 1; g < NW; ++g) {
+        lo = fmin(lo, slo[g]);
+        hi = fmax(hi, shi[g]);
+        bad |= sbad[g];
+    }
+    minmax[blockIdx.x] = lo;
+    minmax[kBinMinmaxBlocks + blockIdx.x] = hi;
+    minmax[2 * kBinMinmaxBlocks + blockIdx.x] = bad ? 1.0 : 0.0;
+}
+
+__global__ __launch_bounds__(kBinMinmaxBlocks) void bin_plan_kernel(SweepArgs a, const double* __restrict__ minmax,
+                                                                     int nblocks, BinPlan* __restrict__ plan) {
+    constexpr int NW = kBinMinmaxBlocks / kWave;
+    __shared__ double slo[NW], shi[NW];
+    __shared__ int sbad[NW];
+    if (sweep_aborted(a.abort)) return;
+    const bool have = (int)threadIdx.x < nblocks;
+    double lo = have ? minmax[threadIdx.x] : INFINITY, hi = have ? minmax[kBinMinmaxBlocks + threadIdx.x] : -INFINITY;
+    int bad = have ? minmax[2 * kBinMinmaxBlocks + threadIdx.x] != 0.0 : 0;
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        lo = fmin(lo, __shfl_down(lo, o, kWave));
+        hi = fmax(hi, __shfl_down(hi, o, kWave));
+        bad |= __shfl_down(bad, o, kWave);
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        slo[threadIdx.x / kWave] = lo;
+        shi[threadIdx.x / kWave] = hi;
+        sbad[threadIdx.x / kWave] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int g = 1; g < NW; ++g) {
+        lo = fmin(lo, slo[g]);
+        hi = fmax(hi, shi[g]);
+        bad |= sbad[g];
+    }
+    const double d = a.m.consts[0];
+    const double n = floor((hi - lo) * (1.0 / LorentzBins::kWidth)) + 1.0;
+    const bool ok = !bad && d > 0.0 && d <= kDblMax && fabs(lo) <= kDblMax && fabs(hi) <= kDblMax
+                    && n <= (double)LorentzBins::kMaxBins;                // (a NaN fails every comparison)
+    plan->origin = lo;
+    plan->nbins = ok ? static_cast<int>(n) : 0;
+    plan->poison = ok ? 0u : 1u;
+}
+
+// exclusive prefix over the lanes of a wavefront, and the wavefront's total
+__device__ __forceinline__ int wave_exclusive(int v, int& total) {
+    const int lane = threadIdx.x & (kWave - 1);
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const int up = __shfl_up(inc, o, kWave);
+        inc += lane >= o ? up : 0;
+    }
+    total = __shfl(inc, kWave - 1, kWave);
+    return inc - v;
+}
+
+// A wavefront walks its unit of draws in order, 64 at a time.  Lane l keeps the running figure of bins l and l + 64
+// (c0, c1); per trip the distinct bins of the 64 draws are taken one by one (ballot), and a draw's rank is its bin's
+// running figure plus the number of lower lanes with the same bin.  SCATTER = false: the figures start at 0 and end
+// as the unit's counts.  SCATTER = true: they start at the first sorted position of (bin, unit) and every packed
+// record is written there.
+template <bool SCATTER>
+__global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t per, int nunits, BinSweepPtrs q) {
+    using LB = LorentzBins;
+    if (sweep_aborted(a.abort)) return;
+    const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    if (nbins == 0) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int unit = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
+    const double origin = q.plan->origin;
+    int c0 = 0, c1 = 0;
+    if constexpr (SCATTER) {
+        // the bins' first positions (and first items): exclusive prefixes of the totals, by every wavefront for itself
+        const int t0 = q.totals[lane], t1 = q.totals[lane + kWave];
+        int sum0, sum1, isum0, isum1;
+        const int e0 = wave_exclusive(t0, sum0), e1 = sum0 + wave_exclusive(t1, sum1);
+        const int i0 = wave_exclusive((t0 + kBinChunk - 1) / kBinChunk, isum0);
+        const int i1 = isum0 + wave_exclusive((t1 + kBinChunk - 1) / kBinChunk, isum1);
+        if (unit == 0) {
+            q.binstart[lane] = e0;
+            q.binstart[lane + kWave] = e1;
+            q.itemstart[lane] = i0;
+            q.itemstart[lane + kWave] = i1;
+            if (lane == 0) {
+                q.binstart[LB::kMaxBins] = sum0 + sum1;
+                q.itemstart[LB::kMaxBins] = isum0 + isum1;
+            }
+        }
+        if (unit >= nunits) return;
+        c0 = e0 + q.counts[lane * kBinMaxUnits + unit];
+        c1 = e1 + q.counts[(lane + kWave) * kBinMaxUnits + unit];
+    }
+    if (unit >= nunits) return;
+    const int64_t begin = (int64_t)unit * per;
+    const int64_t end = begin + per < a.nd ? begin + per : a.nd;
+    const double2* __restrict__ rec = reinterpret_cast<const double2*>(a.packed);
+    for (int64_t i0 = begin; i0 < end; i0 += kWave) {
+        const int64_t i = i0 + lane;
+        const bool live = i < end;
+        double2 ra{0.0, 0.0}, rb{0.0, 0.0};
+        if (live) {
+            ra = rec[2 * i];
+            if constexpr (SCATTER) rb = rec[2 * i + 1];
+        }
+        const int bin = live ? LB::bin_of(origin, ra.x, nbins) : -1;
+        int pos = 0;
+        unsigned long long todo = __ballot(live);
+        while (todo) {
+            const int b = __builtin_amdgcn_readlane(bin, __builtin_ctzll(todo));      // (wave-uniform)
+            const unsigned long long same = __ballot(bin == b);
+            const int figure = __builtin_amdgcn_readlane(b < kWave ? c0 : c1, b & (kWave - 1));
+            if (bin == b) pos = figure + __popcll(same & ((1ull << lane) - 1ull));
+            const int n = __popcll(same);
+            if (lane == (b & (kWave - 1))) {
+                if (b < kWave) c0 += n;
+                else c1 += n;
+            }
+            todo &= ~same;
+        }
+        if constexpr (SCATTER) {
+            if (live && pos >= 0 && pos < a.nd) {
+                double2* __restrict__ out = reinterpret_cast<double2*>(q.sorted) + 2 * (int64_t)pos;
+                out[0] = ra;
+                out[1] = rb;
+            }
+        }
+    }
+    if constexpr (!SCATTER) {
+        q.counts[lane * kBinMaxUnits + unit] = c0;
+        q.counts[(lane + kWave) * kBinMaxUnits + unit] = c1;
+    }
+}
+
+// one workgroup per bin: counts[bin][unit] -> the number of the bin's draws in earlier units, and its total
+__global__ __launch_bounds__(kBlock) void bin_scan_kernel(int nunits, BinSweepPtrs q, const unsigned* abort) {
+    __shared__ int wsum[kBlock / kWave];
+    if (sweep_aborted(abort)) return;
+    const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    const int bin = blockIdx.x;
+    if (nbins == 0) return;
+    if (bin >= nbins) {
+        if (threadIdx.x == 0) q.totals[bin] = 0;
+        return;
+    }
+    int* __restrict__ row = q.counts + bin * kBinMaxUnits;
+    int v[kBinScanPer], mine = 0;
+#pragma unroll
+    for (int u = 0; u < kBinScanPer; ++u) {
+        const int k = threadIdx.x * kBinScanPer + u;
+        v[u] = k < nunits ? row[k] : 0;
+        mine += v[u];
+    }
+    int wtotal;
+    int before = wave_exclusive(mine, wtotal);
+    if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = wtotal;
+    __syncthreads();
+    int total = 0;
+#pragma unroll
+    for (int g = 0; g < kBlock / kWave; ++g) {
+        if (g < (int)threadIdx.x / kWave) before += wsum[g];
+        total += wsum[g];
+    }
+#pragma unroll
+    for (int u = 0; u < kBinScanPer; ++u) {
+        const int k = threadIdx.x * kBinScanPer + u;
+        if (k < nunits) row[k] = before;
+        before += v[u];
+    }
+    if (threadIdx.x == 0) q.totals[bin] = total;
+}
+
+// one wavefront per item: kBinChunk consecutive sorted draws of one bin
+__global__ __launch_bounds__(kWave) void bin_moments_kernel(BinSweepPtrs q, const unsigned* abort) {
+    using LB = LorentzBins;
+    if (sweep_aborted(abort)) return;
+    const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    if (nbins == 0) return;
+    const int lane = threadIdx.x, item = blockIdx.x;
+    if (item >= q.itemstart[LB::kMaxBins]) return;
+    // the last bin whose first item is not behind this one (an empty bin shares its first item with the next)
+    const int s0 = q.itemstart[lane], s1 = q.itemstart[lane + kWave];
+    const int bin = __popcll(__ballot(lane < nbins && s0 <= item)) + __popcll(__ballot(lane + kWave < nbins && s1 <= item)) - 1;
+    const int first = q.binstart[bin] + (item - q.itemstart[bin]) * kBinChunk;
+    const int last = q.binstart[bin + 1];
+    const int end = first + kBinChunk < last ? first + kBinChunk : last;
+    const double tb = LB::centre(q.plan->origin, bin);
+    const double2* __restrict__ rec = reinterpret_cast<const double2*>(q.sorted);
+    LB::Sums z;
+    z.clear();
+    for (int i = first + lane; i < end; i += kWave) {
+        const double2 ra = rec[2 * (int64_t)i], rb = rec[2 * (int64_t)i + 1];
+        const double pk[4] = {ra.x, ra.y, rb.x, rb.y};
+        LB::add_draw(tb, pk, z);
+    }
+    // the 64 lanes' sums by a butterfly (the same association on every lane); lane j keeps coefficient j, j + 64
+    double keep0 = 0.0, keep1 = 0.0;
+    auto reduce = [&](double v, int j, double scale) {
+#pragma unroll
+        for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
+        v *= scale;
+        if (j < kWave) keep0 = lane == j ? v : keep0;
+        else keep1 = lane == j - kWave ? v : keep1;
+    };
+#pragma unroll
+    for (int k = 0; k < LB::kOrder; ++k) {
+        reduce(z.M1[k], k, 1.0);
+        reduce(z.M2[k], LB::kOrder + k, 1.0);
+        reduce(z.M3[k], 2 * LB::kOrder + k, (double)(k + 1));
+    }
+    reduce(z.c1, 3 * LB::kOrder, 1.0);
+    reduce(z.c2, 3 * LB::kOrder + 1, 1.0);
+    double* __restrict__ out = q.part + (int64_t)item * LB::kRow;
+    out[lane] = keep0;
+    if (lane + kWave < LB::kCoefs) out[lane + kWave] = keep1;
+}
+
+// coef[bin][co] = sum over the bin's items of part[item][co]
+__global__ __launch_bounds__(kBinFoldGroups * kWave) void bin_fold_kernel(BinSweepPtrs q, const unsigned* abort) {
+    using LB = LorentzBins;
+    __shared__ double acc[kBinFoldGroups][kWave];
+    if (sweep_aborted(abort)) return;
+    const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    const int bin = blockIdx.x >> 1, co = (blockIdx.x & 1) * kWave + (threadIdx.x & (kWave - 1));
+    if (bin >= nbins) return;
+    const int first = __builtin_amdgcn_readfirstlane(q.itemstart[bin]);
+    const int n = __builtin_amdgcn_readfirstlane(q.itemstart[bin + 1]) - first;
+    if (n == 0) return;                                   // (an empty bin: bin_eval_kernel never reads its row)
+    const bool live = co < LB::kCoefs;
+    const double t = fold_in_order<kBinFoldGroups>(q.part + (int64_t)first * LB::kRow + co, n, LB::kRow, live, acc);
+    if (threadIdx.x < kWave && live) q.coef[(int64_t)bin * LB::kRow + co] = t;
+}
+
+// `ran` receives `seq`, as in cell_eval_kernel.  The rows come kBinTile bins at a time through LDS, the next tile's
+// global loads in flight while this one is evaluated: a row fetched by the wavefront that needs it (scalar loads, one
+// L2 round trip per bin and wavefront, one wavefront per SIMD at 65 536 settings) left the kernel waiting four
+// fifths of its time.
+constexpr int kBinTile = 16;
+__global__ __launch_bounds__(kBlock) void bin_eval_kernel(SweepArgs a, BinSweepPtrs q, unsigned seq) {
+    using LB = LorentzBins;
+    constexpr int kTileDoubles = kBinTile * LB::kRow, kPer = (kTileDoubles + kBlock - 1) / kBlock;
+    __shared__ double tile[kTileDoubles];
+    __shared__ int occupied[kBinTile];
+    if (sweep_aborted(a.abort)) return;
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    double S1 = __builtin_nan(""), S2 = __builtin_nan("");        // poisoned: kappa = NaN, the caller repeats without the bit
+    if (nbins > 0) {
+        double tau;
+        Lorentz<1>::prep_setting(a.settings + (s < a.ns ? s : a.ns - 1), a.m, &tau);
+        const double origin = q.plan->origin;
+        const double* __restrict__ coef = q.coef;
+        const int total = nbins * LB::kRow;
+        double nxt[kPer];
+        int nxt_occ = 0;
+        // (the row of an empty bin was never written: it is fetched with the others and never used)
+        auto fetch = [&](int b0) {
+#pragma unroll
+            for (int u = 0; u < kPer; ++u) {
+                const int e = b0 * LB::kRow + u * kBlock + (int)threadIdx.x;
+                nxt[u] = u * kBlock + (int)threadIdx.x < kTileDoubles && e < total ? coef[e] : 0.0;
+            }
+            const int b = b0 + (int)threadIdx.x;
+            nxt_occ = (int)threadIdx.x < kBinTile && b < nbins ? q.binstart[b + 1] != q.binstart[b] : 0;
+        };
+        fetch(0);
+        double a1 = 0.0, a2 = 0.0, C1 = 0.0, C2 = 0.0;
+        for (int b0 = 0; b0 < nbins; b0 += kBinTile) {
+            __syncthreads();                                      // the previous tile has been evaluated
+#pragma unroll
+            for (int u = 0; u < kPer; ++u)
+                if (u * kBlock + (int)threadIdx.x < kTileDoubles) tile[u * kBlock + threadIdx.x] = nxt[u];
+            if (threadIdx.x < kBinTile) occupied[threadIdx.x] = nxt_occ;
+            __syncthreads();
+            if (b0 + kBinTile < nbins) fetch(b0 + kBinTile);
+            for (int t = 0; t < kBinTile; ++t) {
+                if (!__builtin_amdgcn_readfirstlane(occupied[t])) continue;       // (wave-uniform; beyond nbins: 0)
+                const double* row = tile + t * LB::kRow;
+                double t1, t2;
+                LB::evaluate(row, LB::centre(origin, b0 + t) - tau, t1, t2);
+                a1 += t1;
+                a2 += t2;
+                C1 += row[3 * LB::kOrder];
+                C2 += row[3 * LB::kOrder + 1];
+            }
+        }
+        S1 = a1 + C1;
+        S2 = a2 + C2;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *q.ran = seq;
+    if (s >= a.ns) return;
     a.part1[s] = S1;
     a.part2[s] = S2;
     a.cs_out[s] = 0.0;
@@ -1097,13 +1504,20 @@ struct SweepWs {
     double* packed;
 };
 
-// what a cell sweep (OBE_SWEEP_CELLS) keeps behind the packed draws, with the slack that aligns it; a library built
-// for one generated model has no cell form
+// what a cell sweep (OBE_SWEEP_CELLS) or a bin sweep (OBE_SWEEP_BINS) keeps behind the packed draws, with the slack
+// that aligns it; a library built for one generated model has neither form
 static int64_t cell_form_doubles(int64_t nd) {
 #ifdef OBE_PLUGIN_MODEL_HEADER
     return 0;
 #else
     return cell_ws_doubles(nd) + 2;
+#endif
+}
+static int64_t bin_form_doubles(int64_t nd) {
+#ifdef OBE_PLUGIN_MODEL_HEADER
+    return 0;
+#else
+    return bin_ws_doubles(nd) + 2;
 #endif
 }
 static int64_t sweep_ws_bytes(int64_t part_doubles, int64_t cs_doubles, int64_t slots, int64_t packed_doubles) {
@@ -1115,7 +1529,7 @@ static int64_t sweep_ws_bytes_bound(int64_t ns, int64_t nd, int nc, int packed_w
     // (sized by the monotone bound: the chunk count itself is not monotone in nd after the rounding
     // of the chunk length, and a sweep of N_DRAWS < n_particles draws runs in the same workspace)
     return sweep_ws_bytes((int64_t)p.nchunks_bound * nc * ns, (int64_t)nc * ns, argmax_slots(ns),
-                          nd * packed_w + cell_form_doubles(nd));
+                          nd * packed_w + std::max(cell_form_doubles(nd), bin_form_doubles(nd)));
 }
 static int carve_sweep_ws(void* d_ws, int64_t ws_bytes, int64_t part_doubles, int64_t cs_doubles, SweepWs& w,
                           int64_t slots = kMaxBlocks, int64_t packed_doubles = 0) {
@@ -1243,6 +1657,58 @@ static bool cell_form_selected(const obe_model& m, int flags, int64_t ns, const 
 #endif
 }
 
+// the bin form of one call (it goes before the cell form where both bits are set)
+struct BinSweep {
+    bool on = false;
+#ifndef OBE_PLUGIN_MODEL_HEADER
+    BinSweepPtrs q{};
+#endif
+    unsigned* ran = nullptr;       // bin_eval_kernel's marker
+    unsigned seq = 0;
+    BinUnits units{};
+    int64_t items = 0;             // items bin_moments_kernel is launched for: at least as many as any cloud makes
+};
+// OBE_SWEEP_BINS is honoured where the cell form would be, for clouds whose positions fit an int
+static bool bin_form_selected(const obe_model& m, int flags, int64_t ns, const int64_t* d_draw_idx, int64_t n_draws,
+                              int64_t nd) {
+    return (flags & OBE_SWEEP_BINS) && nd <= ((int64_t)1 << 30)
+           && cell_form_selected(m, flags | OBE_SWEEP_CELLS, ns, d_draw_idx, n_draws);
+}
+
+#ifndef OBE_PLUGIN_MODEL_HEADER
+// once per call, behind the pack: the draws grouped by bin and the bins' folded rows (they depend on the cloud alone)
+static int launch_bin_plan(const SweepArgs& a, const BinSweep& b, hipStream_t st) {
+    using LB = LorentzBins;
+    const int mm_blocks = static_cast<int>(std::min<int64_t>(kBinMinmaxBlocks, (a.nd + kBlock - 1) / kBlock));
+    bin_minmax_kernel<<<mm_blocks, kBlock, 0, st>>>(a, b.q.minmax);
+    OBE_CHECK_LAUNCH("bin_minmax_kernel");
+    bin_plan_kernel<<<1, kBinMinmaxBlocks, 0, st>>>(a, b.q.minmax, mm_blocks, b.q.plan);
+    OBE_CHECK_LAUNCH("bin_plan_kernel");
+    const unsigned group_blocks = (unsigned)((b.units.nunits + kBlock / kWave - 1) / (kBlock / kWave));
+    bin_group_kernel<false><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, b.q);
+    OBE_CHECK_LAUNCH("bin_group_kernel<count>");
+    bin_scan_kernel<<<LB::kMaxBins, kBlock, 0, st>>>(b.units.nunits, b.q, a.abort);
+    OBE_CHECK_LAUNCH("bin_scan_kernel");
+    bin_group_kernel<true><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, b.q);
+    OBE_CHECK_LAUNCH("bin_group_kernel<scatter>");
+    bin_moments_kernel<<<(unsigned)b.items, kWave, 0, st>>>(b.q, a.abort);
+    OBE_CHECK_LAUNCH("bin_moments_kernel");
+    bin_fold_kernel<<<2 * LB::kMaxBins, kBinFoldGroups * kWave, 0, st>>>(b.q, a.abort);
+    OBE_CHECK_LAUNCH("bin_fold_kernel");
+    return 0;
+}
+// in place of launch_sweep: one chunk of moments in part1 / part2, cs_out = 0
+static int launch_bin_sweep(SweepPlan& p, SweepArgs& a, const BinSweep& b, hipStream_t st) {
+    p.nchunks = 1;
+    bin_eval_kernel<<<(unsigned)((a.ns + kBlock - 1) / kBlock), kBlock, 0, st>>>(a, b.q, b.seq);
+    OBE_CHECK_LAUNCH("bin_eval_kernel");
+    return 0;
+}
+#else
+static int launch_bin_plan(const SweepArgs&, const BinSweep&, hipStream_t) { return 0; }
+static int launch_bin_sweep(SweepPlan&, SweepArgs&, const BinSweep&, hipStream_t) { return 0; }
+#endif
+
 #ifndef OBE_PLUGIN_MODEL_HEADER
 // once per call, with the pack: the cells of this call's settings
 static int launch_cell_plan(const SweepArgs& a, const CellSweep& c, hipStream_t st) {
@@ -1277,7 +1743,7 @@ static int prepare_sweep(const obe_model* m, obe_model& mm, const double* d_sett
                          const double* d_particles, int64_t ld_p, int64_t np, const double* d_weights,
                          const int64_t* d_draw_idx, int64_t n_draws, const double* d_moments, void* d_ws,
                          int64_t ws_bytes, SweepPlan& plan, SweepArgs& a, SweepWs& w, int64_t* ws_need = nullptr,
-                         int flags = 0, CellSweep* cells = nullptr) {
+                         int flags = 0, CellSweep* cells = nullptr, BinSweep* bins = nullptr) {
     if (!m || !d_settings || !d_particles || !d_moments || ns <= 0 || np <= 0) return bad_arg("sweep: bad pointer/size");
     if (!d_draw_idx && !d_weights) return bad_arg("sweep: full mode needs weights");
     mm = *m;
@@ -1293,8 +1759,9 @@ static int prepare_sweep(const obe_model* m, obe_model& mm, const double* d_sett
         return rc;
     plan = plan_sweep(ns, nd, cost, mm.n_channels > 4 ? 2 : 8);
     const int64_t part = (int64_t)plan.nchunks * mm.n_channels * ns;
-    const bool cell_form = cells && cell_form_selected(mm, flags, ns, d_draw_idx, n_draws);
-    const int64_t behind_parts = nd * packed_w + (cell_form ? cell_form_doubles(nd) : 0);
+    const bool bin_form = bins && bin_form_selected(mm, flags, ns, d_draw_idx, n_draws, nd);
+    const bool cell_form = !bin_form && cells && cell_form_selected(mm, flags, ns, d_draw_idx, n_draws);
+    const int64_t behind_parts = nd * packed_w + (bin_form ? bin_form_doubles(nd) : cell_form ? cell_form_doubles(nd) : 0);
     if (int rc = carve_sweep_ws(d_ws, ws_bytes, part, (int64_t)mm.n_channels * ns, w, argmax_slots(ns), behind_parts))
         return rc;
     if (ws_need) *ws_need = sweep_ws_bytes(part, (int64_t)mm.n_channels * ns, argmax_slots(ns), behind_parts);
@@ -1309,6 +1776,29 @@ static int prepare_sweep(const obe_model* m, obe_model& mm, const double* d_sett
             cells->part = cells->coef + (int64_t)LorentzCells::kCoefs * LorentzCells::kMaxCells;
             cells->chunks = plan_cell_chunks(nd);
         }
+    }
+    if (bins) {
+        bins->on = bin_form;
+#ifndef OBE_PLUGIN_MODEL_HEADER
+        if (bin_form) {
+            double* base = w.packed + nd * packed_w;
+            base = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(base) + 15) & ~uintptr_t(15));
+            using BL = BinLayout;
+            BinSweepPtrs& q = bins->q;
+            q.plan = reinterpret_cast<BinPlan*>(base + BL::kPlan);
+            q.ran = bins->ran = reinterpret_cast<unsigned*>(base + BL::kRan);
+            q.binstart = reinterpret_cast<int*>(base + BL::kStarts);
+            q.itemstart = q.binstart + LorentzBins::kMaxBins + 2;
+            q.minmax = base + BL::kMinmax;
+            q.totals = reinterpret_cast<int*>(base + BL::kTotals);
+            q.counts = reinterpret_cast<int*>(base + BL::kCounts);
+            q.coef = base + BL::kCoef;
+            q.part = base + BL::kPart;
+            q.sorted = base + BL::sorted(nd);
+            bins->units = plan_bin_units(nd);
+            bins->items = bin_max_items(nd);
+        }
+#endif
     }
     a.cs_out = w.cs;
     a.packed = w.packed;
@@ -1356,6 +1846,24 @@ int obe_sweep_cells_plan(double x_min, double x_max, double d, int64_t n_setting
     return worthwhile ? 3 : 1;
 }
 
+int obe_sweep_bins_plan(double x_min, double x_max, double d, int64_t n_settings, int64_t n_draws) {
+    if (!(d > 0.0 && d <= kDblMax) || !(x_min <= x_max) || !(fabs(x_min) <= kDblMax && fabs(x_max) <= kDblMax)
+        || n_settings < 1 || n_draws < 1 || n_draws > ((int64_t)1 << 30))
+        return 0;
+    // the form it would replace: the cells where their plan takes them, otherwise the direct kernel
+    const int cells = obe_sweep_cells_plan(x_min, x_max, d, n_settings, n_draws);
+    double replaced = (double)n_settings * (double)n_draws * kDirectSlots;
+    if (cells == 3) {
+        const double ncells = std::floor((x_max / d - x_min / d) * (1.0 / LorentzCells::kWidth)) + 1.0;
+        replaced = (double)n_draws * std::ceil(ncells / kWave) * kWave * kCellSlots;
+    }
+    // priced at the cap (the occupied bins are a property of the cloud, which changes): every setting meets
+    // OBE_BIN_MAX bins, every draw is expanded once, and the launches of the pipeline cost what they cost on a
+    // cloud of a few draws
+    const double bins = (double)n_settings * OBE_BIN_MAX * kBinEvalSlots + (double)n_draws * kBinDrawSlots + kBinFixedSlots;
+    return replaced >= OBE_CELL_MIN_GAIN * bins ? 3 : 1;
+}
+
 int obe_sweep_settings_per_lane_for(int64_t n_settings, int64_t n_draws) {
     if (n_settings < 1) n_settings = 1;
     if (n_draws < 1) return obe_sweep_settings_per_lane(n_settings);
@@ -1395,8 +1903,10 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     SweepWs w;
     int64_t sweep_ws_need = 0;
     CellSweep cells;
+    BinSweep bins;
     if (int rc = prepare_sweep(m, mm, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles, d_weights,
-                               d_draw_idx, n_draws, d_moments, d_ws, ws_bytes, plan, a, w, &sweep_ws_need, shifted, &cells))
+                               d_draw_idx, n_draws, d_moments, d_ws, ws_bytes, plan, a, w, &sweep_ws_need, shifted, &cells,
+                               &bins))
         return rc;
     hipStream_t st = as_stream(stream);
     UtilArgs ua;
@@ -1450,12 +1960,19 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     }
     int rc = dispatch_model(mm, [&](auto M) -> int {
         if (int e = launch_pack<decltype(M)>(a, st)) return e;
-        if (cells.on) {
-            if (timed && nowait) cells.seq = ++g_timing.seq ? g_timing.seq : ++g_timing.seq;      // (never 0)
-            if (int e = launch_cell_plan(a, cells, st)) return e;
+        if (cells.on || bins.on) {
+            const unsigned seq = timed && nowait ? (++g_timing.seq ? g_timing.seq : ++g_timing.seq) : 0u;      // (never 0)
+            cells.seq = bins.seq = seq;
+            if (cells.on)
+                if (int e = launch_cell_plan(a, cells, st)) return e;
         }
         if (timed) (void)hipEventRecord(g_timing.e0, st);
-        const int e = cells.on ? launch_cell_sweep(plan, a, cells, st) : launch_sweep<decltype(M)>(plan, a, shifted, st);
+        // (the bins are a function of the cloud: grouping it is part of the sweep, and of its time)
+        if (bins.on)
+            if (int e = launch_bin_plan(a, bins, st)) return e;
+        const int e = bins.on    ? launch_bin_sweep(plan, a, bins, st)
+                      : cells.on ? launch_cell_sweep(plan, a, cells, st)
+                                 : launch_sweep<decltype(M)>(plan, a, shifted, st);
         if (timed) (void)hipEventRecord(g_timing.e1, st);
         return e;
     });
@@ -1483,7 +2000,7 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
         if (timed) {
             g_timing.pending = true;
             g_timing.pending_min_ms = 0.5 * (double)n_settings * (double)n_particles / 8e9;
-            g_timing.pending_ran = cells.on ? cells.ran : nullptr;
+            g_timing.pending_ran = bins.on ? bins.ran : cells.on ? cells.ran : nullptr;
             g_timing.pending_seq = cells.seq;
         }
         return 0;
@@ -1516,14 +2033,20 @@ int obe_sweep_kernel_time(const obe_model* m, const double* d_settings, int64_t 
     SweepArgs a{};
     SweepWs w;
     CellSweep cells;
+    BinSweep bins;
     if (int rc = prepare_sweep(m, mm, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles, d_weights,
-                               nullptr, 0, d_moments, d_ws, ws_bytes, plan, a, w, nullptr, shifted, &cells))
+                               nullptr, 0, d_moments, d_ws, ws_bytes, plan, a, w, nullptr, shifted, &cells, &bins))
         return rc;
     hipStream_t st = as_stream(stream);
     hipEvent_t e0, e1;
     OBE_HIP_TRY(hipEventCreate(&e0));
     OBE_HIP_TRY(hipEventCreate(&e1));
     auto sweep_once = [&]() -> int {
+        // (the bins are a function of the cloud, and a new cloud means a new sweep: the whole pipeline is the sweep)
+        if (bins.on) {
+            if (int e = launch_bin_plan(a, bins, st)) return e;
+            return launch_bin_sweep(plan, a, bins, st);
+        }
         if (cells.on) return launch_cell_sweep(plan, a, cells, st);
         return dispatch_model(mm, [&](auto M) -> int { return launch_sweep<decltype(M)>(plan, a, shifted, st); });
     };

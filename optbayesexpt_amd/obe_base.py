@@ -149,7 +149,8 @@ class OptBayesExpt(ParticlePDF):
         ``pdf_update()`` enqueues the sweep of the next ``opt_setting()`` behind its update (see
         ``_speculation_wanted``): the same results, one host round trip per cycle less.
     ``tuning_parameters['sweep_shift']`` (``'auto'``, ``'always'``, ``'never'``), ``['sweep_cells']`` (``'auto'``,
-    ``'always'``, ``'never'``: the one-peak Lorentzian's unshifted sweep by cell expansions), ``['fused_moments']``,
+    ``'always'``, ``'never'``: the one-peak Lorentzian's unshifted sweep by cell expansions), ``['sweep_bins']`` (the
+    same values: that sweep by bin expansions of the particles), ``['fused_moments']``,
     ``['replica_check_every']``
         see ``_sweep_device``, ``pdf_update``, ``check_replicas``.
     """
@@ -810,6 +811,7 @@ class OptBayesExpt(ParticlePDF):
         between the sweep enqueued ahead and the one being asked for (both must read the same)."""
         return dict(cloud=(self._particles.version, self._weights.version), shifted=bool(shifted),
                     cells=bool(not shifted and self._cell_form_wanted()),
+                    bins=bool(not shifted and self._bin_form_wanted()),
                     noise=self._noise_token(), settings=(self._s_begin, self._s_end),
                     alias=self._parameters is self._particles,
                     cost_hook=_overridden(self, "cost_estimate", OptBayesExpt))
@@ -1090,8 +1092,13 @@ class OptBayesExpt(ParticlePDF):
             # the cell form stands in for the unshifted direct kernel only: every repeat (shifted, safe) is direct
             return full and not shifted and not safe and self._cell_form_wanted()
 
+        def bins_for(shifted, safe=False):
+            # ... and so does the bin form, which goes before the cells where both are wanted
+            return full and not shifted and not safe and self._bin_form_wanted()
+
         def launch(shifted, safe=False, speculative=False):
-            result["cells"] = cells_for(shifted, safe)
+            result["bins"] = bins_for(shifted, safe)
+            result["cells"] = cells_for(shifted, safe) and not result["bins"]
             # sharded: no host read here — the 32-byte result record is all-gathered from
             # device memory and read back once, together with the other ranks' records
             p, w = self._pw_tensors()
@@ -1107,6 +1114,7 @@ class OptBayesExpt(ParticlePDF):
                            None if idx is None else _ptr(idx), n_draws, _ptr(mom),
                            (_lib.OBE_SWEEP_SHIFTED if shifted else 0) | (_lib.OBE_SWEEP_SAFE if safe else 0)
                            | (_lib.OBE_SWEEP_CELLS if cells_for(shifted, safe) else 0)
+                           | (_lib.OBE_SWEEP_BINS if result["bins"] else 0)
                            | (0 if not speculative else _lib.OBE_SWEEP_NOWAIT if speculative == "after_resample"
                               else _lib.OBE_SWEEP_SPECULATIVE),
                            _ptr(noise), noise_ld, None if cost_t is None else _ptr(cost_t), cost_s,
@@ -1152,16 +1160,24 @@ class OptBayesExpt(ParticlePDF):
         form = state.form_for_next_sweep()
         if lazy:
             launch(True)
-            self.last_sweep = dict(shifted=True, kappa=float("nan"), safe=False, cells=False)     # kappa was not read back
+            self.last_sweep = dict(shifted=True, kappa=float("nan"), safe=False, cells=False, bins=False)     # kappa was not read back
             return None
         if form is Form.FAST:
             taken = self._take_speculative_sweep(shifted) if full else None
             if taken is None:
                 launch(shifted)
             else:
-                result["cells"] = cells_for(shifted)       # (part of the ticket's inputs: what was enqueued ahead)
+                result["bins"] = bins_for(shifted)         # (part of the ticket's inputs: what was enqueued ahead)
+                result["cells"] = cells_for(shifted) and not result["bins"]
                 deliver(taken if sharded else None)
             self._check_pending_total()
+            if result["bins"] and np.isnan(kappa[0]):
+                # the cloud does not fit the bins (its x0 / d span more than OBE_BIN_MAX of them, or one is not
+                # finite): that is a property of the particles alone, so nothing asks for bins again before the
+                # cloud is replaced, and this sweep is repeated in the form that would have run without them
+                self._bins_refused = self._particles.version
+                launch(shifted)
+                self._check_pending_total()
             poisoned = checked and bool(np.isnan(kappa[0]))
             if state.sweep_reported_kappa(mode, full, shifted, float(kappa[0])):
                 shifted = True
@@ -1184,7 +1200,8 @@ class OptBayesExpt(ParticlePDF):
             safe = shifted = True
             launch(True, safe=True)
             self._check_pending_total()
-        self.last_sweep = dict(shifted=shifted, kappa=float(kappa[0]), safe=safe, cells=bool(result["cells"]))
+        self.last_sweep = dict(shifted=shifted, kappa=float(kappa[0]), safe=safe, cells=bool(result["cells"]),
+                               bins=bool(result["bins"]))
         if want_best:
             return result["best"]
         return None
@@ -1206,6 +1223,35 @@ class OptBayesExpt(ParticlePDF):
                 lo, hi = float(np.min(x)), float(np.max(x))
             plan = self._cells_plan = (key, int(self._mlib.cdll.obe_sweep_cells_plan(
                 lo, hi, float(self.cons[0]), self._s_end - self._s_begin, self.n_particles)))
+        return bool(plan[1] & 1) and (mode == "always" or bool(plan[1] & 2))
+
+    def _bin_form_wanted(self):
+        """Whether an unshifted full sweep of this object's settings slice runs as bin expansions of the particles
+        (include/obe_hip.h: OBE_SWEEP_BINS; one-peak Lorentzian only).  ``tuning_parameters['sweep_bins']``:
+        ``'auto'`` (default) — where obe_sweep_bins_plan() finds the form worthwhile, and only while
+        ``'sweep_cells'`` is ``'auto'`` too (a caller who pins the cell form, either way, has chosen the form);
+        ``'always'`` — wherever the inputs are valid; ``'never'``.  A cloud that turned out not to fit the bins is
+        not tried again: only a new cloud (a resample, set_pdf) is."""
+        mode = self.tuning_parameters.get("sweep_bins", "auto")
+        dm = self._device_model
+        if mode == "never" or dm is None or not dm.cell_sweep or self._s_end <= self._s_begin:
+            return False
+        if mode != "always" and self.tuning_parameters.get("sweep_cells", "auto") != "auto":
+            return False
+        if self.__dict__.get("_bins_refused") == self._particles.version:
+            return False
+        key = (self._s_begin, self._s_end, self.n_particles)
+        plan = self.__dict__.get("_bins_plan")
+        if plan is None or plan[0] != key:
+            # (sharded: a poisoned bin sweep is repeated, and every rank must repeat it — kappa is the worst over all
+            # ranks —, so every rank takes this decision from the same figures: the whole grid and the longest slice)
+            x, n = self.allsettings[0, self._s_begin:self._s_end], self._s_end - self._s_begin
+            if self._shard is not None:
+                x, n = self.allsettings[0], -(-self._n_settings // self._shard.world_size)
+            with np.errstate(all="ignore"):
+                lo, hi = float(np.min(x)), float(np.max(x))
+            plan = self._bins_plan = (key, int(self._mlib.cdll.obe_sweep_bins_plan(
+                lo, hi, float(self.cons[0]), n, self.n_particles)))
         return bool(plan[1] & 1) and (mode == "always" or bool(plan[1] & 2))
 
     def _settings_per_lane(self, n_draws=0):

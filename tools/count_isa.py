@@ -7,14 +7,15 @@
 prints the instruction mix of the basic block with the most FP64 instructions and the issue
 slots per evaluation (v_rcp_f64 counted as 4 slots: quarter rate), given the evaluations one
 trip of that loop performs (2 particles x 8 settings = 16 for the pair loop).  The cell form's expansion kernel:
-pattern 'cell_moments_kernel', 4 (cell, particle) expansions per trip."""
+pattern 'cell_moments_kernel', 4 (cell, particle) expansions per trip.  The bin form: 'bin_eval_kernel', 1 (setting,
+bin) per trip of the loop over the bins; 'bin_moments_kernel', 1 draw per lane and trip."""
 import re
 import sys
 from collections import Counter
 
 path, pattern, evals = sys.argv[1], sys.argv[2], int(sys.argv[3])
 lines = open(path).read().split("\n")
-starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\w*(sweep_kernel|cell_moments_kernel)\w*:", l)]
+starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\w*(sweep_kernel|cell_moments_kernel|bin_eval_kernel|bin_moments_kernel)\w*:", l)]
 for k, s in enumerate(starts):
     if pattern not in lines[s]:
         continue
