@@ -462,7 +462,8 @@ OBE_API int obe_power_normalize(const double* d_u, int64_t n, double exponent, d
  * d_moments: output of obe_moments for the same particles/weights (mean parameters are
  * used as the variance shift, sum w as the normaliser).
  * `shifted` is a bit set: OBE_SWEEP_SHIFTED (1), for expression (plugin) models
- * OBE_SWEEP_SAFE (2), and for the one-peak Lorentzian OBE_SWEEP_CELLS (4) and OBE_SWEEP_BINS (32).
+ * OBE_SWEEP_SAFE (2), and for the one-peak Lorentzian OBE_SWEEP_CELLS (4) and OBE_SWEEP_BINS (32; with
+ * obe_sweep_utility_keep() also OBE_SWEEP_BINS_KEPT, 64).
  * OBE_SWEEP_SHIFTED set: moments are accumulated about a per-setting shift (always accurate).
  * OBE_SWEEP_SHIFTED clear: one instruction fewer per evaluation, accurate only while the predicted
  * mean does not dominate the spread; *h_kappa (nullable) returns the worst
@@ -577,6 +578,45 @@ OBE_API int obe_sweep_utility(const obe_model* m,
                       double* d_yvar, double* d_utility,
                       double* h_best, int64_t* h_best_idx, double* h_kappa,
                       void* d_ws, int64_t ws_bytes, void* stream);
+/* ---- the grouping of an OBE_SWEEP_BINS sweep, kept from one call to the next ----
+ * Which bin a draw belongs to, where each bin's run of sorted draws starts and where every draw goes in that order
+ * depend on the packed x0/d alone: not on the weights, the mean parameters or the settings.  The workspace is scratch
+ * of every library call, so what is to outlive a sweep lives in a buffer the CALLER owns: device memory of at least
+ * obe_sweep_bins_keep_bytes(n_particles) bytes, 16-byte aligned, used by one sweep at a time (a head of 16 ints, the
+ * two tables of OBE_BIN_MAX + 2 ints and one int32 position per draw; host only, nothing is launched). */
+OBE_API int64_t obe_sweep_bins_keep_bytes(int64_t n_draws);
+/* OBE_SWEEP_BINS_KEPT (a bit of `shifted`): the caller says that d_keep was filled by an earlier call of
+ * obe_sweep_utility_keep() with the same d_particles, ld_p, n_particles and d, and that no particle value has
+ * changed since.  Honoured only together with OBE_SWEEP_BINS where that bit is, in a full sweep (d_draw_idx == NULL:
+ * draws are drawn anew for every call) and with a d_keep of at least obe_sweep_bins_keep_bytes(n_particles) bytes;
+ * otherwise ignored. */
+#define OBE_SWEEP_BINS_KEPT 64
+/* obe_sweep_utility() with a keep buffer behind its arguments (h_value, h_index, h_factor: its h_best, h_best_idx,
+ * h_kappa); d_keep == NULL, a keep_bytes too small for the call, a draws-mode call or a call that does not take the
+ * bin form: exactly obe_sweep_utility(), and d_keep is not touched.  Otherwise
+ *   OBE_SWEEP_BINS_KEPT clear: the sweep of OBE_SWEEP_BINS, which leaves its plan, its tables and every draw's
+ *     sorted position in d_keep and marks the buffer complete with its last grouping launch (a poisoned plan is kept
+ *     as such; a speculative call that is aborted leaves the buffer as it was);
+ *   OBE_SWEEP_BINS_KEPT set: the pack and the five grouping launches are replaced by ONE launch that writes every
+ *     draw's packed record straight to its kept position — the same records in the same places, so the same bits as a
+ *     rebuild.  The caller's word alone decides nothing: every kernel first checks the head (complete, made for
+ *     n_particles draws and this d), and the pack checks of every draw that its x0/d is finite and still lies in the
+ *     bin whose run holds its kept position.  A buffer that fails either check makes the call return *h_factor = NaN
+ *     and NaN variances, as a poisoned plan does, and nothing is written through it: the caller repeats the call
+ *     without the bit.  (A particle that moved within its bin passes, and gives what a rebuild gives.)
+ * OBE_SWEEP_SPECULATIVE, OBE_SWEEP_NOWAIT, obe_sweep_timing() and the result records work as in obe_sweep_utility().
+ * obe_sweep_kernel_time() has no keep buffer: it times the whole rebuild. */
+OBE_API int obe_sweep_utility_keep(const obe_model* m,
+                      const double* d_settings, int64_t ld_s, int64_t n_settings,
+                      const double* d_particles, int64_t ld_p, int64_t n_particles,
+                      const double* d_weights, const int64_t* d_draw_idx, int64_t n_draws,
+                      const double* d_moments, int32_t shifted,
+                      const double* d_noise_var, int64_t noise_ld,
+                      const double* d_cost, double cost_scalar,
+                      double* d_yvar, double* d_utility,
+                      double* h_value, int64_t* h_index, double* h_factor,
+                      void* d_ws, int64_t ws_bytes, void* stream,
+                      void* d_keep, int64_t keep_bytes);
 
 /* Variance over the draw axis of a caller-filled y-space (N_d, C, N_s) — the
  * np.var(utility_y_space, axis=0) of obe_base.py:488 for host-callable models. */
@@ -896,7 +936,8 @@ OBE_API int obe_timer_destroy(void* timer);
 OBE_API int obe_sweep_timing(int32_t enable, double* h_total_ms, int64_t* h_launches);
 /* Launches only the dominant sweep kernel `iters` times between two events on `stream`
  * and returns the average per-launch duration in ms; iters < 0: -iters isolated launches
- * (the stream is drained before each one), as a measurement cycle issues them. */
+ * (the stream is drained before each one), as a measurement cycle issues them.  With OBE_SWEEP_BINS that is the whole
+ * pipeline behind the pack, grouping included — a rebuild, whatever obe_sweep_utility_keep() callers keep. */
 OBE_API int obe_sweep_kernel_time(const obe_model* m,
                           const double* d_settings, int64_t ld_s, int64_t n_settings,
                           const double* d_particles, int64_t ld_p, int64_t n_particles,

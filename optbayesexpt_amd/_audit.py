@@ -99,7 +99,7 @@ class _Audit(_NoAudit):
         self.violations = []
         self.counts = dict(zones=0, armed=0, waited=0, reads=0, syncs=0)
         self.rules = {}           # entry point -> (rule, the argument positions of the parameters it reads)
-        for fn, (rule, *names) in {**_RULES, **_BOUNDS_RULES, **_BATCH_RULES}.items():
+        for fn, (rule, *names) in {**_RULES, **_BOUNDS_RULES, **_BATCH_RULES, **_KEEP_RULES}.items():
             params = [name for _, name in PROTOTYPES[fn][1]]
             self.rules[fn] = (rule, tuple(params.index(name) for name in names))
 
@@ -292,6 +292,12 @@ def _tempered_sums(a, n_trials, h_sums):
 # for as many words as the call has trials, under the parameter names of its own prototype
 _BATCH_RULES = {
     "obe_tempered_sums": (_tempered_sums, "n_trials", "h_sums"),
+}
+
+# the sweep with a keep buffer behind its arguments (include/obe_hip.h: obe_sweep_utility_keep): obe_sweep_utility's
+# rule, under the parameter names of its own prototype
+_KEEP_RULES = {
+    "obe_sweep_utility_keep": (_sweep, "shifted", "h_value", "h_index", "h_factor"),
 }
 
 audit = _Audit() if os.environ.get("OBE_CHECK_DELIVERY") == "1" else _NoAudit()

@@ -41,6 +41,8 @@ OBE_CELL_RHO_INV, OBE_CELL_ORDER, OBE_CELL_MAX = _H["OBE_CELL_RHO_INV"], _H["OBE
 OBE_CELL_MIN_GAIN = _H["OBE_CELL_MIN_GAIN"]
 # the bin form: the same half-width and order on the particles' axis, at most OBE_BIN_MAX bins
 OBE_SWEEP_BINS, OBE_BIN_MAX = _H["OBE_SWEEP_BINS"], _H["OBE_BIN_MAX"]
+# ... whose grouping obe_sweep_utility_keep() keeps in a buffer of the caller's from one sweep to the next
+OBE_SWEEP_BINS_KEPT = _H["OBE_SWEEP_BINS_KEPT"]
 HOST_SENTINEL = 0x7ff8c0dec0dec0de     # the value of an armed host result word (csrc/obe_common.h: kHostSentinel)
 
 c_void_p, c_int, c_int32, c_int64, c_double = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int32,
@@ -133,6 +135,7 @@ MODEL_ENTRY_POINTS = ("obe_model_validate", "obe_workspace_bytes", "obe_sweep_se
                       "obe_bayes_update_sweep",
                       "obe_eval_over_particles",
                       "obe_eval_over_settings", "obe_sweep_utility", "obe_sweep_kernel_time", "obe_sweep_timing",
+                      "obe_sweep_utility_keep", "obe_sweep_bins_keep_bytes",
                       "obe_eval_draws",
                       "obe_predictive_workspace_bytes", "obe_predictive_moments", "obe_predictive_quantiles",
                       "obe_predictive_score_workspace_bytes", "obe_predictive_logpdf", "obe_predictive_tails",

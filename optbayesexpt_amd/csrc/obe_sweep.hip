@@ -27,6 +27,7 @@
 // Variance numerics: moments are accumulated about a per-setting shift
 // c_s = model(x_s; mean parameters), so  var = (S2 - S1^2/W)/W  does not cancel
 // catastrophically (np.var is two-pass; the shift plays the role of its first pass).
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -462,6 +463,25 @@ static_assert(BinLayout::kPart % 2 == 0 && LorentzBins::kRow % 2 == 0, "the sort
 // the plan, the tables and the sorted records of any bin sweep of AT MOST nd draws
 static int64_t bin_ws_doubles(int64_t nd) { return BinLayout::doubles(nd); }
 
+// ---- the kept grouping (obe_sweep_utility_keep, OBE_SWEEP_BINS_KEPT) ----
+// The workspace is scratch of every library call; what outlives a sweep lives in a buffer of the caller's: the plan,
+// binstart / itemstart and the sorted position of every draw — functions of the packed tau0 = x0 / d alone.
+struct BinKeep {           // head of the buffer
+    BinPlan plan;
+    unsigned mark;         // kBinKeepMark once the grouping behind it is complete (bin_group_kernel<true> writes it)
+    int nd;                // the draws it was made for ...
+    unsigned long long dbits;      // ... and the bits of d
+    unsigned mismatch;     // the `call` of the last reuse that found a draw outside its kept bin
+    unsigned pad[7];
+};
+static_assert(sizeof(BinKeep) == 64, "the head of the keep buffer is 16 ints");
+constexpr unsigned kBinKeepMark = 0x6b455042u;
+struct BinKeepLayout {      // in ints
+    static constexpr int64_t kStarts = sizeof(BinKeep) / sizeof(int);                       // 2 x 130 ints
+    static constexpr int64_t kDest = (kStarts + 2 * (LorentzBins::kMaxBins + 2) + 3) & ~(int64_t)3;
+    static int64_t bytes(int64_t nd) { return ((kDest + nd) * (int64_t)sizeof(int) + 15) & ~(int64_t)15; }
+};
+
 #ifndef OBE_PLUGIN_MODEL_HEADER
 __global__ __launch_bounds__(kCellPlanThreads) void cell_plan_kernel(SweepArgs a, CellPlan* __restrict__ plan) {
     constexpr int NW = kCellPlanThreads / kWave;
@@ -682,11 +702,22 @@ __global__ __launch_bounds__(kBlock) void cell_eval_kernel(SweepArgs a, const Ce
 //   bin_eval_kernel      lane <-> setting, the bins' rows through LDS, bins in order; writes part1 / part2 as ONE
 //                        chunk and cs_out = 0, as cell_eval_kernel does.
 // No floating-point atomics; every sum has a fixed association, so two calls on the same inputs give the same bits.
+// With a keep buffer (obe_sweep_utility_keep) the plan, binstart and itemstart live there and bin_group_kernel<1> also
+// leaves every draw's sorted position; a later call with OBE_SWEEP_BINS_KEPT runs, in place of the pack and the five
+// grouping launches,
+//   bin_scatter_pack_kernel   sweep_pack_kernel's record of draw p, written to sorted[dest[p]]
+// and then bin_moments_kernel onwards: the same records in the same places, hence the same bits.
 struct BinSweepPtrs {
     BinPlan* plan;
     unsigned* ran;
     int* binstart;         // [kMaxBins + 1] first sorted draw of each bin
     int* itemstart;        // [kMaxBins + 1] first item of each bin
+    BinKeep* keep;         // the caller's keep buffer (plan, binstart and itemstart point into it), or NULL
+    int* dest;             // [nd] the sorted position of every draw, in the keep buffer (NULL without one)
+    int reuse;             // OBE_SWEEP_BINS_KEPT: the grouping is read from the keep buffer, not made
+    int keep_nd;           // what a reused buffer must have been made for: this many draws ...
+    unsigned long long keep_dbits;     // ... and this d
+    unsigned call;         // this call among the process's calls with a keep buffer (never 0)
     double* minmax;
     int* totals;
     int* counts;           // [bin * kBinMaxUnits + unit]
@@ -694,6 +725,15 @@ struct BinSweepPtrs {
     double* part;
     double* sorted;
 };
+
+// OBE_SWEEP_BINS_KEPT: the caller's word that the buffer fits this cloud does not decide what is read through it.  Every
+// kernel of a reuse first looks at the head: a complete grouping (the mark) of this many draws at this d.  (A rebuild
+// reads what its own kernels have just written.)
+__device__ __forceinline__ bool bin_keep_refused(const BinSweepPtrs& q) {
+    if (!q.reuse) return false;
+    const BinKeep* k = q.keep;
+    return !(k->mark == kBinKeepMark && k->nd == q.keep_nd && k->dbits == q.keep_dbits);
+}
 
 __global__ __launch_bounds__(kBlock) void bin_minmax_kernel(SweepArgs a, double* __restrict__ minmax) {
     constexpr int NW = kBlock / kWave;
@@ -732,7 +772,8 @@ __global__ __launch_bounds__(kBlock) void bin_minmax_kernel(SweepArgs a, double*
 }
 
 __global__ __launch_bounds__(kBinMinmaxBlocks) void bin_plan_kernel(SweepArgs a, const double* __restrict__ minmax,
-                                                                     int nblocks, BinPlan* __restrict__ plan) {
+                                                                     int nblocks, BinPlan* __restrict__ plan,
+                                                                     BinKeep* keep) {
     constexpr int NW = kBinMinmaxBlocks / kWave;
     __shared__ double slo[NW], shi[NW];
     __shared__ int sbad[NW];
@@ -762,6 +803,7 @@ __global__ __launch_bounds__(kBinMinmaxBlocks) void bin_plan_kernel(SweepArgs a,
     const double n = floor((hi - lo) * (1.0 / LorentzBins::kWidth)) + 1.0;
     const bool ok = !bad && d > 0.0 && d <= kDblMax && fabs(lo) <= kDblMax && fabs(hi) <= kDblMax
                     && n <= (double)LorentzBins::kMaxBins;                // (a NaN fails every comparison)
+    if (keep) keep->mark = 0u;        // (the plan lives in the keep buffer: no grouping until the scatter pass says so)
     plan->origin = lo;
     plan->nbins = ok ? static_cast<int>(n) : 0;
     plan->poison = ok ? 0u : 1u;
@@ -790,6 +832,15 @@ __global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t 
     using LB = LorentzBins;
     if (sweep_aborted(a.abort)) return;
     const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    if constexpr (SCATTER) {
+        // the last grouping launch: when it has ended, the keep buffer describes these draws (a poisoned plan included)
+        if (q.keep && blockIdx.x == 0 && threadIdx.x == 0) {
+            q.keep->nd = static_cast<int>(a.nd);
+            q.keep->dbits = q.keep_dbits;
+            q.keep->mismatch = 0u;
+            q.keep->mark = kBinKeepMark;
+        }
+    }
     if (nbins == 0) return;
     const int lane = threadIdx.x & (kWave - 1);
     const int unit = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
@@ -849,11 +900,52 @@ __global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t 
                 out[0] = ra;
                 out[1] = rb;
             }
+            if (q.dest && live) q.dest[i] = pos;
         }
     }
     if constexpr (!SCATTER) {
         q.counts[lane * kBinMaxUnits + unit] = c0;
         q.counts[(lane + kWave) * kBinMaxUnits + unit] = c1;
+    }
+}
+
+// OBE_SWEEP_BINS_KEPT, in place of sweep_pack_kernel and the five launches above: sweep_pack_kernel<Lorentz<1>>'s record of
+// draw p (full mode), written where bin_group_kernel<true> put it when the keep buffer was made.  Nothing is written
+// unless the head fits the call (bin_keep_refused: that is what keeps dest[p] inside `sorted`), and a draw goes
+// nowhere unless it still belongs to the bin whose run holds its kept position: a tau0 that is not finite, lies outside
+// the plan or in another bin stores the call's number into the head, and bin_eval_kernel answers NaN for the whole
+// call, as for a poisoned plan.  (A draw that moved WITHIN its bin gives what a rebuild would: the order of a stable
+// sort by bin does not change.)
+__global__ __launch_bounds__(kBlock) void bin_scatter_pack_kernel(SweepArgs a, BinSweepPtrs q) {
+    using M = Lorentz<1>;
+    using LB = LorentzBins;
+    static_assert(packed_width<M>() == 4, "the sorted records are 32 bytes");
+    if (sweep_aborted(a.abort)) return;
+    if (bin_keep_refused(q)) return;
+    const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    if (nbins <= 0 || nbins > LB::kMaxBins) return;
+    const double origin = q.plan->origin;
+    const double* __restrict__ thbar = a.moments + 2;
+    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < a.nd; p += (int64_t)gridDim.x * kBlock) {
+        double pk[4];
+        const double w = a.weights[p];
+        const double sw = sqrt(w);
+        M::pack(ParamRef{a.particles + p, a.ld_p}, thbar, a.m, sw, pk);
+        pk[M::NPK] = sw;
+        const int pos = q.dest[p];
+        const double t = (pk[0] - origin) * (1.0 / LB::kWidth);      // (bin_of's expression; a NaN fails the test)
+        bool ok = t >= 0.0 && t < (double)nbins && pos >= 0 && pos < a.nd;
+        if (ok) {
+            const int b = LB::bin_of(origin, pk[0], nbins);
+            ok = q.binstart[b] <= pos && pos < q.binstart[b + 1];
+        }
+        if (ok) {
+            double2* __restrict__ out = reinterpret_cast<double2*>(q.sorted) + 2 * (int64_t)pos;
+            out[0] = double2{pk[0], pk[1]};
+            out[1] = double2{pk[2], pk[3]};
+        } else {
+            q.keep->mismatch = q.call;
+        }
     }
 }
 
@@ -899,6 +991,7 @@ __global__ __launch_bounds__(kBlock) void bin_scan_kernel(int nunits, BinSweepPt
 __global__ __launch_bounds__(kWave) void bin_moments_kernel(BinSweepPtrs q, const unsigned* abort) {
     using LB = LorentzBins;
     if (sweep_aborted(abort)) return;
+    if (bin_keep_refused(q)) return;
     const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
     if (nbins == 0) return;
     const int lane = threadIdx.x, item = blockIdx.x;
@@ -945,6 +1038,7 @@ __global__ __launch_bounds__(kBinFoldGroups * kWave) void bin_fold_kernel(BinSwe
     using LB = LorentzBins;
     __shared__ double acc[kBinFoldGroups][kWave];
     if (sweep_aborted(abort)) return;
+    if (bin_keep_refused(q)) return;
     const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
     const int bin = blockIdx.x >> 1, co = (blockIdx.x & 1) * kWave + (threadIdx.x & (kWave - 1));
     if (bin >= nbins) return;
@@ -968,7 +1062,9 @@ __global__ __launch_bounds__(kBlock) void bin_eval_kernel(SweepArgs a, BinSweepP
     __shared__ int occupied[kBinTile];
     if (sweep_aborted(a.abort)) return;
     const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    // (a reuse whose keep buffer does not fit the call, or one of whose draws has left its kept bin: as if poisoned)
+    const bool refused = bin_keep_refused(q) || (q.reuse && q.keep->mismatch == q.call);
+    const int nbins = refused ? 0 : __builtin_amdgcn_readfirstlane(q.plan->nbins);
     double S1 = __builtin_nan(""), S2 = __builtin_nan("");        // poisoned: kappa = NaN, the caller repeats without the bit
     if (nbins > 0) {
         double tau;
@@ -1665,6 +1761,7 @@ struct BinSweep {
 #endif
     unsigned* ran = nullptr;       // bin_eval_kernel's marker
     unsigned seq = 0;
+    bool reuse = false;            // OBE_SWEEP_BINS_KEPT honoured: the grouping comes from the caller's keep buffer
     BinUnits units{};
     int64_t items = 0;             // items bin_moments_kernel is launched for: at least as many as any cloud makes
 };
@@ -1677,20 +1774,23 @@ static bool bin_form_selected(const obe_model& m, int flags, int64_t ns, const i
 
 #ifndef OBE_PLUGIN_MODEL_HEADER
 // once per call, behind the pack: the draws grouped by bin and the bins' folded rows (they depend on the cloud alone)
+// (a reuse has the grouping already: bin_scatter_pack_kernel has put the records where it says)
 static int launch_bin_plan(const SweepArgs& a, const BinSweep& b, hipStream_t st) {
     using LB = LorentzBins;
-    const int mm_blocks = static_cast<int>(std::min<int64_t>(kBinMinmaxBlocks, (a.nd + kBlock - 1) / kBlock));
-    bin_minmax_kernel<<<mm_blocks, kBlock, 0, st>>>(a, b.q.minmax);
-    OBE_CHECK_LAUNCH("bin_minmax_kernel");
-    bin_plan_kernel<<<1, kBinMinmaxBlocks, 0, st>>>(a, b.q.minmax, mm_blocks, b.q.plan);
-    OBE_CHECK_LAUNCH("bin_plan_kernel");
-    const unsigned group_blocks = (unsigned)((b.units.nunits + kBlock / kWave - 1) / (kBlock / kWave));
-    bin_group_kernel<false><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, b.q);
-    OBE_CHECK_LAUNCH("bin_group_kernel<count>");
-    bin_scan_kernel<<<LB::kMaxBins, kBlock, 0, st>>>(b.units.nunits, b.q, a.abort);
-    OBE_CHECK_LAUNCH("bin_scan_kernel");
-    bin_group_kernel<true><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, b.q);
-    OBE_CHECK_LAUNCH("bin_group_kernel<scatter>");
+    if (!b.reuse) {
+        const int mm_blocks = static_cast<int>(std::min<int64_t>(kBinMinmaxBlocks, (a.nd + kBlock - 1) / kBlock));
+        bin_minmax_kernel<<<mm_blocks, kBlock, 0, st>>>(a, b.q.minmax);
+        OBE_CHECK_LAUNCH("bin_minmax_kernel");
+        bin_plan_kernel<<<1, kBinMinmaxBlocks, 0, st>>>(a, b.q.minmax, mm_blocks, b.q.plan, b.q.keep);
+        OBE_CHECK_LAUNCH("bin_plan_kernel");
+        const unsigned group_blocks = (unsigned)((b.units.nunits + kBlock / kWave - 1) / (kBlock / kWave));
+        bin_group_kernel<false><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, b.q);
+        OBE_CHECK_LAUNCH("bin_group_kernel<count>");
+        bin_scan_kernel<<<LB::kMaxBins, kBlock, 0, st>>>(b.units.nunits, b.q, a.abort);
+        OBE_CHECK_LAUNCH("bin_scan_kernel");
+        bin_group_kernel<true><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, b.q);
+        OBE_CHECK_LAUNCH("bin_group_kernel<scatter>");
+    }
     bin_moments_kernel<<<(unsigned)b.items, kWave, 0, st>>>(b.q, a.abort);
     OBE_CHECK_LAUNCH("bin_moments_kernel");
     bin_fold_kernel<<<2 * LB::kMaxBins, kBinFoldGroups * kWave, 0, st>>>(b.q, a.abort);
@@ -1704,9 +1804,16 @@ static int launch_bin_sweep(SweepPlan& p, SweepArgs& a, const BinSweep& b, hipSt
     OBE_CHECK_LAUNCH("bin_eval_kernel");
     return 0;
 }
+// a reuse's pack: every draw's record straight to its kept sorted position
+static int launch_bin_scatter_pack(const SweepArgs& a, const BinSweep& b, hipStream_t st) {
+    bin_scatter_pack_kernel<<<stream_blocks(a.nd, kBlock), kBlock, 0, st>>>(a, b.q);
+    OBE_CHECK_LAUNCH("bin_scatter_pack_kernel");
+    return 0;
+}
 #else
 static int launch_bin_plan(const SweepArgs&, const BinSweep&, hipStream_t) { return 0; }
 static int launch_bin_sweep(SweepPlan&, SweepArgs&, const BinSweep&, hipStream_t) { return 0; }
+static int launch_bin_scatter_pack(const SweepArgs&, const BinSweep&, hipStream_t) { return 0; }
 #endif
 
 #ifndef OBE_PLUGIN_MODEL_HEADER
@@ -1743,7 +1850,8 @@ static int prepare_sweep(const obe_model* m, obe_model& mm, const double* d_sett
                          const double* d_particles, int64_t ld_p, int64_t np, const double* d_weights,
                          const int64_t* d_draw_idx, int64_t n_draws, const double* d_moments, void* d_ws,
                          int64_t ws_bytes, SweepPlan& plan, SweepArgs& a, SweepWs& w, int64_t* ws_need = nullptr,
-                         int flags = 0, CellSweep* cells = nullptr, BinSweep* bins = nullptr) {
+                         int flags = 0, CellSweep* cells = nullptr, BinSweep* bins = nullptr, void* d_keep = nullptr,
+                         int64_t keep_bytes = 0) {
     if (!m || !d_settings || !d_particles || !d_moments || ns <= 0 || np <= 0) return bad_arg("sweep: bad pointer/size");
     if (!d_draw_idx && !d_weights) return bad_arg("sweep: full mode needs weights");
     mm = *m;
@@ -1797,6 +1905,22 @@ static int prepare_sweep(const obe_model* m, obe_model& mm, const double* d_sett
             q.sorted = base + BL::sorted(nd);
             bins->units = plan_bin_units(nd);
             bins->items = bin_max_items(nd);
+            // a keep buffer of the caller's (full sweeps only: draws are drawn anew for every call), large enough
+            // for these draws: the plan and the two tables live there, and OBE_SWEEP_BINS_KEPT is honoured
+            if (d_keep && !d_draw_idx && keep_bytes >= BinKeepLayout::bytes(nd)) {
+                static std::atomic<unsigned> calls{0};
+                int* ints = static_cast<int*>(d_keep);
+                q.keep = static_cast<BinKeep*>(d_keep);
+                q.plan = &q.keep->plan;
+                q.binstart = ints + BinKeepLayout::kStarts;
+                q.itemstart = q.binstart + LorentzBins::kMaxBins + 2;
+                q.dest = ints + BinKeepLayout::kDest;
+                q.reuse = bins->reuse = (flags & OBE_SWEEP_BINS_KEPT) != 0;
+                q.keep_nd = static_cast<int>(nd);
+                memcpy(&q.keep_dbits, &mm.consts[0], sizeof q.keep_dbits);
+                q.call = ++calls;
+                if (q.call == 0u) q.call = ++calls;
+            }
         }
 #endif
     }
@@ -1890,13 +2014,17 @@ int64_t obe_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_c
     return b + 64 * (int64_t)sizeof(double);
 }
 
-int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
-                      const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
-                      const int64_t* d_draw_idx, int64_t n_draws, const double* d_moments, int32_t shifted,
-                      const double* d_noise_var, int64_t noise_ld, const double* d_cost, double cost_scalar,
-                      double* d_yvar, double* d_utility, double* h_best, int64_t* h_best_idx, double* h_kappa,
-                      void* d_ws, int64_t ws_bytes, void* stream) {
+int64_t obe_sweep_bins_keep_bytes(int64_t n_draws) { return BinKeepLayout::bytes(n_draws < 1 ? 1 : n_draws); }
+
+// obe_sweep_utility (d_keep = NULL) and obe_sweep_utility_keep
+static int sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                         const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                         const int64_t* d_draw_idx, int64_t n_draws, const double* d_moments, int32_t shifted,
+                         const double* d_noise_var, int64_t noise_ld, const double* d_cost, double cost_scalar,
+                         double* d_yvar, double* d_utility, double* h_best, int64_t* h_best_idx, double* h_kappa,
+                         void* d_ws, int64_t ws_bytes, void* stream, void* d_keep, int64_t keep_bytes) {
     if (!d_noise_var || !d_yvar || !d_utility) return bad_arg("obe_sweep_utility: bad output/noise pointer");
+    if (d_keep && reinterpret_cast<uintptr_t>(d_keep) % 16) return bad_arg("obe_sweep_utility_keep: d_keep is not 16-byte aligned");
     obe_model mm;
     SweepPlan plan;
     SweepArgs a{};
@@ -1906,7 +2034,7 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     BinSweep bins;
     if (int rc = prepare_sweep(m, mm, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles, d_weights,
                                d_draw_idx, n_draws, d_moments, d_ws, ws_bytes, plan, a, w, &sweep_ws_need, shifted, &cells,
-                               &bins))
+                               &bins, d_keep, keep_bytes))
         return rc;
     hipStream_t st = as_stream(stream);
     UtilArgs ua;
@@ -1959,7 +2087,8 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
         }
     }
     int rc = dispatch_model(mm, [&](auto M) -> int {
-        if (int e = launch_pack<decltype(M)>(a, st)) return e;
+        // (a reuse of a kept grouping packs every draw straight to its sorted position; nothing reads the plain copy)
+        if (int e = bins.on && bins.reuse ? launch_bin_scatter_pack(a, bins, st) : launch_pack<decltype(M)>(a, st)) return e;
         if (cells.on || bins.on) {
             const unsigned seq = timed && nowait ? (++g_timing.seq ? g_timing.seq : ++g_timing.seq) : 0u;      // (never 0)
             cells.seq = bins.seq = seq;
@@ -2011,6 +2140,28 @@ int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s
     return rc;
 }
 
+int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                      const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                      const int64_t* d_draw_idx, int64_t n_draws, const double* d_moments, int32_t shifted,
+                      const double* d_noise_var, int64_t noise_ld, const double* d_cost, double cost_scalar,
+                      double* d_yvar, double* d_utility, double* h_best, int64_t* h_best_idx, double* h_kappa,
+                      void* d_ws, int64_t ws_bytes, void* stream) {
+    return sweep_utility(m, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles, d_weights, d_draw_idx, n_draws,
+                         d_moments, shifted, d_noise_var, noise_ld, d_cost, cost_scalar, d_yvar, d_utility, h_best,
+                         h_best_idx, h_kappa, d_ws, ws_bytes, stream, nullptr, 0);
+}
+
+int obe_sweep_utility_keep(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                           const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                           const int64_t* d_draw_idx, int64_t n_draws, const double* d_moments, int32_t shifted,
+                           const double* d_noise_var, int64_t noise_ld, const double* d_cost, double cost_scalar,
+                           double* d_yvar, double* d_utility, double* h_value, int64_t* h_index, double* h_factor,
+                           void* d_ws, int64_t ws_bytes, void* stream, void* d_keep, int64_t keep_bytes) {
+    return sweep_utility(m, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles, d_weights, d_draw_idx, n_draws,
+                         d_moments, shifted, d_noise_var, noise_ld, d_cost, cost_scalar, d_yvar, d_utility, h_value,
+                         h_index, h_factor, d_ws, ws_bytes, stream, d_keep, keep_bytes);
+}
+
 int obe_sweep_timing(int32_t enable, double* h_total_ms, int64_t* h_launches) {
     resolve_pending_timing();
     if (h_total_ms) *h_total_ms = g_timing.total_ms;
@@ -2042,7 +2193,8 @@ int obe_sweep_kernel_time(const obe_model* m, const double* d_settings, int64_t 
     OBE_HIP_TRY(hipEventCreate(&e0));
     OBE_HIP_TRY(hipEventCreate(&e1));
     auto sweep_once = [&]() -> int {
-        // (the bins are a function of the cloud, and a new cloud means a new sweep: the whole pipeline is the sweep)
+        // (the bins are a function of the cloud, and a new cloud means a new sweep: the whole pipeline is the sweep —
+        // the rebuild's, whatever a caller of obe_sweep_utility_keep may have kept)
         if (bins.on) {
             if (int e = launch_bin_plan(a, bins, st)) return e;
             return launch_bin_sweep(plan, a, bins, st);

@@ -150,7 +150,8 @@ class OptBayesExpt(ParticlePDF):
         ``_speculation_wanted``): the same results, one host round trip per cycle less.
     ``tuning_parameters['sweep_shift']`` (``'auto'``, ``'always'``, ``'never'``), ``['sweep_cells']`` (``'auto'``,
     ``'always'``, ``'never'``: the one-peak Lorentzian's unshifted sweep by cell expansions), ``['sweep_bins']`` (the
-    same values: that sweep by bin expansions of the particles), ``['fused_moments']``,
+    same values: that sweep by bin expansions of the particles), ``['sweep_bins_keep']`` (default True: the bins'
+    grouping of the cloud is kept from sweep to sweep until the particles change), ``['fused_moments']``,
     ``['replica_check_every']``
         see ``_sweep_device``, ``pdf_update``, ``check_replicas``.
     """
@@ -812,6 +813,7 @@ class OptBayesExpt(ParticlePDF):
         return dict(cloud=(self._particles.version, self._weights.version), shifted=bool(shifted),
                     cells=bool(not shifted and self._cell_form_wanted()),
                     bins=bool(not shifted and self._bin_form_wanted()),
+                    kept=self._bins_kept_input(bool(not shifted and self._bin_form_wanted())),
                     noise=self._noise_token(), settings=(self._s_begin, self._s_end),
                     alias=self._parameters is self._particles,
                     cost_hook=_overridden(self, "cost_estimate", OptBayesExpt))
@@ -1099,6 +1101,13 @@ class OptBayesExpt(ParticlePDF):
         def launch(shifted, safe=False, speculative=False):
             result["bins"] = bins_for(shifted, safe)
             result["cells"] = cells_for(shifted, safe) and not result["bins"]
+            # the bins' grouping of the cloud, kept in a buffer of this object's own from one sweep to the next
+            # (include/obe_hip.h: obe_sweep_utility_keep): reused while the key says it was made for these particles
+            keep = self._bins_keep_buffer() if result["bins"] else None
+            result["kept"] = keep is not None and self._bins_kept()
+            result["keep"] = keep is not None
+            if keep is not None and not result["kept"]:
+                self._bins_kept_for = None          # (being rebuilt: nothing to rely on until this sweep is collected)
             # sharded: no host read here — the 32-byte result record is all-gathered from
             # device memory and read back once, together with the other ranks' records
             p, w = self._pw_tensors()
@@ -1109,12 +1118,13 @@ class OptBayesExpt(ParticlePDF):
             mom = self._moments_on_device()
             no_host = sharded or lazy
             stream = self._stream()
-            self._mlib.call("obe_sweep_utility", self._model_struct, s_ptr, self._n_settings, n_local,
+            self._mlib.call("obe_sweep_utility_keep", self._model_struct, s_ptr, self._n_settings, n_local,
                            _ptr(p), p.shape[1], self.n_particles, _ptr(w),
                            None if idx is None else _ptr(idx), n_draws, _ptr(mom),
                            (_lib.OBE_SWEEP_SHIFTED if shifted else 0) | (_lib.OBE_SWEEP_SAFE if safe else 0)
                            | (_lib.OBE_SWEEP_CELLS if cells_for(shifted, safe) else 0)
                            | (_lib.OBE_SWEEP_BINS if result["bins"] else 0)
+                           | (_lib.OBE_SWEEP_BINS_KEPT if result["kept"] else 0)
                            | (0 if not speculative else _lib.OBE_SWEEP_NOWAIT if speculative == "after_resample"
                               else _lib.OBE_SWEEP_SPECULATIVE),
                            _ptr(noise), noise_ld, None if cost_t is None else _ptr(cost_t), cost_s,
@@ -1122,7 +1132,8 @@ class OptBayesExpt(ParticlePDF):
                            None if no_host else p_best,
                            None if no_host else p_best_idx,
                            None if no_host else p_kappa,
-                           _ptr(self._ws), self._ws_bytes, stream)
+                           _ptr(self._ws), self._ws_bytes, stream,
+                           None if keep is None else _ptr(keep), 0 if keep is None else keep.numel() * 4)
             if speculative:
                 # (waited for on the stream it was launched on; the sweep of a resampled cloud has nothing to guess)
                 state.enqueued(Ticket(self._sweep_inputs(shifted), None if sharded else p_best, block,
@@ -1160,7 +1171,8 @@ class OptBayesExpt(ParticlePDF):
         form = state.form_for_next_sweep()
         if lazy:
             launch(True)
-            self.last_sweep = dict(shifted=True, kappa=float("nan"), safe=False, cells=False, bins=False)     # kappa was not read back
+            self.last_sweep = dict(shifted=True, kappa=float("nan"), safe=False, cells=False, bins=False,
+                                   kept=False)     # kappa was not read back
             return None
         if form is Form.FAST:
             taken = self._take_speculative_sweep(shifted) if full else None
@@ -1169,8 +1181,19 @@ class OptBayesExpt(ParticlePDF):
             else:
                 result["bins"] = bins_for(shifted)         # (part of the ticket's inputs: what was enqueued ahead)
                 result["cells"] = cells_for(shifted) and not result["bins"]
+                # (the buffer the enqueued call was given, if any: none is made here)
+                result["keep"] = result["bins"] and "_bins_keep" in self.__dict__ and self._bins_kept_input(True) is not None
+                result["kept"] = result["keep"] and self._bins_kept()
                 deliver(taken if sharded else None)
             self._check_pending_total()
+            if result["kept"] and np.isnan(kappa[0]):
+                # the kept grouping did not fit the cloud after all (the kernels check it themselves): forgotten, and
+                # this sweep is repeated as a rebuild — only a NaN from that one says that the cloud does not fit the bins
+                self._bins_kept_for = None
+                launch(shifted)
+                self._check_pending_total()
+            if result["bins"] and result["keep"] and np.isfinite(kappa[0]):
+                self._bins_kept_for = self._bins_keep_key()       # (collected: the buffer describes these particles)
             if result["bins"] and np.isnan(kappa[0]):
                 # the cloud does not fit the bins (its x0 / d span more than OBE_BIN_MAX of them, or one is not
                 # finite): that is a property of the particles alone, so nothing asks for bins again before the
@@ -1201,7 +1224,7 @@ class OptBayesExpt(ParticlePDF):
             launch(True, safe=True)
             self._check_pending_total()
         self.last_sweep = dict(shifted=shifted, kappa=float(kappa[0]), safe=safe, cells=bool(result["cells"]),
-                               bins=bool(result["bins"]))
+                               bins=bool(result["bins"]), kept=bool(result["bins"] and result["kept"]))
         if want_best:
             return result["best"]
         return None
@@ -1253,6 +1276,36 @@ class OptBayesExpt(ParticlePDF):
             plan = self._bins_plan = (key, int(self._mlib.cdll.obe_sweep_bins_plan(
                 lo, hi, float(self.cons[0]), n, self.n_particles)))
         return bool(plan[1] & 1) and (mode == "always" or bool(plan[1] & 2))
+
+    def _bins_keep_key(self):
+        """What the bins' grouping of the cloud depends on: the particle values (their version stamp never repeats:
+        a resample, set_pdf or a write to ``particles`` makes a new one), the width constant and the count."""
+        return (self._particles.version, float(self.cons[0]), self.n_particles)
+
+    def _bins_kept(self):
+        """Whether the keep buffer holds the grouping of exactly this cloud: set by the last bin sweep that was
+        collected with a finite kappa, never by one that was only enqueued."""
+        return self.__dict__.get("_bins_kept_for") == self._bins_keep_key()
+
+    def _bins_kept_input(self, bins):
+        """How a full sweep of this object uses the keep buffer, as one of the sweep's inputs: False — it (re)builds
+        the grouping, True — it reuses it, None — no buffer is passed at all."""
+        if not bins or not self.tuning_parameters.get("sweep_bins_keep", True):
+            return None
+        return self._bins_kept()
+
+    def _bins_keep_buffer(self):
+        """This object's keep buffer (one per rank of a sharded object; a copy or a restored object starts without
+        one and rebuilds on its first sweep), or None with ``tuning_parameters['sweep_bins_keep']`` False."""
+        if not self.tuning_parameters.get("sweep_bins_keep", True):
+            return None
+        keep = self.__dict__.get("_bins_keep")
+        if keep is None or keep[0] != self.n_particles:
+            nbytes = int(self._mlib.cdll.obe_sweep_bins_keep_bytes(self.n_particles))
+            keep = self._bins_keep = (self.n_particles,
+                                      torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self._device))
+            self._bins_kept_for = None
+        return keep[1]
 
     def _settings_per_lane(self, n_draws=0):
         """Settings one lane of the sweep kernel owns on a slice of this job: at most (n_draws = 0, what a full
