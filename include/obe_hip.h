@@ -789,6 +789,41 @@ OBE_API int obe_predictive_tails(const obe_model* m, const double* d_settings, i
                          int64_t n_particles, const double* d_weights, double* d_lower, double* d_upper,
                          void* d_ws, int64_t ws_bytes, void* stream);
 
+/* ---- posterior predictive of a measurement, inverted: quantiles of the NEXT READING (extension) ----
+ * Where will the next reading fall?  The band to draw against measured points, an outlier threshold fixed before the
+ * reading is taken, the range to set on an instrument: the inverse of obe_predictive_tails.  For a setting point x (a
+ * column of d_settings), a channel c and a level q in (0, 1), with f = what obe_eval_over_particles writes, bit for bit:
+ * a particle CONTRIBUTES to channel c with a weight > 0 (NaN and negative weights count as zero), every noise row of it
+ * > 0 (h_noise_rows only) and a finite f_c — a stated deviation from the tails above, where +-inf counts as mass at
+ * infinity: a reading cannot be infinite, and an infinite component would make the bracket infinite.  With T_c = sum w,
+ * L_c(y) = sum w Phi((y - f_c) / sigma_c) and U_c(y) = sum w Phi((f_c - y) / sigma_c) over the contributing particles,
+ * each a sum of positive terms formed as obe_predictive_tails forms them, the result is the y with L_c(y) = q T_c
+ * (q <= 1/2) or U_c(y) = (1 - q) T_c (q > 1/2; 1 - q is exact there, so a far upper tail keeps its relative accuracy).
+ * T_c == 0 (nobody contributes, sum w == 0 included) gives NaN.  The noise: exactly one of d_sigma (C, n_settings) with
+ * row stride ld_sigma, known, finite and > 0 (a setting with another value gets NaN in every channel), and h_noise_rows
+ * (C rows of the cloud).  The band is per channel, not joint; no choke.
+ * h_q, h_z (n_q,), 1..16 levels: h_z[j] = the standard normal quantile of h_q[j], which the CALLER computes (finite; an
+ * error of 1e-9 (1 + |z|) in it costs nothing but passes: it only places the first bracket).
+ * Geometry of obe_predictive_tails (lane = setting, the particles of a chunk one after the other, setting tiles x
+ * particle chunks, partials folded in chunk order, no atomics: the same bits from run to run).  One bracket pass over
+ * the cloud (per level the min / max of f + (z -+ 1e-9 (1 + |z|)) sigma: a guaranteed bracket), then max_passes (1..64)
+ * pairs of an iteration pass — at every open row's trial y the tail A and the density mass D = sum w phi(z) / sigma —
+ * and a step kernel: Newton's method on log A, y -+ (A / D) log(A / target), safeguarded by the bracket (its midpoint
+ * when the Newton point leaves the open bracket, is not finite, or the step exceeds half the previous one; a Newton
+ * step below the resolution of y is taken as two ulp of y, so that the far end of the bracket comes in).  A row
+ * closes when |A - target| <= 2^-36 target, or when its bracket is <= 4 ulp of its larger end (then at the midpoint).
+ * Workgroups of a pass whose setting tile has no open row return at once; the whole budget is enqueued and NOTHING IS
+ * WAITED FOR: d_quantiles (n_q, C, n_settings) and d_passes (n_q, C, n_settings; the passes a row used, >= 1; 0 for a
+ * NaN row; -max_passes for a row still open at the end, which delivers its bracket's midpoint) land in the caller's
+ * DEVICE buffers.  d_ws: obe_predictive_reading_workspace_bytes(n_particles, n_settings, the model's channels, n_q)
+ * bytes, a buffer of its own; the size does not shrink when an argument grows. */
+OBE_API int64_t obe_predictive_reading_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels, int32_t n_q);
+OBE_API int obe_predictive_reading_quantiles(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                                     const double* d_sigma, int64_t ld_sigma, const int32_t* h_noise_rows,
+                                     const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                                     const double* h_q, const double* h_z, int32_t n_q, int32_t max_passes,
+                                     double* d_quantiles, int32_t* d_passes, void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---- design for parameters of interest: output-parameter covariance and the variance a reading removes (extension) ----
  * Every utility of the reference scores a setting by how much the model output varies there, for any reason
  * (obe_base.py:579-720: sum_c var_p / var_n); a user who wants ONE parameter and treats the others as nuisances needs

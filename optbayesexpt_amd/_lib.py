@@ -139,6 +139,7 @@ MODEL_ENTRY_POINTS = ("obe_model_validate", "obe_workspace_bytes", "obe_sweep_se
                       "obe_eval_draws",
                       "obe_predictive_workspace_bytes", "obe_predictive_moments", "obe_predictive_quantiles",
                       "obe_predictive_score_workspace_bytes", "obe_predictive_logpdf", "obe_predictive_tails",
+                      "obe_predictive_reading_workspace_bytes", "obe_predictive_reading_quantiles",
                       "obe_output_covariance_workspace_bytes", "obe_output_covariance",
                       "obe_records_loglik_workspace_bytes", "obe_records_loglik",
                       "obe_output_cross_covariance_workspace_bytes", "obe_output_cross_covariance")

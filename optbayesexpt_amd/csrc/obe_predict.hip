@@ -15,7 +15,9 @@
 //              loading it was built and measured: slower at both benchmark clouds)
 // K11 — scoring a measurement against the posterior predictive (further down): the log-density of readings and their
 // per-channel tail probabilities, noise included.  The geometry of the moments with lane <-> record.
-// K12 — design for parameters of interest (below K11): per setting the covariance of the model output with itself (S)
+// K15 — quantiles of the next READING (below K11): the inverse of K11's tails.  A bracket pass over the cloud, then a fixed
+// budget of (iteration pass, step kernel) pairs: safeguarded Newton on the log of the tail, K11's geometry throughout.
+// K12 — design for parameters of interest (below K15): per setting the covariance of the model output with itself (S)
 // and with up to eight selected parameter rows (K), for obe_variance_reduction (obe_interest.hip).  The moments' two
 // passes and geometry; the second pass carries C (C + 1) / 2 + R C centred products per evaluation instead of C squares.
 // K14 — design of a batch of measurements (below K13a): the covariance of the model output at every setting with the
@@ -340,7 +342,327 @@ __global__ __launch_bounds__(kBlock) void score_tails_fold_kernel(const double* 
     }
 }
 
-// What the two scoring entry points share: everything that can refuse the call, then the launch geometry.
+// ---- K15: quantiles of the next reading, the inverse of the tails above.  For a setting, a channel c and a level q the
+// y with L_c(y) = q T_c (q <= 1/2) or U_c(y) = (1 - q) T_c (q > 1/2): L, U the tails as score_tails_kernel forms them,
+// T_c = sum w over the particles that contribute to the channel — weight > 0, ROWS: every noise row > 0, f_c finite (a
+// stated deviation from the tails, where +-inf counts as mass at infinity: a reading cannot be infinite).  K11's
+// geometry: lane = one setting, the chunk's particles one after the other, grid = setting tiles x particle chunks x level
+// groups; a group is as many levels as fit kReadSlots (trial, tail, density) triples per lane with the model's channels.
+//   bracket   one pass: T_c and per level the min / max over the contributing particles of f + z^-+ sigma, z^-+ the
+//             level's normal quantile widened by a hair (ReadLevels): at the lower end every term of the tail is <= its
+//             target, at the upper end >=, so the pair brackets the root.
+//   pass      at the trial y of every open row A = L or U (the one its level solves in) and D = sum w phi(z) / sigma.
+//   step      folds the chunk partials in chunk order and moves the trial by Newton's method on log A, safeguarded by the
+//             bracket (midpoint when the Newton point leaves the open bracket, is not finite, or the step exceeds half
+//             the previous one); keeps the number of open rows per (group, setting tile), which the next pass's
+//             workgroups read before anything else.
+// No atomics: the same bits from run to run.
+constexpr int kReadWaves = 4096;                   // waves a pass aims at per level group
+constexpr int kReadSlots = 8;                      // (trial, A, D) triples a lane holds
+constexpr double kInvSqrt2Pi = 0.39894228040143267794;
+constexpr double kReadClose = 0x1p-36;             // a row closes at |A - target| <= this x target ...
+constexpr double kReadUlps = 4.0;                  // ... or when its bracket is no wider than this many ulp of its larger end
+constexpr double kReadHair = 1e-9;                 // z -+ kReadHair (1 + |z|): an inexact inverse normal CDF keeps the root
+
+inline int read_group_of(int n_channels) { return n_channels < kReadSlots ? kReadSlots / n_channels : 1; }
+inline int read_chunks(int64_t n_particles, int64_t n_settings) {
+    const int64_t by_size = (n_particles + kMomentMinChunk - 1) / kMomentMinChunk;
+    const int64_t by_grid = std::max<int64_t>(1, kReadWaves / setting_tiles(n_settings));
+    return (int)std::max<int64_t>(1, std::min(by_size, by_grid));
+}
+
+// the levels of a call, by value in the kernel arguments
+struct ReadLevels {
+    int n;
+    int upper[kMaxQ];                              // the level solves in U (q > 1/2)
+    double frac[kMaxQ];                            // target / T: q or 1 - q
+    double z_lo[kMaxQ], z_hi[kMaxQ];
+};
+
+// row = level * C + channel; every array (rows, padded settings) but tile_open (groups, setting tiles)
+struct ReadState {
+    double *lo, *hi, *trial, *step, *target;
+    int32_t* open;
+    int32_t* tile_open;
+    double* partials;
+};
+// the state, then the chunk partials of the wider pass (the bracket's C (1 + 2 n_q) slots): chunks x padded settings <=
+// (kReadWaves + setting tiles) x 64, whatever the cloud
+inline int64_t read_words(int64_t n_settings, int n_channels, int n_q) {
+    const int64_t tiles = setting_tiles(n_settings), cells = (int64_t)n_q * n_channels * tiles * kWave;
+    return 5 * cells + (cells + 1) / 2 + (n_q * tiles + 1) / 2
+           + ((int64_t)kReadWaves + tiles) * kWave * n_channels * (1 + 2 * n_q);
+}
+inline ReadState read_carve(u64* body, int64_t n_settings, int n_channels, int n_q) {
+    const int64_t tiles = setting_tiles(n_settings), cells = (int64_t)n_q * n_channels * tiles * kWave;
+    double* d = reinterpret_cast<double*>(body);
+    ReadState st;
+    st.lo = d, st.hi = d + cells, st.trial = d + 2 * cells, st.step = d + 3 * cells, st.target = d + 4 * cells;
+    st.open = reinterpret_cast<int32_t*>(d + 5 * cells);
+    st.tile_open = reinterpret_cast<int32_t*>(d + 5 * cells + (cells + 1) / 2);
+    st.partials = d + 5 * cells + (cells + 1) / 2 + (n_q * tiles + 1) / 2;
+    return st;
+}
+
+// the sigma of the lane's setting (known sigma); false: one of them is not finite and > 0
+template <class M>
+__device__ __forceinline__ bool load_sigma(int64_t sc, const double* __restrict__ sigma, int64_t ld_sg, double* sg, double* inv) {
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        sg[c] = sigma[(int64_t)c * ld_sg + sc];
+        ok = ok && sg[c] > 0.0 && sg[c] < kInf;
+        inv[c] = 1.0 / sg[c];
+    }
+    return ok;
+}
+
+// the open rows of this workgroup's block: what the threads of one (64, rows of a group) workgroup found, counted wave
+// by wave in thread order
+__device__ __forceinline__ int count_open_rows(bool open, int* cnt) {
+    const int n = __popcll(__ballot(open));
+    if (threadIdx.x == 0) cnt[threadIdx.y] = n;
+    __syncthreads();
+    int total = 0;
+    for (int k = 0; k < (int)blockDim.y; ++k) total += cnt[k];
+    return total;
+}
+
+// partials (chunk, C (1 + 2 n_q), padded settings): T_c, then per (level, channel) the min of f + z_lo sigma and the max
+// of f + z_hi sigma.  T_c is written by the first level group.
+template <class M, bool ROWS>
+__global__ __launch_bounds__(kWave) void reading_bracket_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                                int64_t n_s, const double* __restrict__ sigma, int64_t ld_sg,
+                                                                ScoreRows rows, const double* __restrict__ particles,
+                                                                int64_t ld_p, int64_t n, const double* __restrict__ w,
+                                                                int64_t chunk_len, ReadLevels lv,
+                                                                double* __restrict__ partials) {
+    constexpr int G = M::NC < kReadSlots ? kReadSlots / M::NC : 1;
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_s ? s : n_s - 1;                    // (the padding lanes repeat the last setting)
+    const int j0 = blockIdx.z * G;
+    double x[M::NS], sg[M::NC], inv[M::NC], T[M::NC], mn[G][M::NC], mx[G][M::NC], zl[G], zh[G];
+#pragma unroll
+    for (int k = 0; k < M::NS; ++k) x[k] = settings[(int64_t)k * ld_s + sc];
+    bool rec_ok = true;
+    if (!ROWS) rec_ok = load_sigma<M>(sc, sigma, ld_sg, sg, inv);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const int j = j0 + g < lv.n ? j0 + g : lv.n - 1;         // (levels beyond the call's repeat the last: not written)
+        zl[g] = lv.z_lo[j];
+        zh[g] = lv.z_hi[j];
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) mn[g][c] = kInf, mx[g][c] = -kInf;
+    }
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) T[c] = 0.0;
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p] and the particle are the same for all lanes)
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        if (ROWS) {
+            bool ok = true;
+#pragma unroll
+            for (int c = 0; c < M::NC; ++c) {
+                sg[c] = particles[(int64_t)rows.row[c] * ld_p + p];
+                ok = ok && sg[c] > 0.0;
+            }
+            if (!ok) continue;
+        }
+        double y[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            if (rec_ok && fabs(y[c]) < kInf) {                   // (NaN fails)
+                T[c] += wp;
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    mn[g][c] = fmin(mn[g][c], y[c] + zl[g] * sg[c]);
+                    mx[g][c] = fmax(mx[g][c], y[c] + zh[g] * sg[c]);
+                }
+            }
+        }
+    }
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+    double* out = partials + (int64_t)blockIdx.y * (M::NC * (1 + 2 * lv.n)) * n_pad + s;
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        if (blockIdx.z == 0) out[c * n_pad] = T[c];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (j0 + g < lv.n) {
+                out[(M::NC + ((j0 + g) * M::NC + c) * 2) * n_pad] = mn[g][c];
+                out[(M::NC + ((j0 + g) * M::NC + c) * 2 + 1) * n_pad] = mx[g][c];
+            }
+        }
+    }
+}
+
+// The state of every row from the bracket's partials, folded in chunk order; workgroup (64 settings, the rows of a level
+// group), grid (setting tiles, groups).  T_c == 0: NaN, 0 passes, never open.
+__global__ void reading_init_kernel(int chunks, int n_channels, int group, ReadLevels lv, int64_t n_pad, int64_t n_s,
+                                    ReadState st, double* __restrict__ out, int32_t* __restrict__ passes) {
+    __shared__ int cnt[kReadSlots];
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int j = blockIdx.y * group + threadIdx.y / n_channels, c = threadIdx.y % n_channels;
+    bool open = false;
+    if (j < lv.n) {
+        const int64_t slots = (int64_t)n_channels * (1 + 2 * lv.n), at = n_channels + (j * n_channels + c) * 2;
+        double T = 0.0, mn = kInf, mx = -kInf;
+        for (int k = 0; k < chunks; ++k) {
+            const double* part = st.partials + k * slots * n_pad + s;
+            T += part[c * n_pad];
+            mn = fmin(mn, part[at * n_pad]);
+            mx = fmax(mx, part[(at + 1) * n_pad]);
+        }
+        const int64_t row = (int64_t)j * n_channels + c, idx = row * n_pad + s;
+        if (s < n_s) {
+            if (T > 0.0) {
+                const double lo = nextafter(mn, -kInf), hi = nextafter(mx, kInf);      // (the sums f + z sigma are rounded)
+                st.lo[idx] = lo;
+                st.hi[idx] = hi;
+                st.trial[idx] = 0.5 * lo + 0.5 * hi;
+                st.step[idx] = hi - lo;
+                st.target[idx] = lv.frac[j] * T;
+                open = true;
+            } else {
+                out[row * n_s + s] = __builtin_nan("");
+                passes[row * n_s + s] = 0;
+            }
+        }
+        st.open[idx] = open;
+    }
+    const int total = count_open_rows(open, cnt);
+    if (threadIdx.x == 0 && threadIdx.y == 0) st.tile_open[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+// partials (chunk, n_q C, 2, padded settings): A and sqrt(2 pi) D of the open rows at their trials.  The model is
+// evaluated once per (setting, particle) and shared by the group's levels.  A workgroup whose tile has no open row in
+// its group returns at once: the count was written by the launch before.
+template <class M, bool ROWS>
+__global__ __launch_bounds__(kWave) void reading_pass_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                             int64_t n_s, const double* __restrict__ sigma, int64_t ld_sg,
+                                                             ScoreRows rows, const double* __restrict__ particles,
+                                                             int64_t ld_p, int64_t n, const double* __restrict__ w,
+                                                             int64_t chunk_len, ReadLevels lv, ReadState st) {
+    constexpr int G = M::NC < kReadSlots ? kReadSlots / M::NC : 1;
+    if (st.tile_open[(int64_t)blockIdx.z * gridDim.x + blockIdx.x] == 0) return;
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_s ? s : n_s - 1;                    // (the padding lanes repeat the last setting: never open)
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+    const int j0 = blockIdx.z * G;
+    double x[M::NS], sg[M::NC], inv[M::NC], yt[G][M::NC], A[G][M::NC], D[G][M::NC], unused;
+    bool open[G][M::NC], up[G];
+#pragma unroll
+    for (int k = 0; k < M::NS; ++k) x[k] = settings[(int64_t)k * ld_s + sc];
+    bool rec_ok = true;
+    if (!ROWS) rec_ok = load_sigma<M>(sc, sigma, ld_sg, sg, inv);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const bool live = j0 + g < lv.n;
+        up[g] = live && lv.upper[live ? j0 + g : 0] != 0;
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const int64_t idx = ((int64_t)(live ? j0 + g : 0) * M::NC + c) * n_pad + s;
+            open[g][c] = live && st.open[idx] != 0;
+            yt[g][c] = open[g][c] ? st.trial[idx] : 0.0;
+            A[g][c] = D[g][c] = 0.0;
+        }
+    }
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p] and the particle are the same for all lanes)
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        if (ROWS && !load_noise<M>(rows, particles, ld_p, p, inv, unused)) continue;
+        double y[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const bool fin = rec_ok && fabs(y[c]) < kInf;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (open[g][c] && fin) {
+                    const double z = (y[c] - yt[g][c]) * inv[c];          // > 0: the model lies above the trial
+                    const double small = 0.5 * erfc(fabs(z) * kSqrtHalf), large = 1.0 - small;
+                    A[g][c] += wp * ((z > 0.0) == up[g] ? large : small);
+                    D[g][c] += wp * (exp(-0.5 * (z * z)) * inv[c]);
+                }
+            }
+        }
+    }
+    double* out = st.partials + (int64_t)blockIdx.y * (2 * M::NC * lv.n) * n_pad + s;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            if (open[g][c]) {
+                out[(((j0 + g) * M::NC + c) * 2) * n_pad] = A[g][c];
+                out[(((j0 + g) * M::NC + c) * 2 + 1) * n_pad] = D[g][c];
+            }
+        }
+    }
+}
+
+// Between two passes: the open rows' A and D folded in chunk order, then the bracket shrunk by the sign of A - target
+// and the trial moved.  d_quantiles, d_passes (n_q, C, n_settings) are written when a row closes (passes = this pass)
+// and, pass == max_passes, for a row still open (its bracket's midpoint, -max_passes).  The workgroup of the init kernel.
+__global__ void reading_step_kernel(int chunks, int n_channels, int group, ReadLevels lv, int64_t n_pad, int64_t n_s,
+                                    ReadState st, int pass, int max_passes, double* __restrict__ out,
+                                    int32_t* __restrict__ passes) {
+    __shared__ int cnt[kReadSlots];
+    int32_t* word = st.tile_open + (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (*word == 0) return;                                      // (the whole workgroup: nothing of this tile is open)
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int j = blockIdx.y * group + threadIdx.y / n_channels, c = threadIdx.y % n_channels;
+    const int64_t row = (int64_t)j * n_channels + c, idx = row * n_pad + s;
+    bool open = j < lv.n && st.open[idx] != 0;
+    if (open) {
+        double A = 0.0, D = 0.0;
+        for (int k = 0; k < chunks; ++k) {
+            const double* part = st.partials + ((int64_t)k * (2 * n_channels * lv.n) + row * 2) * n_pad + s;
+            A += part[0];
+            D += part[n_pad];
+        }
+        D *= kInvSqrt2Pi;
+        const bool up = lv.upper[j] != 0;
+        const double y = st.trial[idx], target = st.target[idx];
+        double lo = st.lo[idx], hi = st.hi[idx], result = y;
+        bool done = fabs(A - target) <= kReadClose * target;
+        if (!done) {
+            if ((A > target) != up) hi = y;                      // L rises with y, U falls
+            else lo = y;
+            const double big = fmax(fabs(lo), fabs(hi)), mid = 0.5 * lo + 0.5 * hi;
+            result = mid;
+            done = hi - lo <= kReadUlps * (nextafter(big, kInf) - big);
+            if (!done) {
+                const double dy = (A / D) * log(A / target);     // Newton on log A: towards the root with the sign below
+                double move = up ? dy : -dy;
+                // a step below the resolution of y would leave the trial on the bracket's end it has just become, and
+                // the far end where it is: two ulp in Newton's direction instead, so that the far end comes in
+                const double ulp2 = 2.0 * (nextafter(fabs(y), kInf) - fabs(y));
+                if (fabs(move) < ulp2) move = copysign(ulp2, move);
+                double next = y + move;
+                if (!(next > lo && next < hi) || !(fabs(dy) <= 0.5 * st.step[idx])) next = mid;
+                st.lo[idx] = lo;
+                st.hi[idx] = hi;
+                st.step[idx] = fabs(next - y);
+                st.trial[idx] = next;
+            }
+        }
+        if (done || pass == max_passes) {
+            out[row * n_s + s] = result;
+            passes[row * n_s + s] = done ? pass : -max_passes;
+            st.open[idx] = 0;
+            open = false;
+        }
+    }
+    const int total = count_open_rows(open, cnt);
+    if (threadIdx.x == 0 && threadIdx.y == 0) *word = total;
+}
+
+// What the scoring entry points and K15 share: everything that can refuse the call, then the launch geometry.
 struct Score {
     obe_model mm;
     ScoreRows rows;
@@ -350,28 +672,30 @@ struct Score {
     int prepare(const char* who, const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
                 const double* d_y_meas, int64_t ld_y, const double* d_sigma, int64_t ld_sigma,
                 const int32_t* h_noise_rows, const double* d_particles, int64_t ld_p, int64_t n_particles,
-                const double* d_weights, void* d_ws, int64_t ws_bytes) {
+                const double* d_weights, void* d_ws, int64_t ws_bytes, int n_q = 0) {      // n_q > 0: K15, no y_meas
         static thread_local std::string msg;
         auto refuse = [&](const char* what) {
             msg = std::string(who) + ": " + what;
             return bad_arg(msg.c_str());
         };
-        if (!d_y_meas) return refuse("null pointer");
+        if (!d_y_meas && !n_q) return refuse("null pointer");
         if (int rc = check_inputs(who, m, d_settings, ld_s, n_records, d_particles, ld_p, n_particles, d_weights, d_ws))
             return rc;
         if ((d_sigma != nullptr) == (h_noise_rows != nullptr)) return refuse("exactly one of d_sigma and h_noise_rows");
-        if (ld_y < n_records || (d_sigma && ld_sigma < n_records)) return refuse("a row of y_meas or sigma shorter than n_records");
+        if ((!n_q && ld_y < n_records) || (d_sigma && ld_sigma < n_records))
+            return refuse("a row of y_meas or sigma shorter than n_records");
         mm = *m;
         if (int rc = obe_model_validate(&mm)) return rc;
         for (int c = 0; c < OBE_MAX_CHANNELS; ++c) {
             rows.row[c] = (h_noise_rows && c < mm.n_channels) ? h_noise_rows[c] : 0;
             if (rows.row[c] && (rows.row[c] < 0 || rows.row[c] >= mm.n_params)) return refuse("noise row index out of range");
         }
-        if (ws_bytes < obe_predictive_score_workspace_bytes(n_particles, n_records, mm.n_channels))
-            return refuse("workspace too small");
+        const int64_t need = n_q ? obe_predictive_reading_workspace_bytes(n_particles, n_records, mm.n_channels, n_q)
+                                 : obe_predictive_score_workspace_bytes(n_particles, n_records, mm.n_channels);
+        if (ws_bytes < need) return refuse("workspace too small");
         tiles = setting_tiles(n_records);
         if (tiles > 0x7fffffff) return refuse("too many records for one call");
-        const int chunks = moment_chunks(n_particles, n_records);
+        const int chunks = n_q ? read_chunks(n_particles, n_records) : moment_chunks(n_particles, n_records);
         chunk_len = ((n_particles + chunks - 1) / chunks + kWave - 1) / kWave * kWave;      // whole waves of particles
         used = (int)((n_particles + chunk_len - 1) / chunk_len);
         ws = carve(d_ws);
@@ -775,6 +1099,76 @@ int obe_predictive_tails(const obe_model* m, const double* d_settings, int64_t l
         score_tails_fold_kernel<<<(int)((n_records + kBlock - 1) / kBlock), kBlock, 0, st>>>(
             partials, sc.used, Model::NC, sc.tiles * kWave, n_records, sc.ws.hdr, d_lower, d_upper);
         OBE_CHECK_LAUNCH("score_tails_fold_kernel");
+        return 0;
+    });
+}
+
+int64_t obe_predictive_reading_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels, int32_t n_q) {
+    (void)n_particles;                                           // (the partials are per chunk: bounded whatever the cloud)
+    if (n_settings < 1) n_settings = 1;
+    n_channels = std::min(std::max(n_channels, 1), OBE_MAX_CHANNELS);
+    n_q = std::min(std::max(n_q, 1), kMaxQ);
+    return (kPredHeadWords + read_words(n_settings, n_channels, n_q)) * (int64_t)sizeof(u64);
+}
+
+int obe_predictive_reading_quantiles(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                                     const double* d_sigma, int64_t ld_sigma, const int32_t* h_noise_rows,
+                                     const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                                     const double* h_q, const double* h_z, int32_t n_q, int32_t max_passes,
+                                     double* d_quantiles, int32_t* d_passes, void* d_ws, int64_t ws_bytes, void* stream) {
+    const char* who = "obe_predictive_reading_quantiles";
+    if (!h_q || !h_z || !d_quantiles || !d_passes) return bad_arg("obe_predictive_reading_quantiles: null pointer");
+    if (n_q < 1 || n_q > kMaxQ) return bad_arg("obe_predictive_reading_quantiles: 1..16 levels per call");
+    if (max_passes < 1 || max_passes > 64) return bad_arg("obe_predictive_reading_quantiles: max_passes outside 1..64");
+    ReadLevels lv{};
+    lv.n = n_q;
+    for (int j = 0; j < n_q; ++j) {
+        const double q = h_q[j], z = h_z[j];
+        if (!(q > 0.0 && q < 1.0)) return bad_arg("obe_predictive_reading_quantiles: q outside (0, 1)");
+        if (!(std::fabs(z) < kInf)) return bad_arg("obe_predictive_reading_quantiles: h_z is not finite");
+        lv.upper[j] = q > 0.5;
+        lv.frac[j] = q > 0.5 ? 1.0 - q : q;                      // (1 - q is exact there)
+        lv.z_lo[j] = z - kReadHair * (1.0 + std::fabs(z));
+        lv.z_hi[j] = z + kReadHair * (1.0 + std::fabs(z));
+    }
+    Score sc;
+    if (int rc = sc.prepare(who, m, d_settings, ld_s, n_settings, nullptr, 0, d_sigma, ld_sigma, h_noise_rows, d_particles,
+                            ld_p, n_particles, d_weights, d_ws, ws_bytes, n_q))
+        return rc;
+    hipStream_t st = as_stream(stream);
+    const ReadState state = read_carve(sc.ws.body, n_settings, sc.mm.n_channels, n_q);
+    return dispatch_model(sc.mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        const int group = read_group_of(Model::NC), groups = (n_q + group - 1) / group;
+        const dim3 grid((unsigned)sc.tiles, (unsigned)sc.used, (unsigned)groups);
+        const dim3 fold_grid((unsigned)sc.tiles, (unsigned)groups), fold_block(kWave, (unsigned)(group * Model::NC));
+        const int64_t n_pad = sc.tiles * kWave;
+        if (h_noise_rows)
+            reading_bracket_kernel<Model, true><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_settings, nullptr, 0, sc.rows,
+                                                                        d_particles, ld_p, n_particles, d_weights,
+                                                                        sc.chunk_len, lv, state.partials);
+        else
+            reading_bracket_kernel<Model, false><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_settings, d_sigma, ld_sigma,
+                                                                         sc.rows, d_particles, ld_p, n_particles, d_weights,
+                                                                         sc.chunk_len, lv, state.partials);
+        OBE_CHECK_LAUNCH("reading_bracket_kernel");
+        reading_init_kernel<<<fold_grid, fold_block, 0, st>>>(sc.used, Model::NC, group, lv, n_pad, n_settings, state,
+                                                              d_quantiles, d_passes);
+        OBE_CHECK_LAUNCH("reading_init_kernel");
+        for (int pass = 1; pass <= max_passes; ++pass) {         // a fixed budget: nothing is waited for
+            if (h_noise_rows)
+                reading_pass_kernel<Model, true><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_settings, nullptr, 0,
+                                                                         sc.rows, d_particles, ld_p, n_particles, d_weights,
+                                                                         sc.chunk_len, lv, state);
+            else
+                reading_pass_kernel<Model, false><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_settings, d_sigma,
+                                                                          ld_sigma, sc.rows, d_particles, ld_p, n_particles,
+                                                                          d_weights, sc.chunk_len, lv, state);
+            OBE_CHECK_LAUNCH("reading_pass_kernel");
+            reading_step_kernel<<<fold_grid, fold_block, 0, st>>>(sc.used, Model::NC, group, lv, n_pad, n_settings, state, pass,
+                                                                  max_passes, d_quantiles, d_passes);
+            OBE_CHECK_LAUNCH("reading_step_kernel");
+        }
         return 0;
     });
 }

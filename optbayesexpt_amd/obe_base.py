@@ -33,7 +33,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _batch, _bounds, _design, _devrng, _interest, _lib, _predictive, _scoring
+from . import _batch, _bounds, _design, _devrng, _interest, _lib, _predictive, _reading, _scoring
 from ._sweepstate import Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
@@ -459,6 +459,26 @@ class OptBayesExpt(ParticlePDF):
     def predictive_pvalue(self, settings, y_meas, sigma=None):
         """Two-sided p-value per channel, ``(n_channels, n_r)``: ``2 min(lower, upper)``, clipped to 1."""
         return _scoring.predictive_pvalue(self, settings, y_meas, sigma)
+
+    # ------------------------------------------------ where will the next reading fall?  (the inverse of predictive_cdf)
+    # (extension: quantiles of the same mixture, noise included — the band to draw against measured points, an outlier
+    # threshold fixed before the reading is taken, the range to set on an instrument.  Per channel, not joint.  On the
+    # device (_reading.py, csrc/obe_predict.hip): a bracket pass over the cloud, then a fixed budget of ``max_passes``
+    # safeguarded Newton passes; nothing of the object changes.  ``settings`` as for predict() (None: the whole design
+    # grid); ``sigma`` as for predictive_cdf, a scalar, (C,), (C, n_x) or for one channel (n_x,) — required here, refused
+    # by OptBayesExptNoiseParameter.)
+    def reading_quantile(self, q, settings=None, sigma=None, max_passes=48, full_output=False):
+        """The y with ``predictive_cdf(x, y, sigma) == q`` for every level ``q`` in (0, 1): ``(n_q, n_channels, n_x)``
+        (``(n_channels, n_x)`` for a scalar ``q``); NaN where no particle contributes.  A result still open after
+        ``max_passes`` passes is the midpoint of its bracket and a ``RuntimeWarning`` names their count.
+        ``full_output``: also ``{"passes": int32 array of the results' shape (0: a NaN result, negative: still open),
+        "unconverged": int}``."""
+        return _reading.reading_quantile(self, q, settings, sigma, max_passes, full_output)
+
+    def reading_interval(self, level=0.95, settings=None, sigma=None, max_passes=48, full_output=False):
+        """Equal-tailed band ``(lo, hi)`` of the next READING, each ``(n_channels, n_x)``: ``reading_quantile`` at
+        ``(1 - level) / 2`` and ``(1 + level) / 2``."""
+        return _reading.reading_interval(self, level, settings, sigma, max_passes, full_output)
 
     # ------------------------------------------------ a recorded data set in one call
     # (extension: pdf_update() takes one reading at a time — obe_base.py:340-399 —; a recorded spectrum, yesterday's
