@@ -559,6 +559,11 @@ OBE_API int obe_sweep_cells_plan(double x_min, double x_max, double d, int64_t n
  * pass over the draws plus the fixed cost of its launches, the form it would replace (the cells where
  * obe_sweep_cells_plan() takes them, otherwise the direct kernel) costs at least OBE_CELL_MIN_GAIN times as much. */
 OBE_API int obe_sweep_bins_plan(double x_min, double x_max, double d, int64_t n_settings, int64_t n_draws);
+/* Host only, nothing is launched: the wavefronts that share each group of 64 settings when an OBE_SWEEP_BINS call of
+ * n_settings settings (the call's own: a rank's slice) evaluates the bins — 8 up to 16 384 settings, 6 up to 32 768,
+ * 3 up to 65 536, the largest at which every workgroup of the launch is resident at once, and 1 beyond.  The results
+ * do not depend on it. */
+OBE_API int obe_sweep_bins_eval_waves(int64_t n_settings);
 /* Settings one lane of the sweep kernel owns at most for a grid of n_settings (1, 2, 4 or 8; a sweep of
  * few draws may use fewer): the number of denominators a model's fast form inverts together, which a
  * caller that predicts whether a settings grid stays inside that form's range needs

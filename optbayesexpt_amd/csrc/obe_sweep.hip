@@ -447,6 +447,27 @@ static BinUnits plan_bin_units(int64_t nd) {
     u.nunits = static_cast<int>((nd + u.per - 1) / u.per);
     return u;
 }
+// Wavefronts that share a group of 64 settings in bin_eval_kernel (its instances: kBinEvalShapes), from the settings
+// of the call alone.  Every instance compiles to at most 168 VGPRs: three wavefronts per SIMD, twelve per CU.  A
+// workgroup is G groups x W wavefronts, always a multiple of four: the wavefronts of a workgroup are dealt to the four
+// SIMDs of its CU in turn, and workgroups of two, three or six wavefronts leave SIMDs short (they measured slower than
+// W = 1: profiles/bin_waves.txt), so W = 3 and 6 come as workgroups of four and two groups.  12 / (G W) whole
+// workgroups fit a CU.  The rule: the largest W at which every workgroup of the launch is resident at once on the
+// chip's 256 CUs, one round and no tail, which also never asks for more wavefronts than fill the SIMDs to that
+// occupancy; 1 where no other instance fits: the workgroups of W = 1 (kBlock threads, four groups) then come in rounds.
+// (W = 4 and W = 2 in workgroups of kBlock threads would serve 768 and 1536 groups, but within 168 VGPRs they compile
+// to scratch; in workgroups of eight wavefronts they serve no more groups than W = 6 and W = 3 do.)
+struct BinEvalShape {
+    int waves, groups;         // W, G
+};
+constexpr BinEvalShape kBinEvalShapes[] = {{8, 1}, {6, 2}, {3, 4}};          // and {1, 4}
+constexpr int kBinEvalWavesPerCU = 12, kChipCUs = 256;
+static int plan_bin_eval_waves(int64_t ns) {
+    const int64_t groups = (ns + kWave - 1) / kWave;
+    for (const BinEvalShape& f : kBinEvalShapes)
+        if (groups <= (int64_t)kChipCUs * f.groups * (kBinEvalWavesPerCU / (f.groups * f.waves))) return f.waves;
+    return 1;
+}
 static int64_t bin_max_items(int64_t nd) { return (nd + kBinChunk - 1) / kBinChunk + LorentzBins::kMaxBins; }
 // where the pieces live, in doubles from a 16-byte aligned base behind the packed draws
 struct BinLayout {
@@ -697,10 +718,11 @@ __global__ __launch_bounds__(kBlock) void cell_eval_kernel(SweepArgs a, const Ce
 //   bin_group_kernel<1>  the same walk again: a draw goes to (start of its bin) + (draws of that bin in earlier
 //                        units) + (earlier draws of that bin in this unit) — the order of a stable sort by bin.
 //   bin_moments_kernel   lane <-> draw within one item (kBinChunk consecutive draws of ONE bin), 3 P + 2 running sums
-//                        per lane, a butterfly over the lanes once per item.
+//                        per lane, reduced over the lanes once per item (halving_reduce: a butterfly's tree).
 //   bin_fold_kernel      a bin's items summed in a fixed order (fold_in_order).
-//   bin_eval_kernel      lane <-> setting, the bins' rows through LDS, bins in order; writes part1 / part2 as ONE
-//                        chunk and cs_out = 0, as cell_eval_kernel does.
+//   bin_eval_kernel      lane <-> setting, the bins' rows through LDS, bins in order, one or several wavefronts per
+//                        64 settings (plan_bin_eval_waves); writes part1 / part2 as ONE chunk and cs_out = 0, as
+//                        cell_eval_kernel does.
 // No floating-point atomics; every sum has a fixed association, so two calls on the same inputs give the same bits.
 // With a keep buffer (obe_sweep_utility_keep) the plan, binstart and itemstart live there and bin_group_kernel<1> also
 // leaves every draw's sorted position; a later call with OBE_SWEEP_BINS_KEPT runs, in place of the pack and the five
@@ -987,6 +1009,46 @@ __global__ __launch_bounds__(kBlock) void bin_scan_kernel(int nunits, BinSweepPt
     if (threadIdx.x == 0) q.totals[bin] = total;
 }
 
+// N sums per lane reduced over the 64 lanes by recursive halving: at distance DIST a lane keeps the lower or the upper
+// half of its list (an odd list is padded), by its lane bit DIST, and adds its partner's copy of that half — mine +
+// partner's, which is what both lanes of a pair compute for that value in a butterfly, so every value passes through
+// the butterfly's tree and has its bits, in N/2 + N/4 + ... exchanges instead of 6 N.  A lane ends with two values.
+template <int N, int DIST>
+__device__ __forceinline__ void halving_reduce(const double (&v)[N], int lane, double (&out)[2]) {
+    constexpr int H = (N + 1) / 2;
+    const bool upper = (lane & DIST) != 0;
+    double k[H];
+#pragma unroll
+    for (int i = 0; i < H; ++i) {
+        const double lo = v[i], hi = H + i < N ? v[H + i] : 0.0;
+        const double mine = upper ? hi : lo, send = upper ? lo : hi;
+        k[i] = mine + __shfl_xor(send, DIST, kWave);
+    }
+    if constexpr (DIST > 1) {
+        halving_reduce<H, DIST / 2>(k, lane, out);
+    } else {
+        static_assert(H == 2, "64 lanes x 2 values: at most 128 sums");
+        out[0] = k[0];
+        out[1] = k[1];
+    }
+}
+// which of the N sums out[e] of halving_reduce<N, 32> is on this lane; -1: padding
+template <int N>
+__device__ __forceinline__ int halving_index(int lane, int e) {
+    int n[7];
+    n[0] = N;
+#pragma unroll
+    for (int l = 0; l < 6; ++l) n[l + 1] = (n[l] + 1) / 2;
+    int j = e;
+    bool real = true;
+#pragma unroll
+    for (int l = 5; l >= 0; --l) {                        // level l: distance 32 >> l, lane bit 5 - l
+        j += ((lane >> (5 - l)) & 1) * n[l + 1];
+        real = real && j < n[l];
+    }
+    return real ? j : -1;
+}
+
 // one wavefront per item: kBinChunk consecutive sorted draws of one bin
 __global__ __launch_bounds__(kWave) void bin_moments_kernel(BinSweepPtrs q, const unsigned* abort) {
     using LB = LorentzBins;
@@ -1006,31 +1068,46 @@ __global__ __launch_bounds__(kWave) void bin_moments_kernel(BinSweepPtrs q, cons
     const double2* __restrict__ rec = reinterpret_cast<const double2*>(q.sorted);
     LB::Sums z;
     z.clear();
-    for (int i = first + lane; i < end; i += kWave) {
-        const double2 ra = rec[2 * (int64_t)i], rb = rec[2 * (int64_t)i + 1];
+    // the records of the next trip are asked for before this trip's arithmetic: the wait for them sits behind it
+    int i = first + lane;
+    double2 ra = double2{0.0, 0.0}, rb = ra;
+    if (i < end) {
+        ra = rec[2 * (int64_t)i];
+        rb = rec[2 * (int64_t)i + 1];
+    }
+    while (i < end) {
+        const int in = i + kWave;
+        double2 na = ra, nb = rb;
+        if (in < end) {
+            na = rec[2 * (int64_t)in];
+            nb = rec[2 * (int64_t)in + 1];
+        }
         const double pk[4] = {ra.x, ra.y, rb.x, rb.y};
         LB::add_draw(tb, pk, z);
+        ra = na;
+        rb = nb;
+        i = in;
     }
-    // the 64 lanes' sums by a butterfly (the same association on every lane); lane j keeps coefficient j, j + 64
-    double keep0 = 0.0, keep1 = 0.0;
-    auto reduce = [&](double v, int j, double scale) {
-#pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-        v *= scale;
-        if (j < kWave) keep0 = lane == j ? v : keep0;
-        else keep1 = lane == j - kWave ? v : keep1;
-    };
+    // the 64 lanes' sums of coefficient j (M1_k at k, M2_k at kOrder + k, M3_k at 2 kOrder + k, c1, c2), each through
+    // the tree (l, l ^ 32), then ^ 16, ... ^ 1 of a butterfly, of which a lane keeps only the half it will store
+    double v[LB::kCoefs], kept[2];
 #pragma unroll
     for (int k = 0; k < LB::kOrder; ++k) {
-        reduce(z.M1[k], k, 1.0);
-        reduce(z.M2[k], LB::kOrder + k, 1.0);
-        reduce(z.M3[k], 2 * LB::kOrder + k, (double)(k + 1));
+        v[k] = z.M1[k];
+        v[LB::kOrder + k] = z.M2[k];
+        v[2 * LB::kOrder + k] = z.M3[k];
     }
-    reduce(z.c1, 3 * LB::kOrder, 1.0);
-    reduce(z.c2, 3 * LB::kOrder + 1, 1.0);
+    v[3 * LB::kOrder] = z.c1;
+    v[3 * LB::kOrder + 1] = z.c2;
+    halving_reduce<LB::kCoefs, kWave / 2>(v, lane, kept);
     double* __restrict__ out = q.part + (int64_t)item * LB::kRow;
-    out[lane] = keep0;
-    if (lane + kWave < LB::kCoefs) out[lane + kWave] = keep1;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int j = halving_index<LB::kCoefs>(lane, e);
+        if (j < 0) continue;                              // (padding of an odd level)
+        const bool m3 = j >= 2 * LB::kOrder && j < 3 * LB::kOrder;
+        out[j] = kept[e] * (m3 ? (double)(j - 2 * LB::kOrder + 1) : 1.0);      // H3_k = (k + 1) M3_k
+    }
 }
 
 // coef[bin][co] = sum over the bin's items of part[item][co]
@@ -1054,14 +1131,39 @@ __global__ __launch_bounds__(kBinFoldGroups * kWave) void bin_fold_kernel(BinSwe
 // global loads in flight while this one is evaluated: a row fetched by the wavefront that needs it (scalar loads, one
 // L2 round trip per bin and wavefront, one wavefront per SIMD at 65 536 settings) left the kernel waiting four
 // fifths of its time.
+// A workgroup holds G groups of 64 settings (lane <-> setting) and W wavefronts for each of them; all share the tile.
+// <4, 1>: a workgroup of kBlock threads, every wavefront walks every occupied bin of its own group.  W > 1: of every
+// tile wavefront w of a group evaluates the occupied bins t = w, w + W, ... and leaves their t1, t2 in LDS, and behind
+// a barrier wavefront 0 of the group adds them in bin order, as the one wavefront of W = 1 does: the same numbers in
+// the same order, the same bits, and the one dependent chain per bin is walked by W wavefronts at once
+// (plan_bin_eval_waves; DESIGN.md, "Several wavefronts per group of settings").  Every wavefront of a workgroup takes
+// the same way through the barriers: nbins and the abort word (read once per workgroup where W > 1) are the same for all.
 constexpr int kBinTile = 16;
-__global__ __launch_bounds__(kBlock) void bin_eval_kernel(SweepArgs a, BinSweepPtrs q, unsigned seq) {
+template <int G, int W>
+__global__ __launch_bounds__(G * W * kWave, W == 1 ? 1 : 3)           // (W > 1: registers for three wavefronts per SIMD)
+void bin_eval_kernel(SweepArgs a, BinSweepPtrs q, unsigned seq) {
     using LB = LorentzBins;
-    constexpr int kTileDoubles = kBinTile * LB::kRow, kPer = (kTileDoubles + kBlock - 1) / kBlock;
+    constexpr int kThreads = G * W * kWave;
+    static_assert(W > 1 || kThreads == kBlock, "W = 1 is the workgroup of four groups");
+    static_assert((G * W) % 4 == 0, "whole wavefronts for every SIMD of the CU (plan_bin_eval_waves)");
+    constexpr int kTileDoubles = kBinTile * LB::kRow, kPer = (kTileDoubles + kThreads - 1) / kThreads;
     __shared__ double tile[kTileDoubles];
     __shared__ int occupied[kBinTile];
-    if (sweep_aborted(a.abort)) return;
-    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
+    const int grp = wave % G, wid = wave / G;             // wavefront `wid` of group `grp`
+    double* term = nullptr;                               // W > 1, the group's: t1 at [t][lane], t2 at [kBinTile + t][lane]
+    if constexpr (W == 1) {
+        if (sweep_aborted(a.abort)) return;
+    } else {
+        __shared__ double terms[G * 2 * kBinTile * kWave];
+        __shared__ int stop;
+        term = terms + grp * (2 * kBinTile * kWave);
+        if (threadIdx.x == 0) stop = sweep_aborted(a.abort);
+        __syncthreads();
+        if (stop) return;
+    }
+    const int64_t s = ((int64_t)blockIdx.x * G + grp) * kWave + lane;
     // (a reuse whose keep buffer does not fit the call, or one of whose draws has left its kept bin: as if poisoned)
     const bool refused = bin_keep_refused(q) || (q.reuse && q.keep->mismatch == q.call);
     const int nbins = refused ? 0 : __builtin_amdgcn_readfirstlane(q.plan->nbins);
@@ -1078,8 +1180,8 @@ __global__ __launch_bounds__(kBlock) void bin_eval_kernel(SweepArgs a, BinSweepP
         auto fetch = [&](int b0) {
 #pragma unroll
             for (int u = 0; u < kPer; ++u) {
-                const int e = b0 * LB::kRow + u * kBlock + (int)threadIdx.x;
-                nxt[u] = u * kBlock + (int)threadIdx.x < kTileDoubles && e < total ? coef[e] : 0.0;
+                const int e = b0 * LB::kRow + u * kThreads + (int)threadIdx.x;
+                nxt[u] = u * kThreads + (int)threadIdx.x < kTileDoubles && e < total ? coef[e] : 0.0;
             }
             const int b = b0 + (int)threadIdx.x;
             nxt_occ = (int)threadIdx.x < kBinTile && b < nbins ? q.binstart[b + 1] != q.binstart[b] : 0;
@@ -1087,29 +1189,50 @@ __global__ __launch_bounds__(kBlock) void bin_eval_kernel(SweepArgs a, BinSweepP
         fetch(0);
         double a1 = 0.0, a2 = 0.0, C1 = 0.0, C2 = 0.0;
         for (int b0 = 0; b0 < nbins; b0 += kBinTile) {
-            __syncthreads();                                      // the previous tile has been evaluated
+            __syncthreads();                                      // the previous tile has been evaluated (and summed)
 #pragma unroll
             for (int u = 0; u < kPer; ++u)
-                if (u * kBlock + (int)threadIdx.x < kTileDoubles) tile[u * kBlock + threadIdx.x] = nxt[u];
+                if (u * kThreads + (int)threadIdx.x < kTileDoubles) tile[u * kThreads + threadIdx.x] = nxt[u];
             if (threadIdx.x < kBinTile) occupied[threadIdx.x] = nxt_occ;
             __syncthreads();
             if (b0 + kBinTile < nbins) fetch(b0 + kBinTile);
-            for (int t = 0; t < kBinTile; ++t) {
-                if (!__builtin_amdgcn_readfirstlane(occupied[t])) continue;       // (wave-uniform; beyond nbins: 0)
-                const double* row = tile + t * LB::kRow;
-                double t1, t2;
-                LB::evaluate(row, LB::centre(origin, b0 + t) - tau, t1, t2);
-                a1 += t1;
-                a2 += t2;
-                C1 += row[3 * LB::kOrder];
-                C2 += row[3 * LB::kOrder + 1];
+            if constexpr (W == 1) {
+                for (int t = 0; t < kBinTile; ++t) {
+                    if (!__builtin_amdgcn_readfirstlane(occupied[t])) continue;       // (wave-uniform; beyond nbins: 0)
+                    const double* row = tile + t * LB::kRow;
+                    double t1, t2;
+                    LB::evaluate(row, LB::centre(origin, b0 + t) - tau, t1, t2);
+                    a1 += t1;
+                    a2 += t2;
+                    C1 += row[3 * LB::kOrder];
+                    C2 += row[3 * LB::kOrder + 1];
+                }
+            } else {
+                for (int t = wid; t < kBinTile; t += W) {        // (a wavefront that owns no occupied bin of the tile: none)
+                    if (!__builtin_amdgcn_readfirstlane(occupied[t])) continue;
+                    double t1, t2;
+                    LB::evaluate(tile + t * LB::kRow, LB::centre(origin, b0 + t) - tau, t1, t2);
+                    term[t * kWave + lane] = t1;
+                    term[(kBinTile + t) * kWave + lane] = t2;
+                }
+                __syncthreads();                                  // the tile's terms are in LDS
+                if (wid == 0) {
+                    for (int t = 0; t < kBinTile; ++t) {
+                        if (!__builtin_amdgcn_readfirstlane(occupied[t])) continue;   // skipped, not added as zero
+                        const double* row = tile + t * LB::kRow;
+                        a1 += term[t * kWave + lane];
+                        a2 += term[(kBinTile + t) * kWave + lane];
+                        C1 += row[3 * LB::kOrder];
+                        C2 += row[3 * LB::kOrder + 1];
+                    }
+                }
             }
         }
         S1 = a1 + C1;
         S2 = a2 + C2;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *q.ran = seq;
-    if (s >= a.ns) return;
+    if (s >= a.ns || (W > 1 && wid != 0)) return;
     a.part1[s] = S1;
     a.part2[s] = S2;
     a.cs_out[s] = 0.0;
@@ -1800,7 +1923,13 @@ static int launch_bin_plan(const SweepArgs& a, const BinSweep& b, hipStream_t st
 // in place of launch_sweep: one chunk of moments in part1 / part2, cs_out = 0
 static int launch_bin_sweep(SweepPlan& p, SweepArgs& a, const BinSweep& b, hipStream_t st) {
     p.nchunks = 1;
-    bin_eval_kernel<<<(unsigned)((a.ns + kBlock - 1) / kBlock), kBlock, 0, st>>>(a, b.q, b.seq);
+    const unsigned groups = (unsigned)((a.ns + kWave - 1) / kWave);
+    switch (plan_bin_eval_waves(a.ns)) {             // (the shapes of kBinEvalShapes)
+        case 8: bin_eval_kernel<1, 8><<<groups, 8 * kWave, 0, st>>>(a, b.q, b.seq); break;
+        case 6: bin_eval_kernel<2, 6><<<(groups + 1) / 2, 12 * kWave, 0, st>>>(a, b.q, b.seq); break;
+        case 3: bin_eval_kernel<4, 3><<<(groups + 3) / 4, 12 * kWave, 0, st>>>(a, b.q, b.seq); break;
+        default: bin_eval_kernel<4, 1><<<(groups + 3) / 4, kBlock, 0, st>>>(a, b.q, b.seq);
+    }
     OBE_CHECK_LAUNCH("bin_eval_kernel");
     return 0;
 }
@@ -1987,6 +2116,8 @@ int obe_sweep_bins_plan(double x_min, double x_max, double d, int64_t n_settings
     const double bins = (double)n_settings * OBE_BIN_MAX * kBinEvalSlots + (double)n_draws * kBinDrawSlots + kBinFixedSlots;
     return replaced >= OBE_CELL_MIN_GAIN * bins ? 3 : 1;
 }
+
+int obe_sweep_bins_eval_waves(int64_t n_settings) { return plan_bin_eval_waves(n_settings < 1 ? 1 : n_settings); }
 
 int obe_sweep_settings_per_lane_for(int64_t n_settings, int64_t n_draws) {
     if (n_settings < 1) n_settings = 1;
