@@ -960,6 +960,34 @@ OBE_API int obe_design_step(const double* d_cross, int64_t pivot_index, double* 
                     int32_t max_rows, double* d_cvar, int32_t n_channels, int64_t n_settings,
                     const double* d_noise_var, int64_t ld_noise, const double* d_cost, double cost,
                     const uint8_t* d_taken, double* d_utility, double* d_best, double* d_info, void* stream);
+/* One step of the greedy design FOR PARAMETERS OF INTEREST: obe_design_step's conditioning applied to the blocks of
+ * obe_output_covariance — the whole S(x) (C x C) and K_dc(x) = cov(theta_d, y_c(x)) — and obe_variance_reduction's score
+ * of what is left.  With a, g and L_m as for obe_design_step (row m = rows_done + c', the rows of earlier calls read
+ * from d_factors):
+ *   b(d)      = K_dc'(p) - sum_{m' < m} T_m'(d) L_m'(c', p)           T_m(d) = b(d) / sqrt(g)
+ *   S_cc''(x) -= L_m(c, x) L_m(c'', x)      K_dc(x) -= T_m(d) L_m(c, x)      Vleft_d -= T_m(d)^2
+ *   G_d(x)    = k_d(x)^T (S(x) + diag nu(x))^-1 k_d(x)                U(x) = [sum_d h_weights[d] G_d(x) / V_d] / cost(x)
+ * d_cross (C, C, n_settings): the pivot's block of obe_output_cross_covariance; NULL: nothing is conditioned on, the
+ * score is formed from d_ycov and d_xcov as they are (with what obe_output_covariance left: obe_variance_reduction's
+ * d_gain and d_utility, bit for bit — the same kernel in the same tiles of 8 rows).  d_factors (max_rows, C, n_settings)
+ * and d_tstore (max_rows, n_sel): rows [0, rows_done) are read (d_factors), rows [rows_done, rows_done + C) written,
+ * nothing beyond.  d_ycov (C (C + 1) / 2, n_settings), packed as obe_output_covariance packs it, and d_xcov (n_sel, C,
+ * n_settings): in and out.  d_pvar (n_sel,): V, the UNCONDITIONED variance of the rows of interest, read only (a term
+ * with V_d == 0 is 0).  d_pvar_left (n_sel,): Vleft, in and out (the caller starts it at V); after the rows of the picks A
+ * it is V_d - k_A^T (K_AA + N_A)^-1 k_A, and what the C rows of a pick remove of it is the G_d that chose the pick.
+ * h_weights (n_sel,) or NULL (1 each): an input, read before the call returns.  d_noise_var, ld_noise, d_cost, cost,
+ * d_taken, d_best: as for obe_design_step.  d_gain (n_sel, n_settings) and d_utility (n_settings,) are both written.
+ * n_sel 1..OBE_MAX_DIMS, n_channels 1..OBE_MAX_CHANNELS.  T_m needs K at the pivot's column, which the grid-wide launch
+ * rewrites: a launch of one workgroup forms the T rows of the pick first and the grid-wide launch reads them — nothing
+ * written by a launch is read by another thread of that launch.  A g that is not > 0 or not finite makes its rows NaN,
+ * and with them everything that follows.  Exact for a model that is linear in its parameters with a Gaussian cloud, a
+ * heuristic otherwise, and greedy.  Everything stays in DEVICE memory, nothing is waited for.  Model-independent. */
+OBE_API int obe_design_interest_step(const double* d_cross, int64_t pivot_index, double* d_factors, double* d_tstore,
+                             int32_t rows_done, int32_t max_rows, double* d_ycov, double* d_xcov, int32_t n_sel,
+                             int32_t n_channels, int64_t n_settings, const double* d_noise_var, int64_t ld_noise,
+                             const double* d_pvar, double* d_pvar_left, const double* h_weights, const double* d_cost,
+                             double cost, const uint8_t* d_taken, double* d_gain, double* d_utility, double* d_best,
+                             void* stream);
 
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);

@@ -11,10 +11,16 @@ output variance of every setting, conditioned on the noisy readings already plan
 of the noise and divided by the cost; the next pick is its first maximum.  That is exact for a model that is linear in
 its parameters with a Gaussian cloud and an approximation otherwise, and greedy, not optimal.  The argument checks are
 plain functions of this module (no device needed); ``OptBayesExpt`` has the methods.
+
+With ``interest`` the same greedy rule designs for chosen parameter rows, the others being nuisances: the blocks of
+``_interest`` — S(x) and K(x) = cov(theta_d, y(x)) — are conditioned on the planned readings by the same rows
+(``obe_design_interest_step``, csrc/obe_design.hip) and every pick maximises ``utility_parameter_variance()``'s score of
+what is left, ``[sum_d a_d G_d(x | picks) / V_d] / cost``.  The same caveat: exact for a model that is linear in its
+parameters with a Gaussian cloud, a heuristic otherwise, and greedy.
 """
 import numpy as np
 
-from . import _interest, _predictive
+from . import _interest, _lib, _predictive
 from ._predictive import _column_tiles, _device_model, _inputs, _ptr
 
 ROWS_PER_CALL = 8                              # obe_output_cross_covariance: rows (pivots x channels) one call serves
@@ -168,8 +174,105 @@ def plan(obe, n, sigma=None, distinct=False):
     return dict(indices=indices, utility=utility, information=information), state
 
 
-def opt_setting_batch(obe, n, sigma=None, distinct=False):
-    report, _ = plan(obe, n, sigma, distinct)
+# ------------------------------------------------------------------------ the design for parameters of interest
+def check_interest(obe, interest, interest_weights):
+    """None (the output-variance design) or ``(rows, weights)`` of the parameters a batch is designed for: ``interest``
+    None or False: none, and weights are refused; True: the object's ``parameters_of_interest``, with
+    ``interest_weights`` in place of its weights if given; an int or a sequence of ints: those rows
+    (``_interest.check_dims``), weighted by ``interest_weights`` (``_interest.check_weights``; None: 1 each)."""
+    if interest is None or (isinstance(interest, (bool, np.bool_)) and not interest):
+        if interest_weights is not None:
+            raise ValueError("interest_weights are the weights of the parameters of interest: pass interest as well")
+        return None
+    if isinstance(interest, (bool, np.bool_)):
+        rows, weights = obe.parameters_of_interest
+        if interest_weights is not None:
+            weights = _interest.check_weights(interest_weights, len(rows))
+        return tuple(rows), weights
+    rows = _interest.check_dims(interest, obe.n_dims)
+    return rows, _interest.check_weights(interest_weights, len(rows))
+
+
+class _InterestStep:
+    """The state of one greedy design for parameters of interest on the device — S (``ycov``, packed) and K (``xcov``)
+    conditioned on the picks so far, ``pvar_left``, the factor and T stores — and the ``obe_design_interest_step`` call
+    on it."""
+
+    def __init__(self, obe, ycov, xcov, pvar, weights, noise_var, cost, max_rows, distinct):
+        import torch
+        self.obe, self.ycov, self.xcov, self.pvar = obe, ycov, xcov, pvar
+        self.n_sel, self.n_c, self.n_x = xcov.shape
+        dev = obe._device
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float64, device=dev)
+        self.pvar_left = pvar.clone()
+        self.weights = np.ascontiguousarray(weights, dtype=np.float64)
+        self.nv = torch.from_numpy(np.ascontiguousarray(noise_var)).to(dev)
+        self.cost = cost
+        self.max_rows, self.rows_done = max_rows, 0
+        self.factors, self.tstore = new(max(max_rows, 1), self.n_c, self.n_x), new(max(max_rows, 1), self.n_sel)
+        self.taken = torch.zeros(self.n_x, dtype=torch.uint8, device=dev) if distinct else None
+        self.gain, self.utility = new(self.n_sel, self.n_x), new(self.n_x)
+        self.out = torch.zeros(2, dtype=torch.float64, device=dev)       # d_best (value, index)
+
+    def step(self, cross=None, pivot_index=0):
+        """Conditions on the pivot's block ``cross (C, C, n_x)`` (None: on nothing); (the best utility left, its index,
+        the ``(n_sel,)`` gains there — None if there is no such setting)."""
+        d_cost, cost_scalar = self.cost
+        self.obe._lib.call("obe_design_interest_step", None if cross is None else _ptr(cross), int(pivot_index),
+                           _ptr(self.factors), _ptr(self.tstore), self.rows_done, self.max_rows, _ptr(self.ycov),
+                           _ptr(self.xcov), self.n_sel, self.n_c, self.n_x, _ptr(self.nv),
+                           0 if self.nv.shape[1] == 1 else self.n_x, _ptr(self.pvar), _ptr(self.pvar_left),
+                           _lib.host_ptr(self.weights), None if d_cost is None else _ptr(d_cost), float(cost_scalar),
+                           None if self.taken is None else _ptr(self.taken), _ptr(self.gain), _ptr(self.utility),
+                           _ptr(self.out), self.obe._stream())
+        if cross is not None:
+            self.rows_done += self.n_c
+        host = self.out.cpu().numpy()                        # the 16 bytes of a pick
+        value, pick = float(host[0]), int(host.view(np.int64)[1])
+        return value, pick, self.gain[:, pick].cpu().numpy() if pick >= 0 else None
+
+
+def plan_interest(obe, n, rows, weights, sigma=None, distinct=False):
+    """The greedy design for the parameter rows ``rows`` with the weights ``weights``: ``(report, step)`` with
+    ``report`` as ``last_batch_design`` holds it and ``step`` the device state after conditioning on the first n - 1
+    picks (the tests read it).  K12's passes once over the grid, then one cross pass per pick but the last."""
+    _device_model(obe)
+    n_c, n_s = obe.n_channels, obe._n_settings
+    n = check_n(n, n_c)
+    nv = check_noise_variance(_interest.noise_variance(sigma, obe.yvar_noise_model, n_c, n_s, n_s, False))
+    x, p, w = _inputs(obe, None)
+    cost = obe._cost_device(whole_grid=True)
+    mean, ycov, xcov, pvar = _interest._blocks(obe, None, rows)
+    state = _InterestStep(obe, ycov, xcov, pvar, weights, nv, cost, (n - 1) * n_c, distinct)
+    prior = pvar.cpu().numpy()
+    indices, utility, left = np.empty(n, dtype=np.int64), np.empty(n), np.empty((n, len(rows)))
+    pick = -1
+    for j in range(n):
+        if j:
+            cross = _cross(obe, x, x[:, pick:pick + 1].contiguous(), p, w, mean)
+            value, pick, gain = state.step(cross[0], pick)
+        else:
+            value, pick, gain = state.step()
+        if pick < 0:
+            raise ValueError(f"opt_setting_batch: no setting with a finite utility is left for pick {j}")
+        indices[j], utility[j] = pick, value
+        left[j] = (left[j - 1] if j else prior) - gain
+        if state.taken is not None:
+            state.taken[pick] = 1
+    report = dict(indices=indices, utility=utility, variance_left=left, prior_variance=prior, dims=tuple(rows),
+                  weights=np.array(weights, dtype=np.float64))
+    return report, state
+
+
+def opt_setting_batch(obe, n, sigma=None, distinct=False, interest=None, interest_weights=None):
+    _device_model(obe)
+    chosen = check_interest(obe, interest, interest_weights)
+    if chosen is None:
+        report, _ = plan(obe, n, sigma, distinct)
+    else:
+        report, _ = plan_interest(obe, n, chosen[0], chosen[1], sigma, distinct)
     obe.last_batch_design = report
     grid = np.asarray(obe.allsettings)
     return tuple(np.array(grid[d, report["indices"]]) for d in range(grid.shape[0]))

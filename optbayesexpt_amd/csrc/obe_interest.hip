@@ -2,12 +2,10 @@
 // obe_predict.hip) left — S (C x C, packed lower triangle) and K (rows x C) per setting — the variance of each
 // parameter of interest that the best linear estimator from one reading removes, G_d = k_d^T (S + diag nu)^-1 k_d, and
 // the utility U = [sum_d a_d G_d / V_d] / cost.  Lane <-> setting; the C x C factor lives in registers.
-#include "obe_common.h"
+#include "obe_design.h"
 
 namespace obe {
 namespace {
-
-constexpr int kGainRows = 8;                       // rows one call serves: obe_output_covariance's
 
 struct GainWeights {
     double a[kGainRows];
@@ -88,6 +86,18 @@ int launch_gain(int n_channels, std::integer_sequence<int, C...>, int blocks, hi
 }
 
 }  // namespace
+
+int launch_variance_reduction(hipStream_t st, const double* d_ycov, const double* d_xcov, int n_rows, int n_channels,
+                              int64_t n_settings, const double* d_noise_var, int64_t ld_noise, const double* d_pvar,
+                              const double* h_weights, const double* d_cost, double cost, double* d_gain,
+                              double* d_utility, int accumulate) {
+    GainWeights wts;
+    for (int r = 0; r < kGainRows; ++r) wts.a[r] = h_weights && r < n_rows ? h_weights[r] : 1.0;
+    const int blocks = (int)((n_settings + kBlock - 1) / kBlock);
+    return launch_gain(n_channels, std::make_integer_sequence<int, OBE_MAX_CHANNELS>{}, blocks, st, d_ycov, d_xcov, n_rows,
+                       n_settings, d_noise_var, ld_noise, d_pvar, wts, d_cost, cost, accumulate, d_gain, d_utility);
+}
+
 }  // namespace obe
 
 using namespace obe;
@@ -104,13 +114,10 @@ int obe_variance_reduction(const double* d_ycov, const double* d_xcov, int32_t n
     if (n_settings < 1 || (ld_noise != 0 && ld_noise < n_settings))
         return bad_arg("obe_variance_reduction: n_settings < 1 or a row of the noise variance shorter than that");
     if (!d_gain && !d_utility) return 0;
-    GainWeights wts;
-    for (int r = 0; r < kGainRows; ++r) wts.a[r] = h_weights && r < n_rows ? h_weights[r] : 1.0;
     const int64_t blocks = (n_settings + kBlock - 1) / kBlock;
     if (blocks > 0x7fffffff) return bad_arg("obe_variance_reduction: too many settings for one call");
-    return launch_gain(n_channels, std::make_integer_sequence<int, OBE_MAX_CHANNELS>{}, (int)blocks, as_stream(stream), d_ycov,
-                       d_xcov, n_rows, n_settings, d_noise_var, ld_noise, d_pvar, wts, d_cost, cost, accumulate, d_gain,
-                       d_utility);
+    return launch_variance_reduction(as_stream(stream), d_ycov, d_xcov, n_rows, n_channels, n_settings, d_noise_var, ld_noise,
+                                     d_pvar, h_weights, d_cost, cost, d_gain, d_utility, accumulate);
 }
 
 }  // extern "C"

@@ -571,7 +571,7 @@ class OptBayesExpt(ParticlePDF):
         ``p_j``.  ``points`` and ``settings`` as ``predict()`` takes settings; ``settings=None``: the design grid."""
         return _design.output_cross_covariance(self, points, settings)
 
-    def opt_setting_batch(self, n, sigma=None, distinct=False):
+    def opt_setting_batch(self, n, sigma=None, distinct=False, interest=None, interest_weights=None):
         """The next ``n`` settings of the design grid, chosen one after the other: a tuple of ``n_setdims`` arrays of
         length ``n`` in pick order, which ``pdf_update_batch(xs, y, sigma)`` takes as they are.  Pick 0 maximises
         ``[sum_c var_c(x) / nu_c(x)] / cost_estimate()``, the ``variance_full`` utility; every later pick maximises the
@@ -583,8 +583,22 @@ class OptBayesExpt(ParticlePDF):
         Independent of ``utility_method``; ``last_setting_index`` stays.  ``last_batch_design`` keeps ``indices``
         (into the design grid), ``utility`` (of each pick when it was made) and ``information`` (nats the first j + 1
         readings are expected to deliver, ``log det(I + N^-1/2 K N^-1/2) / 2``).  On a settings-sharded object every
-        rank computes the whole grid from its replica and reaches the same picks."""
-        return _design.opt_setting_batch(self, n, sigma, distinct)
+        rank computes the whole grid from its replica and reaches the same picks.
+
+        ``interest``: design the batch for chosen parameters, the others being nuisances.  None or False: the design
+        above.  True: the rows and weights of ``parameters_of_interest``; an int or a sequence of distinct ints: those
+        parameter rows, 1 each; ``interest_weights`` replaces the weights for this call (finite, >= 0, not all zero;
+        without ``interest`` it is refused).  Every pick, pick 0 included, then maximises
+        ``utility_parameter_variance()``'s score, ``[sum_d a_d G_d(x | picks before) / V_d] / cost_estimate()``, with
+        ``G_d`` formed from the output covariance and the parameter-output covariance conditioned on noisy readings
+        at the picks before, and ``V_d`` the cloud's unconditioned variance.  ``last_batch_design`` then keeps
+        ``indices``, ``utility``, ``variance_left`` ``(n, n_sel)`` — the variance of each parameter of interest the
+        best linear estimator leaves after the first j + 1 readings, ``variance_left[j] = variance_left[j - 1] -
+        G(x_j | picks before)`` starting from ``prior_variance`` ``(n_sel,)`` —, ``dims`` and ``weights``.  There is no
+        ``information``: the information about the parameters of interest needs their full conditional covariance,
+        which this design does not carry.  The same caveat: exact for a model that is linear in its parameters with a
+        Gaussian cloud, a heuristic otherwise, and greedy."""
+        return _design.opt_setting_batch(self, n, sigma, distinct, interest, interest_weights)
 
     def _setting_array(self, onesettingset):
         """The setting of a record, zero-padded to OBE_MAX_SETDIMS — in this object's record buffer:

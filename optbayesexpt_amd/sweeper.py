@@ -199,7 +199,7 @@ class OptBayesExptSweeper(OptBayesExptNoiseParameter):
         self.last_setting_index = index
         return self.start_stop_indices[index]
 
-    def opt_setting_batch(self, n, sigma=None, distinct=False):
+    def opt_setting_batch(self, n, sigma=None, distinct=False, interest=None, interest_weights=None):
         """Refused: a sweeper's settings are (start, stop) intervals, and a batch design picks points."""
         raise TypeError("opt_setting_batch() designs a batch of point measurements; the settings of an "
                         "OptBayesExptSweeper are (start, stop) intervals")
