@@ -7,8 +7,9 @@ NumPy ``Generator`` (authoritative on the host: ``_devrng.advance`` keeps it whe
 constructor's arguments and a handful of counters.  ``snapshot()`` collects them into a plain dict; ``restore()``
 builds a new object through its class's normal constructor (workspace sizing, plugin load,
 ``obe_model_validate``) and then hands it that state.  The restored object continues bit for bit where the
-original stood.  The bins' kept grouping of the cloud (``_bins_keep``, ``_bins_kept_for``) is neither shared nor
-saved: a copy or a restored object has no buffer, rebuilds the grouping on its first bin sweep and gets the same bits.
+original stood.  The bins' kept grouping of the cloud (the buffer ``_bins_keep``; the key it was made for and the
+"this cloud does not fit the bins" mark, both in ``SweepState``) is neither shared nor saved: a copy or a restored
+object has no buffer and neither mark, rebuilds the grouping on its first bin sweep and gets the same bits.
 
 Taking a snapshot first settles all work in flight (``settle()``): a speculative sweep is dropped (it is recomputed
 on demand, with the same bits), the deferred check of a small draw's ``sum(w)`` runs, a constraint mask's

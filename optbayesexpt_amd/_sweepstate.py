@@ -1,6 +1,6 @@
 """The state of one object's sweep path, in one place and with names.
 
-``OptBayesExpt`` steers three things from cycle to cycle (the reference has none of them: its cycle is
+``OptBayesExpt`` steers four things from cycle to cycle (the reference has none of them: its cycle is
 ``opt_setting`` -> measure -> ``pdf_update``, obe_base.py:733-756, 340-399, with nothing carried over but the
 particles):
 
@@ -10,14 +10,22 @@ particles):
   cancellation factor kappa that every sweep reports);
 * the sweep that ``pdf_update()`` ENQUEUES AHEAD of being asked for it (:class:`Pattern`, :class:`Pending`):
   when it is worth trying, what it swept, whether its update let it run, and what has to be waited for before
-  its result words may be armed again.
+  its result words may be armed again;
+* the EXPANSION FORM of an unshifted full sweep of the one-peak Lorentzian (:class:`Attempt`): by particle bins, by
+  cells or pair by pair, whether the bins' grouping of the cloud is reused or rebuilt, and which form repeats a
+  sweep that came back with kappa = NaN (:meth:`SweepState.after`, the one place where a request's repeats are
+  decided).
 
 Nothing here touches the device: results are waited for through an ``io`` object with two methods
 (``wait_words(words, n, stream)``, ``still_armed(block)``, ``synchronize()``), the real one calling the
 library, the one of tests/test_host_logic.py a recorder.  Every decision is a method with a name; the object
 can be printed (``describe()``) when a run is being debugged.
 """
+import collections
 import enum
+import math
+
+from . import _lib          # (the OBE_SWEEP_* bits of include/obe_hip.h: constants, nothing is loaded)
 
 
 class Form(enum.Enum):
@@ -50,6 +58,37 @@ class Ticket:
         self.stream, self.stream_id = stream, stream_id
 
 
+class Attempt(collections.namedtuple("Attempt", "shifted safe bins cells keep cells_too")):
+    """The form of one sweep attempt, stated once: the flags word of the call, the form entries of the ticket's
+    inputs and ``last_sweep`` are all read from it.  ``bins`` / ``cells``: the expansion form that runs (never both);
+    ``keep``: None — no keep buffer is passed, False — the bins' grouping is rebuilt into it, True — reused;
+    ``cells_too``: a bin sweep of an object that wants the cells as well (their bit goes out next to the bins', which
+    go before it, and a cloud that does not fit the bins is repeated by cells)."""
+
+    __slots__ = ()
+
+    def __new__(cls, shifted, safe=False, bins=False, cells=False, keep=None, cells_too=False):
+        return super().__new__(cls, bool(shifted), bool(safe), bool(bins), bool(cells), keep, bool(cells_too))
+
+    def flags(self, speculative=False):
+        """The ``shifted`` word of obe_sweep_utility_keep(); ``speculative``: True — behind an undecided update,
+        'after_resample' — behind a resample, nothing to guess."""
+        return ((_lib.OBE_SWEEP_SHIFTED if self.shifted else 0) | (_lib.OBE_SWEEP_SAFE if self.safe else 0)
+                | (_lib.OBE_SWEEP_CELLS if self.cells or self.cells_too else 0)
+                | (_lib.OBE_SWEEP_BINS if self.bins else 0) | (_lib.OBE_SWEEP_BINS_KEPT if self.keep is True else 0)
+                | (0 if not speculative else _lib.OBE_SWEEP_NOWAIT if speculative == "after_resample"
+                   else _lib.OBE_SWEEP_SPECULATIVE))
+
+    def inputs(self):
+        """What a sweep's result depends on besides its data (the twin is never enqueued ahead: not an input)."""
+        return dict(shifted=self.shifted, cells=self.cells or self.cells_too, bins=self.bins, kept=self.keep)
+
+    def report(self, kappa):
+        """``last_sweep`` of a request that ended with this attempt."""
+        return dict(shifted=self.shifted, kappa=kappa, safe=self.safe, cells=self.cells, bins=self.bins,
+                    kept=self.keep is True)
+
+
 class SweepState:
     def __init__(self, io, limits):
         """``limits``: anything with KAPPA_ENTER, KAPPA_LEAVE, SAFE_STREAK, SAFE_RETRY (the owning object: read
@@ -69,6 +108,10 @@ class SweepState:
         self.unavailable = False      # the library refused the enqueue forms: never again for this object
         self.pending = Pending.NONE
         self.ticket = None
+        # expansion form (a copy or a restored object starts with neither mark: it has no keep buffer either)
+        self.bins_refused = None      # particles version of the cloud that did not fit the bins
+        self.bins_kept_for = None     # key (particles version, width, count) the kept grouping was made for
+        self._request = None          # the request in progress: (that key, its shifted repeat has gone out)
 
     # ------------------------------------------------------------------ form of the sweep kernel
     @property
@@ -116,6 +159,93 @@ class SweepState:
             self.unshifted = False
             return True
         return False
+
+    # ------------------------------------------------------------------ expansion form of an unshifted full sweep
+    @staticmethod
+    def _plan_takes(mode, plan):
+        """``plan``: the word of obe_sweep_cells_plan() / obe_sweep_bins_plan() (bit 0: valid, bit 1: worthwhile)."""
+        return mode != "never" and bool(plan & 1) and (mode == "always" or bool(plan & 2))
+
+    def cells_wanted(self, tuning, plan):
+        return self._plan_takes(tuning.get("sweep_cells", "auto"), plan)
+
+    def bins_wanted(self, tuning, plan, version):
+        """The bins stand down when ``sweep_cells`` is pinned (a caller who pins the cell form, either way, has
+        chosen the form) and for a cloud (``version``) that turned out not to fit them."""
+        mode = tuning.get("sweep_bins", "auto")
+        if mode != "always" and tuning.get("sweep_cells", "auto") != "auto":
+            return False
+        return self.bins_refused != version and self._plan_takes(mode, plan)
+
+    def bins_kept(self, key):
+        """Whether the keep buffer holds the grouping of exactly this cloud: set by the last bin sweep that was
+        collected with a finite kappa, never by one that was only enqueued."""
+        return self.bins_kept_for == key
+
+    def attempt_for(self, shifted, full, tuning, forms):
+        """The form a sweep starts in.  ``forms``: (cells plan word, bins plan word, key — what the bins' grouping
+        depends on, the particles version first), or None for a model without expansion forms.  They stand in for
+        the unshifted direct kernel of a full sweep only: every repeat, shifted or safe, is direct."""
+        if not full or shifted or forms is None:
+            return Attempt(shifted)
+        cells_plan, bins_plan, key = forms
+        cells = self.cells_wanted(tuning, cells_plan)
+        if not self.bins_wanted(tuning, bins_plan, key[0]):
+            return Attempt(False, cells=cells)
+        keep = self.bins_kept(key) if tuning.get("sweep_bins_keep", True) else None
+        return Attempt(False, bins=True, keep=keep, cells_too=cells)
+
+    def first_attempt(self, form, shifted, full, tuning, forms):
+        """Opens a request (a sweep somebody waits for).  Pinned to the twin — the fast form has left its range
+        SAFE_STREAK sweeps in a row: a property of the settings grid (its span against the model's width), not of
+        one cloud —: one shifted safe sweep, no fast attempt that is thrown away."""
+        self._request = (None if forms is None else forms[2], False)
+        return Attempt(True, safe=True) if form is Form.SAFE else self.attempt_for(shifted, full, tuning, forms)
+
+    def launched(self, attempt):
+        """``attempt`` goes out (also ahead of its request): a rebuild leaves nothing to rely on until it is
+        collected."""
+        if attempt.keep is False:
+            self.bins_kept_for = None
+
+    def keep_buffer_replaced(self):
+        self.bins_kept_for = None
+
+    def after(self, attempt, kappa, checked, mode, full):
+        """``attempt`` of the request in progress was collected with ``kappa``: the attempt that repeats it, or None
+        — its result stands.  The ladder is kept -> rebuild -> form without bins -> shifted -> safe twin, five
+        attempts at the most.  ``checked``: the fast form of this sweep can leave its range at all, then NaN says
+        so."""
+        if attempt.safe:
+            return None
+        key, repeated = self._request
+        if attempt.bins:
+            if attempt.keep is True and math.isnan(kappa):
+                # the kept grouping did not fit the cloud after all (the kernels check it themselves): forgotten, and
+                # the sweep is repeated as a rebuild — only a NaN from that one says that the cloud does not fit
+                self.bins_kept_for = None
+                return attempt._replace(keep=False)
+            if attempt.keep is not None and math.isfinite(kappa):
+                self.bins_kept_for = key                # (collected: the buffer describes these particles)
+            if math.isnan(kappa):
+                # the cloud does not fit the bins (its x0 / d span more than OBE_BIN_MAX of them, or one is not
+                # finite): a property of the particles alone, so nothing asks for bins again before the cloud is
+                # replaced, and the sweep is repeated in the form that would have run without them
+                self.bins_refused = key[0]
+                return Attempt(attempt.shifted, cells=attempt.cells_too)
+        poisoned = checked and math.isnan(kappa)
+        # (the kappa of the shifted repeat itself does not move the hysteresis: the next request's first sweep does)
+        if not repeated and self.sweep_reported_kappa(mode, full, attempt.shifted, kappa) and not poisoned:
+            self._request = (key, True)
+            return Attempt(True)
+        if poisoned:
+            # a model's branch-free batched divisions left their exact range somewhere (or the model really
+            # produces NaN): repeated with its always-in-range twin, shifted (a poisoned unshifted sweep skips
+            # the shifted fast repeat)
+            self.fast_form_left_its_range()
+            return Attempt(True, safe=True)
+        self.fast_form_held()
+        return None
 
     # ------------------------------------------------------------------ the update -> sweep pattern
     @property

@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _batch, _bounds, _design, _devrng, _interest, _lib, _predictive, _reading, _scoring
-from ._sweepstate import Form, Pending, SweepState, Ticket
+from ._sweepstate import Attempt, Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
 from .models import DeviceModel
@@ -241,6 +241,7 @@ class OptBayesExpt(ParticlePDF):
         self._hargs.keep(self._host_out)
         # which form / shift the next sweep uses, and the sweep pdf_update() enqueues ahead (_sweepstate.py)
         self._sweeps = SweepState(_SweepIO(self), self)
+        self._cells_plan = self._bins_plan = None       # (grid, plan word): _expansion_forms()
         if settings_shard is not None and self._device_model is not None:
             self._s_begin, self._s_end = settings_shard.bounds(self._n_settings)
         else:
@@ -844,10 +845,7 @@ class OptBayesExpt(ParticlePDF):
     def _sweep_inputs(self, shifted):
         """Everything the result of a full sweep of this object depends on besides the kernels: compared
         between the sweep enqueued ahead and the one being asked for (both must read the same)."""
-        return dict(cloud=(self._particles.version, self._weights.version), shifted=bool(shifted),
-                    cells=bool(not shifted and self._cell_form_wanted()),
-                    bins=bool(not shifted and self._bin_form_wanted()),
-                    kept=self._bins_kept_input(bool(not shifted and self._bin_form_wanted())),
+        return dict(cloud=(self._particles.version, self._weights.version), **self._sweep_attempt(shifted).inputs(),
                     noise=self._noise_token(), settings=(self._s_begin, self._s_end),
                     alias=self._parameters is self._particles,
                     cost_hook=_overridden(self, "cost_estimate", OptBayesExpt))
@@ -1091,104 +1089,26 @@ class OptBayesExpt(ParticlePDF):
         elif not speculate:
             self._drop_speculative_sweep()
         idx = None
-        n_draws = 0
         if not full:
             if self.N_DRAWS > self._ws_draws:       # more draws than particles (N_DRAWS is a public attribute):
                 self._alloc_scratch()               # the packed draws of the sweep need the room
             # consumes N_DRAWS uniforms (randdraw); its check of sum(w) waits for the sweep's own sync
             idx = self._draw_indices(self.N_DRAWS, defer_validation=True)
-            n_draws = self.N_DRAWS
-        n_local = self._s_end - self._s_begin
-        res = self.__dict__.get("_sweep_result")
-        if res is None:               # persistent host landing zone of the sweep result, pointers made once:
-            block = _lib.pinned_array(4)          # {best, index bits, kappa} in three consecutive words
-            best, best_idx, kappa = block[0:1], block.view(np.int64)[1:2], block[2:3]
-            res = self._sweep_result = (best, best_idx, kappa, _lib.host_ptr(best), _lib.host_ptr(best_idx),
-                                        _lib.host_ptr(kappa), block)
-        best, best_idx, kappa, p_best, p_best_idx, p_kappa, block = res
-        s_ptr = _P(self._settings_dev.data_ptr() + 8 * self._s_begin)
-
         if sharded and not speculate:
             every = int(self.tuning_parameters.get("replica_check_every", 64) or 0)
             self._sharded_sweeps += 1
             if every > 0 and self._sharded_sweeps % every == 0:
                 self.check_replicas()
-        result = {}
         # Nobody waits for this sweep: its caller wants the utility on the device (good_setting,
         # utility_variance), a draws-mode sweep is always shifted (kappa decides nothing) and the model's
         # fast form cannot leave its range.  Then the launch returns no host result and does not
         # synchronise; the deferred check of sum(w) happens at the caller's own synchronisation.
-        checked = self._sweep_needs_range_check(n_draws)
+        checked = self._sweep_needs_range_check(0 if idx is None else self.N_DRAWS)
         lazy = not want_best and not full and not sharded and not checked
         # (sharded: the 32-byte result record at the END of the workspace — include/obe_hip.h: OBE_WS_RESULT_TAIL —,
-        # which the update calls between a sweep enqueued ahead and its collection do not touch)
+        # which the update calls between a sweep enqueued ahead and its collection do not touch; kappa is the worst
+        # over all ranks, so every rank takes the same branch and the collectives stay in step)
         tail = self._ws[-6:-2] if sharded else None
-
-        def cells_for(shifted, safe=False):
-            # the cell form stands in for the unshifted direct kernel only: every repeat (shifted, safe) is direct
-            return full and not shifted and not safe and self._cell_form_wanted()
-
-        def bins_for(shifted, safe=False):
-            # ... and so does the bin form, which goes before the cells where both are wanted
-            return full and not shifted and not safe and self._bin_form_wanted()
-
-        def launch(shifted, safe=False, speculative=False):
-            result["bins"] = bins_for(shifted, safe)
-            result["cells"] = cells_for(shifted, safe) and not result["bins"]
-            # the bins' grouping of the cloud, kept in a buffer of this object's own from one sweep to the next
-            # (include/obe_hip.h: obe_sweep_utility_keep): reused while the key says it was made for these particles
-            keep = self._bins_keep_buffer() if result["bins"] else None
-            result["kept"] = keep is not None and self._bins_kept()
-            result["keep"] = keep is not None
-            if keep is not None and not result["kept"]:
-                self._bins_kept_for = None          # (being rebuilt: nothing to rely on until this sweep is collected)
-            # sharded: no host read here — the 32-byte result record is all-gathered from
-            # device memory and read back once, together with the other ranks' records
-            p, w = self._pw_tensors()
-            cost_t, cost_s = self._cost_device()
-            noise, noise_ld = self._noise_var_device()
-            # last, so that the moments kernels and the sweep are enqueued back to back (every idle
-            # microsecond before the sweep kernel also costs clock ramp-up inside it)
-            mom = self._moments_on_device()
-            no_host = sharded or lazy
-            stream = self._stream()
-            self._mlib.call("obe_sweep_utility_keep", self._model_struct, s_ptr, self._n_settings, n_local,
-                           _ptr(p), p.shape[1], self.n_particles, _ptr(w),
-                           None if idx is None else _ptr(idx), n_draws, _ptr(mom),
-                           (_lib.OBE_SWEEP_SHIFTED if shifted else 0) | (_lib.OBE_SWEEP_SAFE if safe else 0)
-                           | (_lib.OBE_SWEEP_CELLS if cells_for(shifted, safe) else 0)
-                           | (_lib.OBE_SWEEP_BINS if result["bins"] else 0)
-                           | (_lib.OBE_SWEEP_BINS_KEPT if result["kept"] else 0)
-                           | (0 if not speculative else _lib.OBE_SWEEP_NOWAIT if speculative == "after_resample"
-                              else _lib.OBE_SWEEP_SPECULATIVE),
-                           _ptr(noise), noise_ld, None if cost_t is None else _ptr(cost_t), cost_s,
-                           _ptr(self._yvar_dev), _ptr(self._utility_dev),
-                           None if no_host else p_best,
-                           None if no_host else p_best_idx,
-                           None if no_host else p_kappa,
-                           _ptr(self._ws), self._ws_bytes, stream,
-                           None if keep is None else _ptr(keep), 0 if keep is None else keep.numel() * 4)
-            if speculative:
-                # (waited for on the stream it was launched on; the sweep of a resampled cloud has nothing to guess)
-                state.enqueued(Ticket(self._sweep_inputs(shifted), None if sharded else p_best, block,
-                                      tail if sharded else None, stream, stream.value),
-                               certain=speculative == "after_resample")
-            else:
-                deliver(None if not sharded else tail)
-
-        def deliver(record):
-            if lazy:
-                result["best"] = None
-                kappa[0] = 0.0
-            elif sharded:
-                val, gidx, k = self._shard.combine_records(record, self._n_settings)
-                result["best"] = (val, gidx)
-                kappa[0] = k
-            else:
-                result["best"] = (float(best[0]), int(best_idx[0]) + self._s_begin)
-
-        # (sharded: kappa is the worst over all ranks, so every rank takes the same branch and the
-        # collectives stay in step)
         # Shift policy (full sweep only).  The unshifted kernel saves one FP64 instruction
         # per evaluation (12 % of the sweep) but loses accuracy in proportion to
         # kappa = (mean of y)^2 / var, which every sweep reports: measured ~1e-15 * kappa
@@ -1197,90 +1117,125 @@ class OptBayesExpt(ParticlePDF):
         # with the shift: the variance is always good to a few 1e-12.  (SweepState.sweep_reported_kappa)
         mode = self.tuning_parameters.get("sweep_shift", "auto")
         shifted = state.shifted_for_next_sweep(mode, full)
-        safe = False
         if speculate:
-            launch(shifted, speculative=speculate)
+            # (waited for on the stream it was launched on; the sweep of a resampled cloud has nothing to guess)
+            stream = self._launch_sweep(self._sweep_attempt(shifted, full), idx, sharded, speculative=speculate)
+            landing = self._sweep_landing()
+            state.enqueued(Ticket(self._sweep_inputs(shifted), None if sharded else landing[3], landing[6], tail,
+                                  stream, stream.value), certain=speculate == "after_resample")
             return None
         self._apply_range_hint()
         form = state.form_for_next_sweep()
         if lazy:
-            launch(True)
-            self.last_sweep = dict(shifted=True, kappa=float("nan"), safe=False, cells=False, bins=False,
-                                   kept=False)     # kappa was not read back
+            self._launch_sweep(Attempt(True), idx, True)
+            self.last_sweep = Attempt(True).report(float("nan"))     # kappa was not read back
             return None
-        if form is Form.FAST:
-            taken = self._take_speculative_sweep(shifted) if full else None
-            if taken is None:
-                launch(shifted)
-            else:
-                result["bins"] = bins_for(shifted)         # (part of the ticket's inputs: what was enqueued ahead)
-                result["cells"] = cells_for(shifted) and not result["bins"]
-                # (the buffer the enqueued call was given, if any: none is made here)
-                result["keep"] = result["bins"] and "_bins_keep" in self.__dict__ and self._bins_kept_input(True) is not None
-                result["kept"] = result["keep"] and self._bins_kept()
-                deliver(taken if sharded else None)
-            self._check_pending_total()
-            if result["kept"] and np.isnan(kappa[0]):
-                # the kept grouping did not fit the cloud after all (the kernels check it themselves): forgotten, and
-                # this sweep is repeated as a rebuild — only a NaN from that one says that the cloud does not fit the bins
-                self._bins_kept_for = None
-                launch(shifted)
-                self._check_pending_total()
-            if result["bins"] and result["keep"] and np.isfinite(kappa[0]):
-                self._bins_kept_for = self._bins_keep_key()       # (collected: the buffer describes these particles)
-            if result["bins"] and np.isnan(kappa[0]):
-                # the cloud does not fit the bins (its x0 / d span more than OBE_BIN_MAX of them, or one is not
-                # finite): that is a property of the particles alone, so nothing asks for bins again before the
-                # cloud is replaced, and this sweep is repeated in the form that would have run without them
-                self._bins_refused = self._particles.version
-                launch(shifted)
-                self._check_pending_total()
-            poisoned = checked and bool(np.isnan(kappa[0]))
-            if state.sweep_reported_kappa(mode, full, shifted, float(kappa[0])):
-                shifted = True
-                if not poisoned:          # (a poisoned sweep is repeated below anyway, with the twin)
-                    launch(True)
-                    poisoned = checked and bool(np.isnan(kappa[0]))
-            if poisoned:
-                # a model's branch-free batched divisions left their exact range somewhere (or the
-                # model really produces NaN): repeat with its always-in-range twin
-                safe = shifted = True
-                launch(True, safe=True)
-                state.fast_form_left_its_range()
-            else:
-                state.fast_form_held()
-        else:
-            # the fast form has left its range SAFE_STREAK sweeps in a row: that is a property of the
-            # settings grid (its span against the model's width), not of one cloud — stop paying for a
-            # fast attempt that is thrown away
+        # The form of the first attempt, and of every repeat that its kappa asks for, is SweepState's decision
+        # (first_attempt, after); here each attempt is launched — or, the first one, found enqueued ahead — and read.
+        attempt = state.first_attempt(form, shifted, full, self.tuning_parameters, self._expansion_forms())
+        taken = None
+        if attempt.safe:
             self._drop_speculative_sweep()
-            safe = shifted = True
-            launch(True, safe=True)
+        elif full:
+            taken = self._take_speculative_sweep(shifted)
+        while attempt is not None:
+            if taken is None:
+                self._launch_sweep(attempt, idx, sharded)
+            best, kappa = self._sweep_delivered(tail if taken is None else taken)
             self._check_pending_total()
-        self.last_sweep = dict(shifted=shifted, kappa=float(kappa[0]), safe=safe, cells=bool(result["cells"]),
-                               bins=bool(result["bins"]), kept=bool(result["bins"] and result["kept"]))
-        if want_best:
-            return result["best"]
-        return None
+            last, taken = attempt, None
+            attempt = state.after(last, kappa, checked, mode, full)
+        self.last_sweep = last.report(kappa)
+        return best if want_best else None
+
+    def _sweep_landing(self):
+        """The persistent host landing zone of the sweep result, pointers made once: the words {best, index bits,
+        kappa}, their addresses and the block they are three consecutive words of."""
+        res = self.__dict__.get("_sweep_result")
+        if res is None:
+            block = _lib.pinned_array(4)
+            best, best_idx, kappa = block[0:1], block.view(np.int64)[1:2], block[2:3]
+            res = self._sweep_result = (best, best_idx, kappa, _lib.host_ptr(best), _lib.host_ptr(best_idx),
+                                        _lib.host_ptr(kappa), block)
+        return res
+
+    def _launch_sweep(self, attempt, idx, no_host, speculative=False):
+        """One call of obe_sweep_utility_keep() over this rank's settings slice in the form ``attempt``; returns the
+        stream it went out on.  ``idx``: the draws of a draws-mode sweep (None: every particle, weighted);
+        ``no_host``: nothing lands in the host words — a sharded object's 32-byte result record is all-gathered
+        from device memory and read back once, together with the other ranks' records, and nobody waits for a
+        lazy sweep; ``speculative``: see Attempt.flags."""
+        # the bins' grouping of the cloud, kept in a buffer of this object's own from one sweep to the next
+        # (include/obe_hip.h: obe_sweep_utility_keep): reused while the key says it was made for these particles
+        keep = self._bins_keep_buffer() if attempt.keep is not None else None
+        self._sweeps.launched(attempt)
+        _, _, _, p_best, p_best_idx, p_kappa, _ = self._sweep_landing()
+        p, w = self._pw_tensors()
+        cost_t, cost_s = self._cost_device()
+        noise, noise_ld = self._noise_var_device()
+        # last, so that the moments kernels and the sweep are enqueued back to back (every idle
+        # microsecond before the sweep kernel also costs clock ramp-up inside it)
+        mom = self._moments_on_device()
+        stream = self._stream()
+        self._mlib.call("obe_sweep_utility_keep", self._model_struct,
+                        _P(self._settings_dev.data_ptr() + 8 * self._s_begin), self._n_settings,
+                        self._s_end - self._s_begin, _ptr(p), p.shape[1], self.n_particles, _ptr(w),
+                        None if idx is None else _ptr(idx), 0 if idx is None else self.N_DRAWS, _ptr(mom),
+                        attempt.flags(speculative),
+                        _ptr(noise), noise_ld, None if cost_t is None else _ptr(cost_t), cost_s,
+                        _ptr(self._yvar_dev), _ptr(self._utility_dev),
+                        None if no_host else p_best,
+                        None if no_host else p_best_idx,
+                        None if no_host else p_kappa,
+                        _ptr(self._ws), self._ws_bytes, stream,
+                        None if keep is None else _ptr(keep), 0 if keep is None else keep.numel() * 4)
+        return stream
+
+    def _sweep_delivered(self, record):
+        """((best value, best global index), kappa) of the sweep that has just been waited for; ``record``: a sharded
+        object's device record, combined with the other ranks' (kappa: the worst over all ranks)."""
+        if self._shard is not None:
+            val, gidx, k = self._shard.combine_records(record, self._n_settings)
+            return (val, gidx), float(k)
+        best, best_idx, kappa = self._sweep_landing()[:3]
+        return (float(best[0]), int(best_idx[0]) + self._s_begin), float(kappa[0])
+
+    def _sweep_attempt(self, shifted, full=True):
+        """The form a sweep of the present cloud starts in (the policy: SweepState.attempt_for)."""
+        return self._sweeps.attempt_for(shifted, full, self.tuning_parameters, self._expansion_forms())
+
+    def _expansion_forms(self):
+        """(cells plan word, bins plan word, key of the bins' grouping) for the unshifted full sweep of this object's
+        settings slice — include/obe_hip.h: obe_sweep_cells_plan, obe_sweep_bins_plan, each asked once per settings
+        grid and particle count —, or None: the forms are the one-peak Lorentzian's, and an empty slice has no grid."""
+        dm = self._device_model
+        if dm is None or not dm.cell_sweep or self._s_end <= self._s_begin:
+            return None
+        key = (self._s_begin, self._s_end, self.n_particles)
+        cells, bins = self._cells_plan, self._bins_plan
+        if cells is None or cells[0] != key:
+            x, n = self.allsettings[0, self._s_begin:self._s_end], self._s_end - self._s_begin
+            with np.errstate(all="ignore"):
+                lo, hi = float(np.min(x)), float(np.max(x))
+            cells = self._cells_plan = (key, int(self._mlib.cdll.obe_sweep_cells_plan(
+                lo, hi, float(self.cons[0]), n, self.n_particles)))
+            # (sharded: a poisoned bin sweep is repeated, and every rank must repeat it — kappa is the worst over all
+            # ranks —, so every rank takes this decision from the same figures: the whole grid and the longest slice)
+            if self._shard is not None:
+                x, n = self.allsettings[0], -(-self._n_settings // self._shard.world_size)
+                with np.errstate(all="ignore"):
+                    lo, hi = float(np.min(x)), float(np.max(x))
+            bins = self._bins_plan = (key, int(self._mlib.cdll.obe_sweep_bins_plan(
+                lo, hi, float(self.cons[0]), n, self.n_particles)))
+        return cells[1], bins[1], self._bins_keep_key()
 
     def _cell_form_wanted(self):
         """Whether an unshifted full sweep of this object's settings slice runs as cell expansions
         (include/obe_hip.h: OBE_SWEEP_CELLS; one-peak Lorentzian only).  ``tuning_parameters['sweep_cells']``:
         ``'auto'`` (default) — where obe_sweep_cells_plan() finds the grid within the cap AND the form worthwhile;
-        ``'always'`` — wherever it is valid; ``'never'``.  The helper is asked once per settings grid."""
-        mode = self.tuning_parameters.get("sweep_cells", "auto")
-        dm = self._device_model
-        if mode == "never" or dm is None or not dm.cell_sweep or self._s_end <= self._s_begin:
-            return False
-        key = (self._s_begin, self._s_end, self.n_particles)
-        plan = self.__dict__.get("_cells_plan")
-        if plan is None or plan[0] != key:
-            x = self.allsettings[0, self._s_begin:self._s_end]
-            with np.errstate(all="ignore"):
-                lo, hi = float(np.min(x)), float(np.max(x))
-            plan = self._cells_plan = (key, int(self._mlib.cdll.obe_sweep_cells_plan(
-                lo, hi, float(self.cons[0]), self._s_end - self._s_begin, self.n_particles)))
-        return bool(plan[1] & 1) and (mode == "always" or bool(plan[1] & 2))
+        ``'always'`` — wherever it is valid; ``'never'``."""
+        forms = self._expansion_forms()
+        return forms is not None and self._sweeps.cells_wanted(self.tuning_parameters, forms[0])
 
     def _bin_form_wanted(self):
         """Whether an unshifted full sweep of this object's settings slice runs as bin expansions of the particles
@@ -1289,27 +1244,8 @@ class OptBayesExpt(ParticlePDF):
         ``'sweep_cells'`` is ``'auto'`` too (a caller who pins the cell form, either way, has chosen the form);
         ``'always'`` — wherever the inputs are valid; ``'never'``.  A cloud that turned out not to fit the bins is
         not tried again: only a new cloud (a resample, set_pdf) is."""
-        mode = self.tuning_parameters.get("sweep_bins", "auto")
-        dm = self._device_model
-        if mode == "never" or dm is None or not dm.cell_sweep or self._s_end <= self._s_begin:
-            return False
-        if mode != "always" and self.tuning_parameters.get("sweep_cells", "auto") != "auto":
-            return False
-        if self.__dict__.get("_bins_refused") == self._particles.version:
-            return False
-        key = (self._s_begin, self._s_end, self.n_particles)
-        plan = self.__dict__.get("_bins_plan")
-        if plan is None or plan[0] != key:
-            # (sharded: a poisoned bin sweep is repeated, and every rank must repeat it — kappa is the worst over all
-            # ranks —, so every rank takes this decision from the same figures: the whole grid and the longest slice)
-            x, n = self.allsettings[0, self._s_begin:self._s_end], self._s_end - self._s_begin
-            if self._shard is not None:
-                x, n = self.allsettings[0], -(-self._n_settings // self._shard.world_size)
-            with np.errstate(all="ignore"):
-                lo, hi = float(np.min(x)), float(np.max(x))
-            plan = self._bins_plan = (key, int(self._mlib.cdll.obe_sweep_bins_plan(
-                lo, hi, float(self.cons[0]), n, self.n_particles)))
-        return bool(plan[1] & 1) and (mode == "always" or bool(plan[1] & 2))
+        forms = self._expansion_forms()
+        return forms is not None and self._sweeps.bins_wanted(self.tuning_parameters, forms[1], forms[2][0])
 
     def _bins_keep_key(self):
         """What the bins' grouping of the cloud depends on: the particle values (their version stamp never repeats:
@@ -1317,28 +1253,18 @@ class OptBayesExpt(ParticlePDF):
         return (self._particles.version, float(self.cons[0]), self.n_particles)
 
     def _bins_kept(self):
-        """Whether the keep buffer holds the grouping of exactly this cloud: set by the last bin sweep that was
-        collected with a finite kappa, never by one that was only enqueued."""
-        return self.__dict__.get("_bins_kept_for") == self._bins_keep_key()
-
-    def _bins_kept_input(self, bins):
-        """How a full sweep of this object uses the keep buffer, as one of the sweep's inputs: False — it (re)builds
-        the grouping, True — it reuses it, None — no buffer is passed at all."""
-        if not bins or not self.tuning_parameters.get("sweep_bins_keep", True):
-            return None
-        return self._bins_kept()
+        """Whether the keep buffer holds the grouping of exactly this cloud (SweepState.bins_kept)."""
+        return self._sweeps.bins_kept(self._bins_keep_key())
 
     def _bins_keep_buffer(self):
         """This object's keep buffer (one per rank of a sharded object; a copy or a restored object starts without
-        one and rebuilds on its first sweep), or None with ``tuning_parameters['sweep_bins_keep']`` False."""
-        if not self.tuning_parameters.get("sweep_bins_keep", True):
-            return None
+        one and rebuilds on its first sweep)."""
         keep = self.__dict__.get("_bins_keep")
         if keep is None or keep[0] != self.n_particles:
             nbytes = int(self._mlib.cdll.obe_sweep_bins_keep_bytes(self.n_particles))
             keep = self._bins_keep = (self.n_particles,
                                       torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self._device))
-            self._bins_kept_for = None
+            self._sweeps.keep_buffer_replaced()
         return keep[1]
 
     def _settings_per_lane(self, n_draws=0):

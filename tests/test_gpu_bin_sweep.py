@@ -156,6 +156,47 @@ def test_far_particle(obe):
     assert o._bin_form_wanted() and o._sweep_inputs(False)["bins"]
 
 
+def test_far_particle_launch_sequence(obe):
+    """The flags word of every obe_sweep_utility_keep() call over four requests on the cloud of test_far_particle:
+    what a request launches is decided from kappa alone (SweepState.after), so the sequence is the decision."""
+    from optbayesexpt_amd import _lib
+    x = np.linspace(1.5, 4.5, 257)
+    cloud, w = prior_cloud(513, 14), weights(513, 15)
+    cloud[0, 100] = 3.0 + 1e9 * D
+    w[100] = 0.0              # (the bins' span counts zero-weight particles too; a resample never draws this one)
+    w /= w.sum()
+    o = make(obe, x, cloud, w)
+    o.rng = np.random.default_rng(16)
+    lib, flags = o._mlib, []
+    call = lib.call
+
+    def recording(name, *args):
+        if name == "obe_sweep_utility_keep":
+            flags.append(args[11])                      # (include/obe_hip.h: the `shifted` word)
+        return call(name, *args)
+
+    lib.call = recording                                # (on the instance: the class's method comes back below)
+    try:
+        o.yvar_from_parameter_draws()                   # the cloud does not fit the bins: repeated pair by pair
+        first, flags[:] = list(flags), []
+        o.yvar_from_parameter_draws()                   # nothing asks for bins again
+        second, flags[:] = list(flags), []
+        o.resample()                                    # a new cloud (the far particle's weight is next to nothing)
+        o.yvar_from_parameter_draws()
+        third, flags[:] = list(flags), []
+        assert o.last_sweep["bins"] and o.last_sweep["kept"] is False, o.last_sweep
+        o.yvar_from_parameter_draws()
+        fourth = list(flags)
+        assert o.last_sweep["bins"] and o.last_sweep["kept"] is True, o.last_sweep
+    finally:
+        del lib.call
+    print("flags words:", first, second, third, fourth)
+    assert first == [_lib.OBE_SWEEP_BINS, 0]
+    assert second == [0]
+    assert third == [_lib.OBE_SWEEP_BINS]
+    assert fourth == [_lib.OBE_SWEEP_BINS | _lib.OBE_SWEEP_BINS_KEPT]
+
+
 def c_sweep(o, flags, s_begin, n_local, draw_idx=None):
     """obe_sweep_utility on a slice of the object's settings with its own cloud: (status, yvar, kappa, best index)."""
     import torch

@@ -562,6 +562,173 @@ def test_sweepstate_form_policy():
     assert st.form is ss.Form.SAFE
 
 
+# The expansion form of a sweep (Attempt) and the repeats of a request (SweepState.after).  KEY: what the owner says the
+# bins' grouping depends on, the particles version first; plan words as obe_sweep_*_plan() return them (1: valid,
+# 3: valid and worthwhile).
+_NAN = float("nan")
+_KEY = (7, 0.1, 100)
+
+
+def _forms(cells=False, bins=True, key=_KEY):
+    return (3 if cells else 0, 3 if bins else 0, key)
+
+
+def _request(st, kappas, forms, tuning=None, checked=False, mode="auto", full=True):
+    """One request, driven as OptBayesExpt._sweep_device drives it: the attempts in the order they go out."""
+    tuning = {} if tuning is None else tuning
+    attempt = st.first_attempt(st.form_for_next_sweep(), st.shifted_for_next_sweep(mode, full), full, tuning, forms)
+    attempts, kappas = [], list(kappas)
+    while attempt is not None:
+        st.launched(attempt)
+        attempts.append(attempt)
+        attempt = st.after(attempt, kappas.pop(0), checked, mode, full)
+    assert not kappas, kappas
+    return attempts
+
+
+def _kept_state(ss, unshifted=True):
+    st = _state(ss, _FakeIO())
+    st.unshifted, st.bins_kept_for = unshifted, _KEY
+    return st
+
+
+def test_sweepstate_repeat_ladder():
+    ss = _load_sweepstate()
+    A = ss.Attempt
+    reuse, rebuild, plain_bins = A(False, bins=True, keep=True), A(False, bins=True, keep=False), A(False, bins=True)
+    direct, shifted, twin = A(False), A(True), A(True, safe=True)
+
+    st = _kept_state(ss)                                  # kept bins, a good sweep: one attempt, the key stays
+    assert _request(st, [10.0], _forms()) == [reuse]
+    assert st.bins_kept_for == _KEY and st.bins_refused is None and st.unshifted
+
+    st = _kept_state(ss)                                  # the kept grouping did not fit: the same form as a rebuild
+    assert _request(st, [_NAN, 10.0], _forms()) == [reuse, rebuild]
+    assert st.bins_kept_for == _KEY and st.bins_refused is None
+
+    st = _kept_state(ss)                                  # ... nor does the cloud fit the bins: the cells, where wanted
+    both = _forms(cells=True)
+    assert _request(st, [_NAN, _NAN, 10.0], both) \
+        == [reuse._replace(cells_too=True), rebuild._replace(cells_too=True), A(False, cells=True)]
+    assert st.bins_refused == _KEY[0] and st.bins_kept_for is None
+    assert st.first_attempt(st.form, False, True, {}, both) == A(False, cells=True)       # the next request: no bins
+    changed = _forms(cells=True, key=(8, 0.1, 100))                                         # a new cloud: bins again
+    assert st.first_attempt(st.form, False, True, {}, changed) == rebuild._replace(cells_too=True)
+
+    st = _kept_state(ss)                                  # no cells, nothing checked: direct, then direct shifted
+    assert _request(st, [_NAN, _NAN, _NAN, 5.0], _forms()) == [reuse, rebuild, direct, shifted]
+    assert st.unshifted is False and st.bins_refused == _KEY[0] and st.safe_streak == 0
+
+    st = _state(ss, _FakeIO())                            # no keep buffer, checked: no shifted fast launch in between
+    st.unshifted = True
+    assert _request(st, [_NAN, _NAN, _NAN], _forms(), tuning={"sweep_bins_keep": False}, checked=True) \
+        == [plain_bins, direct, twin]
+    assert st.safe_streak == 1 and st.bins_kept_for is None and st.unshifted is False
+
+    st = _state(ss, _FakeIO())                            # bins above KAPPA_LEAVE: repeated shifted, the fast form held
+    st.unshifted, st.safe_streak = True, 2
+    assert _request(st, [5000.0, 2000.0], _forms(), checked=True) == [rebuild, shifted]
+    assert st.safe_streak == 0 and st.bins_kept_for == _KEY and st.unshifted is False
+
+    st = _state(ss, _FakeIO())                            # 'never': the direct unshifted repeat stands, NaN and all
+    assert _request(st, [_NAN, _NAN], _forms(), tuning={"sweep_bins_keep": False}, mode="never") \
+        == [plain_bins, direct]
+    assert st.bins_refused == _KEY[0] and st.safe_streak == 0
+
+    st = _state(ss, _FakeIO())                            # a shifted first attempt is direct, whatever is wanted
+    assert not st.unshifted
+    assert _request(st, [500.0], _forms(cells=True)) == [shifted]
+    assert st.unshifted is True and st.bins_kept_for is None
+
+    st = _kept_state(ss)                                  # pinned to the twin: one shifted safe attempt, nothing moves
+    st.safe_streak = 3
+    assert _request(st, [500.0], _forms(cells=True), checked=True) == [twin]
+    assert st.unshifted is True and st.safe_streak == 3 and st.bins_kept_for == _KEY
+
+    st = _kept_state(ss)                                  # a draws-mode sweep: shifted and direct
+    assert _request(st, [500.0], _forms(cells=True), mode="never", full=False) == [shifted]
+    assert st.unshifted is True and st.bins_kept_for == _KEY
+
+    st = _kept_state(ss)                                  # a rebuild that was only enqueued ahead, then dropped
+    ahead = st.attempt_for(False, True, {}, _forms(key=(8, 0.1, 100)))
+    assert ahead == rebuild
+    st.launched(ahead)
+    st.enqueued(ss.Ticket(_inputs(), "words", "block", None, "s1", 1))
+    st.drop(1)
+    assert st.bins_kept_for is None and st.bins_refused is None
+
+    st = _kept_state(ss)                                  # the longest chain: five attempts and no more
+    got = _request(st, [_NAN, _NAN, 5000.0, _NAN, 7.0], both, checked=True)
+    assert got == [reuse._replace(cells_too=True), rebuild._replace(cells_too=True), A(False, cells=True), shifted, twin]
+    assert st.safe_streak == 1 and st.bins_refused == _KEY[0] and st.bins_kept_for is None and not st.unshifted
+    assert got[-1].report(7.0) == dict(shifted=True, kappa=7.0, safe=True, cells=False, bins=False, kept=False)
+    assert reuse.report(10.0) == dict(shifted=False, kappa=10.0, safe=False, cells=False, bins=True, kept=True)
+
+
+def test_sweepstate_expansion_form_policy():
+    ss = _load_sweepstate()
+    st = _state(ss, _FakeIO())
+    A = ss.Attempt
+
+    def first(tuning, cells_plan, bins_plan, shifted=False, full=True):
+        return st.attempt_for(shifted, full, tuning, (cells_plan, bins_plan, _KEY))
+
+    assert first({}, 3, 3) == A(False, bins=True, keep=False, cells_too=True)         # bins go before the cells
+    assert first({}, 3, 1) == A(False, cells=True)                                      # valid, not worthwhile
+    assert first({"sweep_bins": "always"}, 1, 1) == A(False, bins=True, keep=False)
+    assert first({"sweep_bins": "always"}, 1, 0) == A(False) == first({"sweep_cells": "always"}, 0, 3)
+    assert first({"sweep_bins": "never"}, 3, 3) == A(False, cells=True)
+    # a caller who pins the cell form, either way, has chosen the form: the bins stand down unless pinned themselves
+    assert first({"sweep_cells": "never"}, 3, 3) == A(False)
+    assert first({"sweep_cells": "always"}, 1, 3) == A(False, cells=True)
+    assert first({"sweep_cells": "never", "sweep_bins": "always"}, 3, 1) == A(False, bins=True, keep=False)
+    assert first({"sweep_bins_keep": False}, 0, 3) == A(False, bins=True, keep=None)
+    # every shifted sweep, every draws-mode sweep and a model without such forms: direct
+    assert first({}, 3, 3, shifted=True) == A(True) and first({}, 3, 3, shifted=True, full=False) == A(True)
+    assert st.attempt_for(False, True, {"sweep_bins": "always"}, None) == A(False)
+    st.bins_refused = _KEY[0]
+    assert first({"sweep_bins": "always"}, 3, 3) == A(False, cells=True)
+    st.keep_buffer_replaced()
+    assert st.bins_kept_for is None and not st.bins_kept(_KEY)
+
+
+def _attempts_that_occur(ss, twin=True):
+    A = ss.Attempt
+    out = [A(False), A(True), A(False, cells=True)]
+    out += [A(False, bins=True, keep=k, cells_too=c) for k in (None, False, True) for c in (False, True)]
+    return out + ([A(True, safe=True)] if twin else [])
+
+
+def test_sweepstate_attempt_flags_word():
+    from optbayesexpt_amd import _lib
+    ss = _load_sweepstate()
+    A = ss.Attempt
+    S, T, C, B, K = (_lib.OBE_SWEEP_SHIFTED, _lib.OBE_SWEEP_SAFE, _lib.OBE_SWEEP_CELLS, _lib.OBE_SWEEP_BINS,
+                     _lib.OBE_SWEEP_BINS_KEPT)
+    words = {A(False): 0, A(True): S, A(True, safe=True): S | T, A(False, cells=True): C,
+             A(False, bins=True): B, A(False, bins=True, keep=False): B, A(False, bins=True, keep=True): B | K,
+             A(False, bins=True, cells_too=True): B | C, A(False, bins=True, keep=False, cells_too=True): B | C,
+             A(False, bins=True, keep=True, cells_too=True): B | C | K}
+    assert set(words) == set(_attempts_that_occur(ss))
+    for attempt, word in words.items():
+        assert attempt.flags() == word, attempt
+        if not attempt.safe:                              # (the twin is never enqueued ahead)
+            assert attempt.flags(True) == word | _lib.OBE_SWEEP_SPECULATIVE, attempt
+            assert attempt.flags("after_resample") == word | _lib.OBE_SWEEP_NOWAIT, attempt
+        assert not (attempt.cells and attempt.bins)
+        assert attempt.report(1.0)["cells"] is attempt.cells and attempt.report(1.0)["kept"] is (attempt.keep is True)
+
+
+def test_sweepstate_attempt_inputs_tell_the_attempts_apart():
+    ss = _load_sweepstate()
+    attempts = _attempts_that_occur(ss, twin=False)       # what can be enqueued ahead and asked for
+    for a in attempts:
+        assert set(a.inputs()) == {"shifted", "cells", "bins", "kept"}
+        for b in attempts:
+            assert (a.inputs() == b.inputs()) == (a == b), (a, b)
+            assert (dict(_inputs(), **a.inputs()) == dict(_inputs(), **b.inputs())) == (a == b), (a, b)
+
+
 def test_released_landing_zones_wait_in_limbo(monkeypatch):
     """Page-locked landing zones that an object releases are not handed back to the allocator while a kernel of
     that object may still write to them (_lib.pinned_array): the storage moves to a limbo list — with the device

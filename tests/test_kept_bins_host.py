@@ -47,12 +47,27 @@ def test_audit_rule_of_the_keep_entry_point_is_the_sweeps():
 
 
 def test_the_key_follows_the_particles_the_width_and_the_count():
+    from optbayesexpt_amd._sweepstate import SweepState
     fake = types.SimpleNamespace(_particles=types.SimpleNamespace(version=7), cons=np.array([0.1]), n_particles=100,
-                                 tuning_parameters={})
-    for name in ("_bins_keep_key", "_bins_kept", "_bins_kept_input"):
+                                 tuning_parameters={"sweep_bins": "always"}, KAPPA_ENTER=1000.0, KAPPA_LEAVE=3000.0,
+                                 SAFE_STREAK=3, SAFE_RETRY=64)
+    fake._sweeps = SweepState(None, fake)            # (the mark and what an attempt does with it live there)
+    for name in ("_bins_keep_key", "_bins_kept"):
         setattr(fake, name, types.MethodType(getattr(OptBayesExpt, name), fake))
+
+    def _bins_kept_input(bins):
+        """How a full sweep uses the keep buffer, as one of the sweep's inputs (``bins``: the plan takes them)."""
+        forms = (0, 1 if bins else 0, fake._bins_keep_key())
+        return fake._sweeps.attempt_for(False, True, fake.tuning_parameters, forms).inputs()["kept"]
+
+    fake._bins_kept_input = _bins_kept_input
     assert not fake._bins_kept() and fake._bins_kept_input(True) is False and fake._bins_kept_input(False) is None
-    fake._bins_kept_for = fake._bins_keep_key()
+    # (set as the object sets it: a bin sweep that passed the buffer is collected with a finite kappa)
+    rebuild = fake._sweeps.first_attempt(fake._sweeps.form, False, True, fake.tuning_parameters,
+                                         (0, 1, fake._bins_keep_key()))
+    assert rebuild.bins and rebuild.keep is False
+    assert fake._sweeps.after(rebuild, 10.0, False, "never", True) is None
+    assert fake._sweeps.bins_kept_for == fake._bins_keep_key()
     assert fake._bins_kept() and fake._bins_kept_input(True) is True
     fake._particles.version = 8                       # a resample, set_pdf, a write to the particles
     assert not fake._bins_kept()
