@@ -11,6 +11,6 @@ host-callable model.  The names are those the reference exports (optbayesexpt/__
 without the TCP server and socket, which are outside this package's scope.
 """
 from optbayesexpt_amd import (MeasurementSimulator, OptBayesExpt, OptBayesExptNoiseParameter,      # noqa: F401
-                              OptBayesExptSweeper, ParticlePDF, models, obe_base, obe_noiseparam, obe_utils,
-                              particlepdf, trace_sort)
+                              OptBayesExptSignalNoise, OptBayesExptSweeper, ParticlePDF, models, obe_base,
+                              obe_noiseparam, obe_signalnoise, obe_utils, particlepdf, trace_sort)
 from optbayesexpt_amd import __version__                                                            # noqa: F401

@@ -989,6 +989,43 @@ OBE_API int obe_design_interest_step(const double* d_cross, int64_t pivot_index,
                              double cost, const uint8_t* d_taken, double* d_gain, double* d_utility, double* d_best,
                              void* stream);
 
+/* ---- measurement noise that depends on the signal (extension) ----
+ * Every other call takes the noise of a reading as a number per channel or as a parameter row.  The reference names the
+ * case neither covers and leaves it out (obe_base.py:542-564: noise that "depends on the measurement value, like
+ * root(N), Poisson-like counting noise" needs the noise model averaged over the distribution).  Here the noise variance
+ * of a reading whose noise-free value is y is, per channel c of the model,
+ *   nu_c(y) = a_c + b_c |y| + c_c y^2
+ * h_noise_coef: 3 doubles per channel of the model, {a, b, c} channel after channel; each finite and >= 0, and in every
+ * channel one of them > 0 (else -1 before any launch).  y_c,i = what obe_eval_over_particles writes, bit for bit.  All
+ * results land in the caller's DEVICE buffers, nothing is waited for.
+ * d_lik (n_particles,): what obe_bayes_update_lik multiplies the weights by,
+ *   L_i = prod_{c < n_lik_channels} exp(-(y_c,i - h_y_meas[c])^2 / (2 nu_c(y_c,i))) / sqrt(nu_c(y_c,i))
+ * (obe_base.py:418-461 with sigma^2 = nu: no 1 / sqrt(2 pi), channels truncated as :453-455), as one exp of the summed
+ * exponent over one product of square roots, then L^choke unless choke is NaN.  A particle with a nu_c that is not > 0
+ * or not finite gets L = 0.  d_y == NULL: the model is evaluated at h_setting (n_setdims values; NULL: zeros) on the
+ * cloud d_particles; d_y given, (C, n_particles) rows ld_y apart with C the model's channels: those values are used and
+ * neither d_particles nor h_setting is read.  Both forms give the same bits.  Lane <-> particle, one stream over the
+ * cloud. */
+OBE_API int obe_signal_noise_likelihood(const obe_model* m, const double* d_y, int64_t ld_y,
+                                const double* d_particles, int64_t ld_p, int64_t n_particles, const double* h_setting,
+                                const double* h_y_meas, const double* h_noise_coef, int32_t n_lik_channels, double choke,
+                                double* d_lik, void* stream);
+/* d_noise_var (C, n_settings) = nu_bar_c(x_s) = a_c + b_c sum w |y_c| / W + c_c sum w y_c^2 / W over the whole weighted
+ * cloud, W = sum w: the noise variance a sweep divides by (obe_sweep_utility's d_noise_var with noise_ld = n_settings).
+ * NaN and negative weights count as zero, a particle of zero weight contributes nothing whatever its y is, W == 0 gives
+ * NaN.  d_settings (n_setdims, n_settings) with row stride ld_s: a slice of a grid is its first column's address with
+ * the grid's stride.  obe_predictive_moments' geometry (lane = setting, the particles of a chunk one after the other,
+ * setting tiles x particle chunks) in ONE pass: both sums are of non-negative terms and need no centring, and W rides
+ * along.  Chunk partials are folded in chunk order: no atomics, the same bits from run to run — and for a slice the bits
+ * of those columns of the whole grid's call while the cloud decides the number of chunks (n_particles <= 256 x 8192 /
+ * the grid's tiles of 64 settings).  d_ws: obe_signal_noise_workspace_bytes(n_particles, n_settings, the model's
+ * channels) bytes, a buffer of its own; the size does not shrink when an argument grows. */
+OBE_API int64_t obe_signal_noise_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels);
+OBE_API int obe_signal_noise_variance(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                              const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                              const double* h_noise_coef, double* d_noise_var, void* d_ws, int64_t ws_bytes,
+                              void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

@@ -142,7 +142,8 @@ MODEL_ENTRY_POINTS = ("obe_model_validate", "obe_workspace_bytes", "obe_sweep_se
                       "obe_predictive_reading_workspace_bytes", "obe_predictive_reading_quantiles",
                       "obe_output_covariance_workspace_bytes", "obe_output_covariance",
                       "obe_records_loglik_workspace_bytes", "obe_records_loglik",
-                      "obe_output_cross_covariance_workspace_bytes", "obe_output_cross_covariance")
+                      "obe_output_cross_covariance_workspace_bytes", "obe_output_cross_covariance",
+                      "obe_signal_noise_likelihood", "obe_signal_noise_workspace_bytes", "obe_signal_noise_variance")
 
 
 class HipLib:

@@ -44,6 +44,8 @@ LIBRARY_ATTRIBUTES = frozenset((
     "last_batch_design",
     # OptBayesExptNoiseParameter
     "noise_parameter_index",
+    # OptBayesExptSignalNoise
+    "noise_floor", "noise_gain", "noise_relative",
     # OptBayesExptSweeper
     "sweep_settings", "start_stop_subsample", "start_stop_indices", "start_stop_choice_indices", "start_stop_values",
     "cost_of_new_sweep", "last_sweep_batches",
@@ -55,9 +57,10 @@ _SELECTION = {"opt_setting": "optimal", "good_setting": "good", "random_setting"
 def _library_classes():
     from .obe_base import OptBayesExpt
     from .obe_noiseparam import OptBayesExptNoiseParameter
+    from .obe_signalnoise import OptBayesExptSignalNoise
     from .particlepdf import ParticlePDF
     from .sweeper import OptBayesExptSweeper
-    return OptBayesExptSweeper, OptBayesExptNoiseParameter, OptBayesExpt, ParticlePDF
+    return OptBayesExptSweeper, OptBayesExptNoiseParameter, OptBayesExptSignalNoise, OptBayesExpt, ParticlePDF
 
 
 def library_class(cls):
@@ -139,6 +142,7 @@ def snapshot(obj, on_device=False):
     (``copy.deepcopy``)."""
     from .obe_base import OptBayesExpt
     from .obe_noiseparam import OptBayesExptNoiseParameter
+    from .obe_signalnoise import OptBayesExptSignalNoise, state_fields
     from .sweeper import OptBayesExptSweeper
     settle(obj)
     cls = type(obj)
@@ -184,6 +188,8 @@ def snapshot(obj, on_device=False):
     if isinstance(obj, OptBayesExptNoiseParameter):
         st["noise_parameter_index"] = np.array(obj.noise_parameter_index)
         st["constraint_count"] = obj.last_constraint_count
+    if isinstance(obj, OptBayesExptSignalNoise):
+        st["signal_noise"] = state_fields(obj)
     if isinstance(obj, OptBayesExptSweeper):
         st["sweeper"] = {k: getattr(obj, k) for k in ("sweep_settings", "start_stop_subsample", "start_stop_indices",
                                                       "start_stop_choice_indices", "start_stop_values",
@@ -216,6 +222,7 @@ def restore(state, device=None, settings_shard=None, into=None):
     (collective: every rank restores the same state)."""
     from .obe_base import OptBayesExpt
     from .obe_noiseparam import OptBayesExptNoiseParameter
+    from .obe_signalnoise import OptBayesExptSignalNoise, kwargs_from_state
     from .sweeper import OptBayesExptSweeper
     check_version(state)
     cls = type(into) if into is not None else _resolve(state["cls"])
@@ -246,6 +253,8 @@ def restore(state, device=None, settings_shard=None, into=None):
             base.__init__(obj, *args, state["noise_parameter_index"], **kw)
         elif base is OptBayesExptNoiseParameter:
             base.__init__(obj, *args, noise_parameter_index=state["noise_parameter_index"], **kw)
+        elif base is OptBayesExptSignalNoise:
+            base.__init__(obj, *args, **kwargs_from_state(state["signal_noise"]), **kw)
         else:
             base.__init__(obj, *args, **kw)
     dev = obj._device
