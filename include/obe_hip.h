@@ -309,13 +309,15 @@ OBE_API int obe_systematic_indices(const double* d_cdf, int64_t n, double u0, in
  * of entries a draw's bucket spans — the same indices, ~3 instead of ~11 cold accesses per draw. */
 OBE_API int obe_cdf_search(const double* d_cdf, int64_t n, const double* d_uniforms, int64_t n_draws,
                    int64_t* d_idx_out, void* d_ws, int64_t ws_bytes, void* stream);
-/* randdraw gather: d_out (D, n_draws) = particles[:, idx]  (particlepdf.py:332-343). */
+/* randdraw gather: d_out (D, n_draws) = particles[:, idx]  (particlepdf.py:332-343).  An index outside
+ * [0, n_particles) reads the nearest end of the cloud (particle 0 or n_particles - 1): nothing is read out of bounds. */
 OBE_API int obe_gather_columns(const double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
                        const int64_t* d_idx, int64_t n_draws,
                        double* d_out, int64_t ld_out, void* stream);
 /* resample(): new[i,p] = old[i, idx[p]] + sum_j z[p,j] F[i,j]   (F = u*sqrt(s) of the
  * SVD of (1-a^2) cov, h_factor row-major D*D; z = standard normals (N, D) row-major);
  * if scale: new = new*a + mean[i]*(1-a)   (particlepdf.py:296-305).  Then weights = 1/N.
+ * An idx[p] outside [0, n_particles) reads the nearest end of the cloud (particle 0 or n_particles - 1).
  * d_ws (nullable): with 8 * n_dims * n_particles bytes of scratch a large cloud is first copied
  * to (N, D) order, so that the gather of a particle touches one or two 64-byte sectors instead
  * of n_dims of them. */
