@@ -279,6 +279,13 @@ inline int make_bounds_arg(BoundsArg& ba, const int32_t* h_rows, const double* h
     return 0;
 }
 
+// lane `lane` (wave-uniform) of x, the same value in every lane
+__device__ __forceinline__ double readlane_f64(double x, int lane) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
+    return __hiloint2double(hi, lo);
+}
+
 // ---- reductions: wave shuffle, then 4 partials through LDS; fixed order => deterministic
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

@@ -652,9 +652,45 @@ struct LorentzBins : LorentzSeries {
             if (k + 1 < kOrder) e *= eps;
         }
     }
-    // one bin's share of a setting's two moments from its folded row (M1_k at k, M2_k at kOrder + k, H3_k at
-    // 2 kOrder + k), s = tau_b - tau: each series summed from the highest order down
-    __device__ __forceinline__ static void evaluate(const double* __restrict__ row, double s, double& t1, double& t2) {
+    // A bin's folded row (M1_k at k, M2_k at kOrder + k, H3_k at 2 kOrder + k, C1, C2 last) is the same for the 64
+    // settings of a wavefront: it lives in registers ACROSS the lanes and every use names the lane that holds the
+    // coefficient, so a series step costs no memory access ("The row of a bin in the lanes").
+    // Every 16-lane row of the wavefront holds a copy: register i, lane l: coefficient 16 i + (l & 15).  The use is
+    // the multiply-add itself, v_fmac_f64 with the DPP source row_newbcast:j (lane j of the own 16-lane row).  The
+    // registers are written by loads alone: a VGPR that a VALU instruction wrote may not be read through DPP in the
+    // next two instructions, and nothing looks for that inside inline assembly.  All 64 lanes must be active.
+    static constexpr int kLaneRegs = (kCoefs + 15) / 16;
+    struct LaneRow { double v[kLaneRegs]; };
+    __device__ __forceinline__ static void load_row(const double* __restrict__ row, int lane, LaneRow& x) {
+#pragma unroll
+        for (int i = 0; i < kLaneRegs; ++i) {
+            const int j = 16 * i + (lane & 15);
+            x.v[i] = row[j < kCoefs ? j : kCoefs - 1];            // (beyond the row: never named by a use)
+        }
+    }
+    template <int J>   // fma(coefficient J of the row, x, t)
+    __device__ __forceinline__ static double fma_coef(const LaneRow& row, double x, double t) {
+        static_assert(J >= 0 && J < kCoefs, "a coefficient of the row");
+        asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+            : "+v"(t) : "v"(row.v[J >> 4]), "v"(x), "n"(J & 15));
+        return t;
+    }
+    // C1 += row[3 kOrder], C2 += row[3 kOrder + 1]: fma(c, 1, C) is c + C, rounded once
+    __device__ __forceinline__ static void add_constants(const LaneRow& row, double& C1, double& C2) {
+        C1 = fma_coef<3 * kOrder>(row, 1.0, C1);
+        C2 = fma_coef<3 * kOrder + 1>(row, 1.0, C2);
+    }
+    template <int K>   // orders K, K - 1, ..., 0 of the three series
+    __device__ __forceinline__ static void sum_down(const LaneRow& row, const double (&r)[kOrder],
+                                                    const double (&g)[kOrder], double& t1, double& t2) {
+        t1 = fma_coef<K>(row, r[K], t1);
+        t2 = fma_coef<kOrder + K>(row, r[K], t2);
+        t2 = fma_coef<2 * kOrder + K>(row, g[K], t2);
+        if constexpr (K > 0) sum_down<K - 1>(row, r, g, t1, t2);
+    }
+    // one bin's share of a setting's two moments from its folded row, s = tau_b - tau: each series summed from the
+    // highest order down
+    __device__ __forceinline__ static void evaluate(const LaneRow& row, double s, double& t1, double& t2) {
         double r[kOrder], g[kOrder];
         double A, B, Brp = 0.0, Bgp = 0.0;
         start(s, r[0], A, B);
@@ -667,12 +703,7 @@ struct LorentzBins : LorentzSeries {
         }
         t1 = 0.0;
         t2 = 0.0;
-#pragma unroll
-        for (int k = kOrder - 1; k >= 0; --k) {
-            t1 = fma(row[k], r[k], t1);
-            t2 = fma(row[kOrder + k], r[k], t2);
-            t2 = fma(row[2 * kOrder + k], g[k], t2);
-        }
+        sum_down<kOrder - 1>(row, r, g, t1, t2);
     }
 };
 

@@ -142,12 +142,6 @@ __global__ __launch_bounds__(kBlock) void scan_write_cdf(const double* __restric
     }
 }
 
-__device__ __forceinline__ double readlane_f64(double x, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
-    return __hiloint2double(hi, lo);
-}
-
 // Strict mode: c_i = fl(c_{i-1} + w_i) in index order, exactly np.cumsum.  One
 // wavefront: a coalesced 64-wide load, then 64 dependent adds fed by v_readlane.
 __global__ __launch_bounds__(kWave) void cdf_strict_kernel(const double* __restrict__ w, int64_t n,

@@ -720,7 +720,7 @@ __global__ __launch_bounds__(kBlock) void cell_eval_kernel(SweepArgs a, const Ce
 //   bin_moments_kernel   lane <-> draw within one item (kBinChunk consecutive draws of ONE bin), 3 P + 2 running sums
 //                        per lane, reduced over the lanes once per item (halving_reduce: a butterfly's tree).
 //   bin_fold_kernel      a bin's items summed in a fixed order (fold_in_order).
-//   bin_eval_kernel      lane <-> setting, the bins' rows through LDS, bins in order, one or several wavefronts per
+//   bin_eval_kernel      lane <-> setting, a bin's row across the lanes, bins in order, one or several wavefronts per
 //                        64 settings (plan_bin_eval_waves); writes part1 / part2 as ONE chunk and cs_out = 0, as
 //                        cell_eval_kernel does.
 // No floating-point atomics; every sum has a fixed association, so two calls on the same inputs give the same bits.
@@ -1127,17 +1127,21 @@ __global__ __launch_bounds__(kBinFoldGroups * kWave) void bin_fold_kernel(BinSwe
     if (threadIdx.x < kWave && live) q.coef[(int64_t)bin * LB::kRow + co] = t;
 }
 
-// `ran` receives `seq`, as in cell_eval_kernel.  The rows come kBinTile bins at a time through LDS, the next tile's
-// global loads in flight while this one is evaluated: a row fetched by the wavefront that needs it (scalar loads, one
-// L2 round trip per bin and wavefront, one wavefront per SIMD at 65 536 settings) left the kernel waiting four
-// fifths of its time.
-// A workgroup holds G groups of 64 settings (lane <-> setting) and W wavefronts for each of them; all share the tile.
-// <4, 1>: a workgroup of kBlock threads, every wavefront walks every occupied bin of its own group.  W > 1: of every
-// tile wavefront w of a group evaluates the occupied bins t = w, w + W, ... and leaves their t1, t2 in LDS, and behind
-// a barrier wavefront 0 of the group adds them in bin order, as the one wavefront of W = 1 does: the same numbers in
-// the same order, the same bits, and the one dependent chain per bin is walked by W wavefronts at once
-// (plan_bin_eval_waves; DESIGN.md, "Several wavefronts per group of settings").  Every wavefront of a workgroup takes
-// the same way through the barriers: nbins and the abort word (read once per workgroup where W > 1) are the same for all.
+// `ran` receives `seq`, as in cell_eval_kernel.  A bin's row is the same for the 64 settings of a wavefront, so it is
+// held in registers across the lanes and named lane by lane where it is used (obe_models.h: LorentzBins::LaneRow): a
+// wavefront fetches the rows of its own bins from q.coef (at most OBE_BIN_MAX rows of 688 bytes, the same lines for
+// every wavefront of the chip), the row of its next occupied bin before it evaluates the current one, and the series
+// sums wait for no memory.  (The rows used to come through an LDS tile: one exposed LDS round trip per series step,
+// DESIGN.md.)  Two register sets take turns, so that no row register is ever copied.  The occupied bins are two
+// ballots over binstart (lane <-> bin), walked lowest first.
+// A workgroup holds G groups of 64 settings (lane <-> setting) and W wavefronts for each of them.
+// <4, 1>: a workgroup of kBlock threads, every wavefront walks every occupied bin of its own group; no LDS, no barrier.
+// W > 1: of every tile of kBinTile bins wavefront w of a group evaluates the occupied bins t = w, w + W, ... and leaves
+// their t1, t2 in LDS, and behind a barrier wavefront 0 of the group adds them in bin order, as the one wavefront of
+// W = 1 does: the same numbers in the same order, the same bits, and the one dependent chain per bin is walked by W
+// wavefronts at once (plan_bin_eval_waves; DESIGN.md, "Several wavefronts per group of settings").  Every wavefront of
+// a workgroup passes two barriers per tile of the plan, whichever bins it owns: nbins and the abort word (read once
+// per workgroup where W > 1) are the same for all.  All 64 lanes stay active to the end (LaneRow).
 constexpr int kBinTile = 16;
 template <int G, int W>
 __global__ __launch_bounds__(G * W * kWave, W == 1 ? 1 : 3)           // (W > 1: registers for three wavefronts per SIMD)
@@ -1146,9 +1150,7 @@ void bin_eval_kernel(SweepArgs a, BinSweepPtrs q, unsigned seq) {
     constexpr int kThreads = G * W * kWave;
     static_assert(W > 1 || kThreads == kBlock, "W = 1 is the workgroup of four groups");
     static_assert((G * W) % 4 == 0, "whole wavefronts for every SIMD of the CU (plan_bin_eval_waves)");
-    constexpr int kTileDoubles = kBinTile * LB::kRow, kPer = (kTileDoubles + kThreads - 1) / kThreads;
-    __shared__ double tile[kTileDoubles];
-    __shared__ int occupied[kBinTile];
+    static_assert(LB::kMaxBins <= 2 * kWave && kWave % kBinTile == 0, "two ballots name the occupied bins");
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
     const int grp = wave % G, wid = wave / G;             // wavefront `wid` of group `grp`
@@ -1173,61 +1175,94 @@ void bin_eval_kernel(SweepArgs a, BinSweepPtrs q, unsigned seq) {
         Lorentz<1>::prep_setting(a.settings + (s < a.ns ? s : a.ns - 1), a.m, &tau);
         const double origin = q.plan->origin;
         const double* __restrict__ coef = q.coef;
-        const int total = nbins * LB::kRow;
-        double nxt[kPer];
-        int nxt_occ = 0;
-        // (the row of an empty bin was never written: it is fetched with the others and never used)
-        auto fetch = [&](int b0) {
-#pragma unroll
-            for (int u = 0; u < kPer; ++u) {
-                const int e = b0 * LB::kRow + u * kThreads + (int)threadIdx.x;
-                nxt[u] = u * kThreads + (int)threadIdx.x < kTileDoubles && e < total ? coef[e] : 0.0;
-            }
-            const int b = b0 + (int)threadIdx.x;
-            nxt_occ = (int)threadIdx.x < kBinTile && b < nbins ? q.binstart[b + 1] != q.binstart[b] : 0;
-        };
-        fetch(0);
-        double a1 = 0.0, a2 = 0.0, C1 = 0.0, C2 = 0.0;
-        for (int b0 = 0; b0 < nbins; b0 += kBinTile) {
-            __syncthreads();                                      // the previous tile has been evaluated (and summed)
-#pragma unroll
-            for (int u = 0; u < kPer; ++u)
-                if (u * kThreads + (int)threadIdx.x < kTileDoubles) tile[u * kThreads + threadIdx.x] = nxt[u];
-            if (threadIdx.x < kBinTile) occupied[threadIdx.x] = nxt_occ;
-            __syncthreads();
-            if (b0 + kBinTile < nbins) fetch(b0 + kBinTile);
-            if constexpr (W == 1) {
-                for (int t = 0; t < kBinTile; ++t) {
-                    if (!__builtin_amdgcn_readfirstlane(occupied[t])) continue;       // (wave-uniform; beyond nbins: 0)
-                    const double* row = tile + t * LB::kRow;
-                    double t1, t2;
-                    LB::evaluate(row, LB::centre(origin, b0 + t) - tau, t1, t2);
-                    a1 += t1;
-                    a2 += t2;
-                    C1 += row[3 * LB::kOrder];
-                    C2 += row[3 * LB::kOrder + 1];
+        // (the row of an empty bin was never written: it is never fetched)
+        const int* __restrict__ start = q.binstart;
+        const bool here0 = lane < nbins && start[lane + 1] != start[lane];
+        const bool here1 = kWave + lane < nbins && start[kWave + lane + 1] != start[kWave + lane];
+        const uint64_t occ0 = __ballot(here0), occ1 = __ballot(here1);            // bins 0-63, 64-127
+        uint64_t own0 = occ0, own1 = occ1;                                        // ... that this wavefront evaluates
+        double c1col[2] = {0.0, 0.0}, c2col[2] = {0.0, 0.0};                      // W > 1, wavefront 0: lane <-> bin
+        if constexpr (W > 1) {
+            uint64_t mine = 0;
+            for (int t = wid; t < kBinTile; t += W) mine |= (uint64_t)1 << t;
+            mine |= mine << 16;
+            mine |= mine << 32;
+            own0 &= mine;
+            own1 &= mine;
+            if (wid == 0) {
+                if (here0) {
+                    c1col[0] = coef[lane * LB::kRow + 3 * LB::kOrder];
+                    c2col[0] = coef[lane * LB::kRow + 3 * LB::kOrder + 1];
                 }
-            } else {
-                for (int t = wid; t < kBinTile; t += W) {        // (a wavefront that owns no occupied bin of the tile: none)
-                    if (!__builtin_amdgcn_readfirstlane(occupied[t])) continue;
-                    double t1, t2;
-                    LB::evaluate(tile + t * LB::kRow, LB::centre(origin, b0 + t) - tau, t1, t2);
-                    term[t * kWave + lane] = t1;
-                    term[(kBinTile + t) * kWave + lane] = t2;
-                }
-                __syncthreads();                                  // the tile's terms are in LDS
-                if (wid == 0) {
-                    for (int t = 0; t < kBinTile; ++t) {
-                        if (!__builtin_amdgcn_readfirstlane(occupied[t])) continue;   // skipped, not added as zero
-                        const double* row = tile + t * LB::kRow;
-                        a1 += term[t * kWave + lane];
-                        a2 += term[(kBinTile + t) * kWave + lane];
-                        C1 += row[3 * LB::kOrder];
-                        C2 += row[3 * LB::kOrder + 1];
-                    }
+                if (here1) {
+                    c1col[1] = coef[(kWave + lane) * LB::kRow + 3 * LB::kOrder];
+                    c2col[1] = coef[(kWave + lane) * LB::kRow + 3 * LB::kOrder + 1];
                 }
             }
         }
+        auto next_bin = [&]() {                                   // the lowest bin left, or -1 (wave-uniform)
+            int b = -1;
+            if (own0) {
+                b = __builtin_ctzll(own0);
+                own0 &= own0 - 1;
+            } else if (own1) {
+                b = kWave + __builtin_ctzll(own1);
+                own1 &= own1 - 1;
+            }
+            return b;
+        };
+        double a1 = 0.0, a2 = 0.0, C1 = 0.0, C2 = 0.0;
+        int tile = 0;                                             // W > 1: the tile whose terms are being written
+        auto close_tile = [&]() {
+            __syncthreads();                                      // the tile's terms are in LDS
+            if (wid == 0) {
+                const int half = tile * kBinTile / kWave;
+                const uint64_t occ = half ? occ1 : occ0;
+                for (int t = 0; t < kBinTile; ++t) {
+                    const int l = (tile * kBinTile + t) & (kWave - 1);
+                    if (!((occ >> l) & 1)) continue;              // skipped, not added as zero
+                    a1 += term[t * kWave + lane];
+                    a2 += term[(kBinTile + t) * kWave + lane];
+                    C1 += readlane_f64(half ? c1col[1] : c1col[0], l);
+                    C2 += readlane_f64(half ? c2col[1] : c2col[0], l);
+                }
+            }
+            __syncthreads();                                      // ... and summed: the next tile's may replace them
+            ++tile;
+        };
+        auto evaluate = [&](const LB::LaneRow& row, int b) {
+            double t1, t2;
+            if constexpr (W == 1) {
+                LB::evaluate(row, LB::centre(origin, b) - tau, t1, t2);
+                a1 += t1;
+                a2 += t2;
+                LB::add_constants(row, C1, C2);
+            } else {
+                while (tile < b / kBinTile) close_tile();
+                LB::evaluate(row, LB::centre(origin, b) - tau, t1, t2);
+                term[(b % kBinTile) * kWave + lane] = t1;
+                term[(kBinTile + b % kBinTile) * kWave + lane] = t2;
+            }
+        };
+        LB::LaneRow row0, row1;
+        // (behind the last bin its own row is fetched once more: a fetch under a condition would make the wait for
+        // the current row a wait for every load in flight)
+        int b0 = next_bin();
+        if (b0 >= 0) {
+            LB::load_row(coef + b0 * LB::kRow, lane, row0);
+            for (;;) {
+                const int b1 = next_bin();
+                LB::load_row(coef + (b1 >= 0 ? b1 : b0) * LB::kRow, lane, row1);
+                evaluate(row0, b0);
+                if (b1 < 0) break;
+                b0 = next_bin();
+                LB::load_row(coef + (b0 >= 0 ? b0 : b1) * LB::kRow, lane, row0);
+                evaluate(row1, b1);
+                if (b0 < 0) break;
+            }
+        }
+        if constexpr (W > 1)
+            while (tile < (nbins + kBinTile - 1) / kBinTile) close_tile();
         S1 = a1 + C1;
         S2 = a2 + C2;
     }

@@ -40,7 +40,9 @@ for k, s in enumerate(starts):
         n_rcp = sum(v for op, v in c.items() if op.startswith("v_rcp_f64"))
         n_f64 = f64(top)
         slots = (n_f64 - n_rcp) + 4 * n_rcp
-        print(f"  block {name}: {n_f64} FP64 VALU ({n_rcp} v_rcp_f64), {len(top)} instructions in all")
+        # (v_fmac_f64_dpp, the multiply-add that reads a bin's coefficient from another lane, is one FP64 slot like any other)
+        n_dpp = sum(v for op, v in c.items() if re.match(r"v_\w+_f64_dpp", op))
+        print(f"  block {name}: {n_f64} FP64 VALU ({n_rcp} v_rcp_f64, {n_dpp} with a DPP source), {len(top)} instructions in all")
         print(f"    per evaluation ({evals} per trip): {(n_f64 - n_rcp) / evals:.3f} + {n_rcp / evals:.4f} rcp"
               f" = {slots / evals:.3f} issue slots")
         print("    " + ", ".join(f"{op} {v}" for op, v in c.most_common(8)))
