@@ -61,8 +61,10 @@ def test_moments_large_ragged(obe):
 @pytest.mark.parametrize("d", [1, 2, 7, 16])
 def test_moments_every_dimension_class(obe, d):
     """The block partials are reduced by a wave reduce-scatter in groups of up to 64 values and
-    folded by one 16-wave workgroup: 2 + 2 D values in pass 1, D (D + 1) / 2 in pass 2 — 4 ... 136,
-    i.e. one partly filled group up to three groups.  Against the oracle, several workgroups."""
+    folded by one 16-wave workgroup: 2 + 2 D values in pass 1, D (D + 1) / 2 in pass 2 — 4 ... 136.
+    Here: one partly filled group (D = 1, 2, 7) and three groups (D = 16), against the oracle, several
+    workgroups; the two-group triangles (D = 11 ... 15) and every other D are in
+    tests/test_gpu_moments_exact.py, bit for bit."""
     g = np.random.default_rng(40 + d)
     n = 300007
     x = g.normal(0.0, 1.0, (d, n)) * g.uniform(0.5, 20.0, (d, 1)) + g.normal(0.0, 5.0, (d, 1))
