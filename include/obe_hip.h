@@ -450,6 +450,27 @@ OBE_API int obe_mask_bounds_moments(const double* d_particles, int64_t ld_p, int
                             const int32_t* h_open, int32_t n_rows, double* d_weights, double* d_moments,
                             double* h_first_moments, int64_t* h_count, void* d_ws, int64_t ws_bytes, void* stream);
 
+/* ---- parameter drift: the prediction step of the filter (ParticlePDF.drift; extension — the reference's parameters
+ * are constants, its cloud moves only in the nudge of particlepdf.py:296-305) ----
+ * n_rows chosen rows of the (D, N) cloud, h_rows ascending, do one step of a Gaussian random walk IN PLACE; the other
+ * rows are never touched, nor are the columns n_particles .. ld_p of any row, nor the weights.  h_factor (n_rows x
+ * n_rows, row-major) is G = sqrt(dt) L with L L^T the drift covariance per unit time, formed by the caller; d_normals
+ * = standard normals (N, n_rows) row-major.  The contract is the chain itself, per drifted row k and particle p, every
+ * operation one correctly rounded double operation:
+ *   s = +0.0;  s = fma(z[p, j], G[k, j], s)  for j = 0 .. n_rows-1    (all n_rows terms, zeros of a triangular G too)
+ *   v = x[h_rows[k], p] + s
+ *   with h_lower / h_upper (n_rows each, the interval of row h_rows[k]; -inf / +inf: no bound there; both NULL: no
+ *   reflection at all):  if v < lo: v = lo + (lo - v)  else if v > hi: v = hi - (v - hi)   — ONE reflection, each
+ *   operation rounded on its own, a NaN left alone; a value still outside afterwards stays where it is (a mask's business)
+ *   x[h_rows[k], p] = v
+ * Nothing is waited for; no host result.  Model-independent.
+ * Refused (-1) before anything is launched: a NULL pointer (h_lower and h_upper go together), n_rows outside
+ * 1..OBE_FAST_DIMS, n_dims outside 1..OBE_CLOUD_MAX_DIMS, a row outside [0, n_dims), a row named twice or rows not
+ * ascending, ld_p < n_particles, a factor entry that is not finite, a NaN bound, lower > upper. */
+OBE_API int obe_drift_particles(double* d_particles, int64_t ld_p, int32_t n_dims, int64_t n_particles,
+                        const int32_t* h_rows, const double* h_factor, int32_t n_rows,
+                        const double* d_normals, const double* h_lower, const double* h_upper, void* stream);
+
 /* ---- good_setting (obe_base.py:781-784): p = nan_to_num(u ** exponent); p /= sum(p) ---- */
 OBE_API int obe_power_normalize(const double* d_u, int64_t n, double exponent, double* d_p_out,
                         void* d_ws, int64_t ws_bytes, void* stream);

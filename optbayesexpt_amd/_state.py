@@ -25,7 +25,7 @@ import importlib
 import numpy as np
 import torch
 
-from . import _lib
+from . import _drift, _lib
 from ._mirror import Mirror
 
 #: version of the snapshot layout; a snapshot of any other version is refused
@@ -164,6 +164,8 @@ def snapshot(obj, on_device=False):
         mom["host_values"] = np.array(obj._moments_host[:])      # (a checked read under OBE_CHECK_DELIVERY)
     st["moments"] = mom
     st["sumsq"] = float(obj._sumsq) if obj._sumsq_key == wm.version and obj._sumsq is not None else None
+    if obj.__dict__.get("_drift") is not None:       # (only when set: objects that never were write the snapshots they did)
+        st["parameter_drift"] = _drift.copy(obj._drift)
 
     if isinstance(obj, OptBayesExpt):
         getter = getattr(obj.get_setting, "__name__", "opt_setting")
@@ -276,6 +278,10 @@ def restore(state, device=None, settings_shard=None, into=None):
         obj._mom_host_key = cloud + (mom["host"],)
     if state["sumsq"] is not None:
         obj._sumsq, obj._sumsq_key = state["sumsq"], wm.version
+    drift = state.get("parameter_drift")                 # (absent: never set, or a state written before)
+    if drift is not None:
+        obj._drift = dict(rows=np.array(drift["rows"], dtype=np.int32), cholesky=np.array(drift["cholesky"], dtype=np.float64),
+                          per_update=bool(drift["per_update"]), at_bounds=drift["at_bounds"])
 
     if isinstance(obj, OptBayesExpt):
         par = state["parameters"]

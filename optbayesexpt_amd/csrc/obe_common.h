@@ -29,8 +29,8 @@ int bad_arg(const char* what);
 
 // Host-side dispatch on the width of the cloud: f(std::integral_constant<int, D>{}) for D == n_dims in
 // [LO, kFastDims], the widths the cloud kernels are instantiated for; any other width is refused with `refusal`.
-static_assert(OBE_FAST_DIMS == 16, "edit with OBE_FAST_DIMS the four refusals that say \"1..16\": obe_bayes_update_model_moments, "
-                                   "obe_mask_renorm_moments, obe_resample_begin, obe_resample_particles");
+static_assert(OBE_FAST_DIMS == 16, "edit with OBE_FAST_DIMS the five refusals that say \"1..16\": obe_bayes_update_model_moments, "
+                                   "obe_mask_renorm_moments, obe_resample_begin, obe_resample_particles, obe_drift_particles");
 template <int LO, class F, int... I>
 int dispatch_dims_from(int n_dims, const char* refusal, F&& f, std::integer_sequence<int, I...>) {
     int rc = 0;
@@ -215,6 +215,9 @@ inline int stream_blocks(int64_t n, int per_block) {
     if (b > kMaxBlocks) b = kMaxBlocks;
     return static_cast<int>(b);
 }
+// obe_drift_particles: one particle per thread, at most kMaxBlocks workgroups of kBlock — a cloud of more than
+// kMaxBlocks * kBlock = 524 288 particles takes further trips of the kernel's grid-stride loop
+inline int drift_blocks(int64_t n_particles) { return stream_blocks(n_particles, kBlock); }
 
 // ---- what the calls of obe_resample.hip need of the caller's workspace (they check against these; so does
 // obe_workspace_bytes, next to moments_ws_bytes of obe_moments.h, update_ws_bytes of obe_update.h and the sweep's own)

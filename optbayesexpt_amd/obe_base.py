@@ -33,7 +33,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _batch, _bounds, _design, _devrng, _interest, _lib, _predictive, _reading, _scoring
+from . import _batch, _bounds, _design, _devrng, _drift, _interest, _lib, _predictive, _reading, _scoring
 from ._sweepstate import Attempt, Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
@@ -731,6 +731,7 @@ class OptBayesExpt(ParticlePDF):
         self._parameters = self._particles
         if self.just_resampled:
             self.enforce_parameter_constraints()
+        self._drift_after_update()
         # (the cycle pattern the speculative sweep looks for: a full sweep of exactly this cloud comes next)
         self._sweeps.update_finished((self._particles.version, self._weights.version) if fused else None,
                                      self.just_resampled)
@@ -765,6 +766,8 @@ class OptBayesExpt(ParticlePDF):
         mode = self.tuning_parameters.get("speculative_sweep", _SPECULATIVE_DEFAULT)
         if not self._sweeps.speculation_wanted(mode, after_resample):      # (the policy: _sweepstate.py)
             return False
+        if self._drifts_per_update():
+            return False          # (pdf_update() ends with a drift: nobody could take a sweep of the cloud before it)
         if after_resample and self._parameters is not self._particles:
             return False
         return (self.utility_method == "variance_full" and self._utility_fusable()
@@ -972,6 +975,39 @@ class OptBayesExpt(ParticlePDF):
             self._constraint_pending = False
             if changed[0]:
                 self._weights.mark_device_written()
+
+    # ------------------------------------------------------- parameter drift (ParticlePDF.set_parameter_drift)
+    def _drifts_per_update(self):
+        drift = self.__dict__.get("_drift")
+        return drift is not None and drift["per_update"]
+
+    def _drift_after_update(self):
+        """The last step of a pdf_update() whose drift was set with ``per_update=True``: ``drift(1.0)``, behind the
+        update, the resample and the constraints (a sweeper steps once per sweep, not once per point)."""
+        if self._drifts_per_update() and not self.__dict__.get("_drift_held"):
+            self.drift(1.0)
+
+    def _drift_bounds(self, drift):
+        """``at_bounds='reflect'``: the effective bounds of the drifted rows — the user's, intersected with what the
+        class adds itself (the noise-parameter class's sigma > 0) —, or None where none of them is bounded."""
+        if drift["at_bounds"] != "reflect":
+            return None
+        normal = self.__dict__.get("_parameter_bounds")
+        if normal is None:
+            d = self.n_dims
+            normal = (np.full(d, -np.inf), np.full(d, np.inf), np.zeros(d, dtype=bool), np.zeros(d, dtype=bool))
+        return _drift.reflection_bounds(drift, self._effective_bounds(normal))
+
+    def drift(self, dt=1.0):
+        """``ParticlePDF.drift()`` on this object's particles (a stale ``parameters`` alias stays the alias): a sweep
+        enqueued ahead is dropped first, and ``enforce_parameter_constraints()`` follows the step as it follows a
+        resample in ``pdf_update()`` — declared bounds, the noise-parameter class's sigma > 0 or a user's hook act
+        on the moved cloud."""
+        self._drop_speculative_sweep()
+        before = self._particles.version
+        ParticlePDF.drift(self, dt)
+        if self._particles.version != before:
+            self.enforce_parameter_constraints()
 
     def _resample_mask_rows(self):
         """The gather of a resample may apply this class's constraint itself when that constraint is certain to

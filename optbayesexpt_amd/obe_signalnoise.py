@@ -128,6 +128,7 @@ class OptBayesExptSignalNoise(OptBayesExpt):
         self._parameters = self._particles
         if self.just_resampled:
             self.enforce_parameter_constraints()
+        self._drift_after_update()
         self._sweeps.update_finished(None, self.just_resampled)
         return _LazyState(self)
 

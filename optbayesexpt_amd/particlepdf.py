@@ -13,7 +13,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _devrng, _lib, _posterior
+from . import _devrng, _drift, _lib, _posterior
 from ._mirror import Mirror
 
 _P = ctypes.c_void_p
@@ -67,7 +67,8 @@ class ParticlePDF:
         self._set_cloud(prior, None)
         #: bool: True if the last bayesian_update() resampled
         self.just_resampled = False
-        #: numpy Generator feeding randdraw() and resample(); reseed by assignment
+        self._drift = None            # set_parameter_drift(): rows, factor, per_update, at_bounds; None: no drift
+        #: numpy Generator feeding randdraw(), resample() and drift(); reseed by assignment
         self.rng = np.random.default_rng()
         self._host_out = _lib.pinned_array(16)       # page-locked: the folding kernels write their scalars here
 
@@ -687,6 +688,60 @@ class ParticlePDF:
             self._resample_apply(idx, z_dev, factor, mean, aos=b["aos"])
         else:
             _devrng.advance(self._rng, st, n + consumed)
+
+    # ------------------------------------------------------- parameter drift
+    # (extension: the reference's parameters are constants — its cloud moves only in the nudge of resample(), which
+    # with scale=True does not widen the posterior —, so a quantity that walks during a run leaves the cloud behind.
+    # The prediction step of a particle filter: chosen rows do a Gaussian random walk, on the device, from the
+    # object's own generator exactly as resample() takes its normals.  _drift.py: argument forms and refusals.)
+    def set_parameter_drift(self, rates, rows=None, per_update=False, at_bounds="mask"):
+        """The random walk that ``drift(dt)`` applies: ``theta_rows += sqrt(dt) L z``, ``z ~ N(0, I)``, ``L L^T`` the
+        drift covariance per unit time.  ``rates``: a scalar or a (K,) vector of standard deviations per sqrt(time)
+        for ``rows`` (default: all rows), a mapping ``{row: std}``, or a (K, K) covariance of ``rows``; None clears.
+        A row of standard deviation 0 does not drift; at most OBE_FAST_DIMS rows may.  ``per_update=True``:
+        ``OptBayesExpt.pdf_update()`` ends with ``drift(1.0)``.  ``at_bounds``: ``'mask'`` — a particle that drifts
+        out of the object's parameter bounds is left to ``enforce_parameter_constraints()`` —, ``'reflect'`` — it is
+        first reflected at the bound it crossed, once.  Travels with save / load / deepcopy."""
+        self._drift = _drift.settings(rates, rows, self.n_dims, per_update, at_bounds)
+
+    @property
+    def parameter_drift(self):
+        """None, or a dict copy of the drift that is set: ``rows`` (ascending), ``cholesky`` (the (K, K) lower factor
+        of the covariance per unit time), ``per_update``, ``at_bounds``."""
+        return _drift.copy(self.__dict__.get("_drift"))
+
+    def _drift_bounds(self, drift):
+        """Hook: ``(lower, upper)`` of the drifted rows if this step reflects at bounds, else None (OptBayesExpt)."""
+        return None
+
+    def drift(self, dt=1.0):
+        """One prediction step of ``dt`` time units of the drift that ``set_parameter_drift()`` set: every particle
+        moves, whatever its weight, and consumes its K normals of ``self.rng`` — ``rng.standard_normal((N, K))``,
+        row-major, on the device where ``resample()`` would draw there too; the weights stay.  ``dt == 0`` draws
+        nothing and changes nothing.  ``RuntimeError`` if no drift is set."""
+        drift = self.__dict__.get("_drift")
+        if drift is None:
+            raise RuntimeError("drift(): no parameter drift is set (set_parameter_drift)")
+        dt = _drift.check_dt(dt)
+        rows = drift["rows"]
+        n, k = self.n_particles, int(rows.size)
+        if dt == 0.0 or k == 0:
+            return
+        if rows[-1] >= self.n_dims:
+            raise ValueError(f"drift(): row {int(rows[-1])} of the drift is outside the cloud's {self.n_dims} rows")
+        factor = _drift.factor(drift["cholesky"], dt)
+        bounds = self._drift_bounds(drift)
+        rstream = self._device_stream(0, n * k)           # exact continuation of self.rng, or None
+        if rstream is not None:
+            z_dev = rstream.normals()                     # (n*k,) row-major (n, k); advances self.rng
+        else:
+            z_dev = torch.from_numpy(np.ascontiguousarray(self.rng.standard_normal((n, k)))).to(self._device)
+        p = self._particles.tensor()
+        self._lib.call("obe_drift_particles", _ptr(p), p.shape[1], self.n_dims, n, _lib.host_ptr(rows),
+                       _lib.host_ptr(factor), k, _ptr(z_dev), None if bounds is None else _lib.host_ptr(bounds[0]),
+                       None if bounds is None else _lib.host_ptr(bounds[1]), self._stream())
+        # a new version of the cloud: cached moments, the bins' kept grouping and tracked host views go stale
+        self._particles.mark_device_written()
 
     # ------------------------------------------------------- copy, pickle, save
     def __getstate__(self):

@@ -58,7 +58,19 @@ class OptBayesExptSweeper(OptBayesExptNoiseParameter):
         in batches (``obe_bayes_update_sweep``): the resample test between the points runs on
         the device, and the host synchronises once per batch instead of once per point.  A point
         that calls for a resample ends its batch; the resample (and the constraint hook) run
-        on the host path exactly as in the one-by-one loop, then the rest of the sweep follows."""
+        on the host path exactly as in the one-by-one loop, then the rest of the sweep follows.
+
+        A parameter drift with ``per_update=True`` steps once per sweep, behind its last point."""
+        self._drift_held = True                 # (the per-point updates below do not drift)
+        try:
+            out = self._pdf_update_points(measurement_record)
+        finally:
+            self._drift_held = False
+        if out is not None:
+            self._drift_after_update()
+        return out
+
+    def _pdf_update_points(self, measurement_record):
         (setting_values,), result_values = measurement_record
         points = list(zip(setting_values, result_values))
         self.last_sweep_batches = []            # (points submitted, points applied) per device batch; empty: point by point
