@@ -416,7 +416,7 @@ static int64_t cell_ws_doubles(int64_t nd) {
 }
 
 // ---- the bin form of the same sweep (OBE_SWEEP_BINS): its plan, its sizes and where its pieces live ----
-struct BinPlan {           // written by bin_plan_kernel
+struct BinPlan {           // written by bin_group_kernel<false> (bin_plan_of)
     double origin;         // the smallest packed tau0: the left edge of bin 0
     int nbins;             // 0 when poisoned
     unsigned poison;       // a non-finite tau0, more than kMaxBins bins, or d not finite and positive
@@ -710,24 +710,26 @@ __global__ __launch_bounds__(kBlock) void cell_eval_kernel(SweepArgs a, const Ce
     a.cs_out[s] = 0.0;
 }
 // ---- the bin form of the same sweep (OBE_SWEEP_BINS; obe_models.h: LorentzBins) ----
-// The particles are summarised instead of the settings.  Behind sweep_pack_kernel:
-//   bin_minmax_kernel    min / max of the packed tau0 (zero-weight draws included), one partial per workgroup.
-//   bin_plan_kernel      -> origin, bin count, poison word.
-//   bin_group_kernel<0>  a wavefront owns a contiguous unit of draws and counts them by bin (integers, no atomics).
+// The particles are summarised instead of the settings.  No sweep_pack_kernel: the grouping reads the cloud itself
+// (tau0 = x0 / d, the division of Lorentz<1>::pack), and a draw's record is formed once, where it is stored:
+//   bin_minmax_kernel    min / max of tau0 (zero-weight draws included), one partial per workgroup.
+//   bin_group_kernel<0>  every workgroup folds those partials into the plan (origin, bin count, poison word: workgroup 0
+//                        stores it); a wavefront owns a contiguous unit of draws, counts them by bin (integers, no
+//                        atomics) and leaves every draw's bin and its rank among the unit's draws of that bin (bin_code).
 //   bin_scan_kernel      exclusive scan of the counts over the units, bin by bin, and each bin's total.
-//   bin_group_kernel<1>  the same walk again: a draw goes to (start of its bin) + (draws of that bin in earlier
-//                        units) + (earlier draws of that bin in this unit) — the order of a stable sort by bin.
+//   bin_group_kernel<1>  a draw's record goes to (start of its bin) + (draws of that bin in earlier units) + (its
+//                        rank) — the order of a stable sort by bin.
 //   bin_moments_kernel   lane <-> draw within one item (kBinChunk consecutive draws of ONE bin), 3 P + 2 running sums
 //                        per lane, reduced over the lanes once per item (halving_reduce: a butterfly's tree).
 //   bin_fold_kernel      a bin's items summed in a fixed order (fold_in_order).
 //   bin_eval_kernel      lane <-> setting, a bin's row across the lanes, bins in order, one or several wavefronts per
-//                        64 settings (plan_bin_eval_waves); writes part1 / part2 as ONE chunk and cs_out = 0, as
-//                        cell_eval_kernel does.
+//                        64 settings (plan_bin_eval_waves); the moments are ONE chunk, and the wavefront that holds
+//                        them finishes its 64 settings as sweep_finalize would (no finalize launch: argmax_fold next).
 // No floating-point atomics; every sum has a fixed association, so two calls on the same inputs give the same bits.
 // With a keep buffer (obe_sweep_utility_keep) the plan, binstart and itemstart live there and bin_group_kernel<1> also
-// leaves every draw's sorted position; a later call with OBE_SWEEP_BINS_KEPT runs, in place of the pack and the five
-// grouping launches,
-//   bin_scatter_pack_kernel   sweep_pack_kernel's record of draw p, written to sorted[dest[p]]
+// leaves every draw's sorted position; a later call with OBE_SWEEP_BINS_KEPT runs, in place of the four grouping
+// launches,
+//   bin_scatter_pack_kernel   the record of draw p (bin_record), written to sorted[dest[p]]
 // and then bin_moments_kernel onwards: the same records in the same places, hence the same bits.
 struct BinSweepPtrs {
     BinPlan* plan;
@@ -736,6 +738,7 @@ struct BinSweepPtrs {
     int* itemstart;        // [kMaxBins + 1] first item of each bin
     BinKeep* keep;         // the caller's keep buffer (plan, binstart and itemstart point into it), or NULL
     int* dest;             // [nd] the sorted position of every draw, in the keep buffer (NULL without one)
+    int* code;             // [nd] a rebuild's bin and rank of every draw (bin_code): dest, or the head of the packed draws
     int reuse;             // OBE_SWEEP_BINS_KEPT: the grouping is read from the keep buffer, not made
     int keep_nd;           // what a reused buffer must have been made for: this many draws ...
     unsigned long long keep_dbits;     // ... and this d
@@ -757,15 +760,44 @@ __device__ __forceinline__ bool bin_keep_refused(const BinSweepPtrs& q) {
     return !(k->mark == kBinKeepMark && k->nd == q.keep_nd && k->dbits == q.keep_dbits);
 }
 
-__global__ __launch_bounds__(kBlock) void bin_minmax_kernel(SweepArgs a, double* __restrict__ minmax) {
+// tau0 of draw p as the sorted record holds it: Lorentz<1>::pack's division, on the draw's own particle
+__device__ __forceinline__ double bin_tau0(const SweepArgs& a, int64_t p) {
+    double w;
+    const int64_t src = draw_source(a, p, w);
+    return a.particles[src] / a.m.consts[0];
+}
+
+// the sorted record of draw p: what sweep_pack_kernel<Lorentz<1>> makes of it
+__device__ __forceinline__ void bin_record(const SweepArgs& a, int64_t p, double2& ra, double2& rb) {
+    using M = Lorentz<1>;
+    static_assert(packed_width<M>() == 4 && M::NPK == 3, "the sorted records are 32 bytes");
+    double w, pk[4];
+    const int64_t src = draw_source(a, p, w);
+    const double sw = sqrt(w);
+    M::pack(ParamRef{a.particles + src, a.ld_p}, a.moments + 2, a.m, sw, pk);
+    ra = double2{pk[0], pk[1]};
+    rb = double2{pk[2], sw};
+}
+
+// a draw between the two grouping passes of a rebuild: its bin, and its rank among its unit's draws of that bin
+constexpr int kBinRankBits = 24;
+static_assert((((int64_t)1 << 30) + kBinMaxUnits - 1) / kBinMaxUnits <= ((int64_t)1 << kBinRankBits)
+                  && LorentzBins::kMaxBins <= (1 << (31 - kBinRankBits)),
+              "a unit of a cloud of 2^30 draws (bin_form_selected) has at most 2^19 draws: rank and bin share an int");
+__device__ __forceinline__ int bin_code(int bin, int rank) { return (bin << kBinRankBits) | rank; }
+
+// (the first launch of a rebuild: with a keep buffer, no grouping stands behind its head until the scatter pass says so)
+__global__ __launch_bounds__(kBlock) void bin_minmax_kernel(SweepArgs a, BinSweepPtrs q) {
     constexpr int NW = kBlock / kWave;
     __shared__ double slo[NW], shi[NW];
     __shared__ int sbad[NW];
     if (sweep_aborted(a.abort)) return;
+    if (q.keep && blockIdx.x == 0 && threadIdx.x == 0) q.keep->mark = 0u;
+    double* __restrict__ minmax = q.minmax;
     double lo = INFINITY, hi = -INFINITY;
     int bad = 0;
     for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < a.nd; p += (int64_t)gridDim.x * kBlock) {
-        const double t = a.packed[4 * p];
+        const double t = bin_tau0(a, p);
         bad |= !(fabs(t) <= kDblMax);
         lo = fmin(lo, t);
         hi = fmax(hi, t);
@@ -793,42 +825,31 @@ __global__ __launch_bounds__(kBlock) void bin_minmax_kernel(SweepArgs a, double*
     minmax[2 * kBinMinmaxBlocks + blockIdx.x] = bad ? 1.0 : 0.0;
 }
 
-__global__ __launch_bounds__(kBinMinmaxBlocks) void bin_plan_kernel(SweepArgs a, const double* __restrict__ minmax,
-                                                                     int nblocks, BinPlan* __restrict__ plan,
-                                                                     BinKeep* keep) {
-    constexpr int NW = kBinMinmaxBlocks / kWave;
-    __shared__ double slo[NW], shi[NW];
-    __shared__ int sbad[NW];
-    if (sweep_aborted(a.abort)) return;
-    const bool have = (int)threadIdx.x < nblocks;
-    double lo = have ? minmax[threadIdx.x] : INFINITY, hi = have ? minmax[kBinMinmaxBlocks + threadIdx.x] : -INFINITY;
-    int bad = have ? minmax[2 * kBinMinmaxBlocks + threadIdx.x] != 0.0 : 0;
+// The plan from bin_minmax_kernel's partials, by every wavefront for itself and in every lane: at most kBinMinmaxBlocks
+// of each kind, 6 KB from L2; min, max and OR are exact in any order.
+__device__ __forceinline__ BinPlan bin_plan_of(const SweepArgs& a, const double* __restrict__ minmax, int nblocks) {
+    const int lane = threadIdx.x & (kWave - 1);
+    double lo = INFINITY, hi = -INFINITY;
+    int bad = 0;
+#pragma unroll
+    for (int g = 0; g < kBinMinmaxBlocks / kWave; ++g) {
+        const int b = g * kWave + lane;
+        const bool have = b < nblocks;
+        lo = fmin(lo, have ? minmax[b] : INFINITY);
+        hi = fmax(hi, have ? minmax[kBinMinmaxBlocks + b] : -INFINITY);
+        bad |= have ? minmax[2 * kBinMinmaxBlocks + b] != 0.0 : 0;
+    }
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) {
-        lo = fmin(lo, __shfl_down(lo, o, kWave));
-        hi = fmax(hi, __shfl_down(hi, o, kWave));
-        bad |= __shfl_down(bad, o, kWave);
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        slo[threadIdx.x / kWave] = lo;
-        shi[threadIdx.x / kWave] = hi;
-        sbad[threadIdx.x / kWave] = bad;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int g = 1; g < NW; ++g) {
-        lo = fmin(lo, slo[g]);
-        hi = fmax(hi, shi[g]);
-        bad |= sbad[g];
+        lo = fmin(lo, __shfl_xor(lo, o, kWave));
+        hi = fmax(hi, __shfl_xor(hi, o, kWave));
+        bad |= __shfl_xor(bad, o, kWave);
     }
     const double d = a.m.consts[0];
     const double n = floor((hi - lo) * (1.0 / LorentzBins::kWidth)) + 1.0;
     const bool ok = !bad && d > 0.0 && d <= kDblMax && fabs(lo) <= kDblMax && fabs(hi) <= kDblMax
                     && n <= (double)LorentzBins::kMaxBins;                // (a NaN fails every comparison)
-    if (keep) keep->mark = 0u;        // (the plan lives in the keep buffer: no grouping until the scatter pass says so)
-    plan->origin = lo;
-    plan->nbins = ok ? static_cast<int>(n) : 0;
-    plan->poison = ok ? 0u : 1u;
+    return BinPlan{lo, ok ? static_cast<int>(n) : 0, ok ? 0u : 1u};
 }
 
 // exclusive prefix over the lanes of a wavefront, and the wavefront's total
@@ -844,17 +865,23 @@ __device__ __forceinline__ int wave_exclusive(int v, int& total) {
     return inc - v;
 }
 
-// A wavefront walks its unit of draws in order, 64 at a time.  Lane l keeps the running figure of bins l and l + 64
-// (c0, c1); per trip the distinct bins of the 64 draws are taken one by one (ballot), and a draw's rank is its bin's
-// running figure plus the number of lower lanes with the same bin.  SCATTER = false: the figures start at 0 and end
-// as the unit's counts.  SCATTER = true: they start at the first sorted position of (bin, unit) and every packed
-// record is written there.
+// The two grouping passes of a rebuild; a wavefront owns a unit of `per` consecutive draws in both.
+// SCATTER = false, the counting pass: the plan first (bin_plan_of).  Then the wavefront walks its unit in order, 64 draws
+// at a time.  Lane l keeps the count of bins l and l + 64 (c0, c1); per trip the distinct bins of the 64 draws are taken
+// one by one (ballot), and a draw's rank is its bin's count so far plus the number of lower lanes with the same bin.
+// The counts end as the unit's, and every draw leaves its bin_code.
+// SCATTER = true: lane l holds the first sorted position of (bin l, unit) and of (bin l + 64, unit); every draw's
+// record (bin_record) is formed from the cloud and written at its bin's first position plus its rank.
 template <bool SCATTER>
-__global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t per, int nunits, BinSweepPtrs q) {
+__global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t per, int nunits, int mm_blocks,
+                                                           BinSweepPtrs q) {
     using LB = LorentzBins;
     if (sweep_aborted(a.abort)) return;
-    const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    const int lane = threadIdx.x & (kWave - 1);
+    const int unit = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
+    BinPlan plan;
     if constexpr (SCATTER) {
+        plan = *q.plan;
         // the last grouping launch: when it has ended, the keep buffer describes these draws (a poisoned plan included)
         if (q.keep && blockIdx.x == 0 && threadIdx.x == 0) {
             q.keep->nd = static_cast<int>(a.nd);
@@ -862,11 +889,12 @@ __global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t 
             q.keep->mismatch = 0u;
             q.keep->mark = kBinKeepMark;
         }
+    } else {
+        plan = bin_plan_of(a, q.minmax, mm_blocks);
+        if (blockIdx.x == 0 && threadIdx.x == 0) *q.plan = plan;
     }
+    const int nbins = __builtin_amdgcn_readfirstlane(plan.nbins);
     if (nbins == 0) return;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int unit = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
-    const double origin = q.plan->origin;
     int c0 = 0, c1 = 0;
     if constexpr (SCATTER) {
         // the bins' first positions (and first items): exclusive prefixes of the totals, by every wavefront for itself
@@ -892,37 +920,40 @@ __global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t 
     if (unit >= nunits) return;
     const int64_t begin = (int64_t)unit * per;
     const int64_t end = begin + per < a.nd ? begin + per : a.nd;
-    const double2* __restrict__ rec = reinterpret_cast<const double2*>(a.packed);
     for (int64_t i0 = begin; i0 < end; i0 += kWave) {
         const int64_t i = i0 + lane;
         const bool live = i < end;
-        double2 ra{0.0, 0.0}, rb{0.0, 0.0};
-        if (live) {
-            ra = rec[2 * i];
-            if constexpr (SCATTER) rb = rec[2 * i + 1];
-        }
-        const int bin = live ? LB::bin_of(origin, ra.x, nbins) : -1;
-        int pos = 0;
-        unsigned long long todo = __ballot(live);
-        while (todo) {
-            const int b = __builtin_amdgcn_readlane(bin, __builtin_ctzll(todo));      // (wave-uniform)
-            const unsigned long long same = __ballot(bin == b);
-            const int figure = __builtin_amdgcn_readlane(b < kWave ? c0 : c1, b & (kWave - 1));
-            if (bin == b) pos = figure + __popcll(same & ((1ull << lane) - 1ull));
-            const int n = __popcll(same);
-            if (lane == (b & (kWave - 1))) {
-                if (b < kWave) c0 += n;
-                else c1 += n;
-            }
-            todo &= ~same;
-        }
         if constexpr (SCATTER) {
+            const int code = live ? q.code[i] : 0;
+            const int bin = code >> kBinRankBits;
+            // (every lane takes part in the exchange: a lane without a draw asks for bin 0)
+            const int first0 = __shfl(c0, bin & (kWave - 1), kWave), first1 = __shfl(c1, bin & (kWave - 1), kWave);
+            const int pos = (bin < kWave ? first0 : first1) + (code & ((1 << kBinRankBits) - 1));
             if (live && pos >= 0 && pos < a.nd) {
+                double2 ra, rb;
+                bin_record(a, i, ra, rb);
                 double2* __restrict__ out = reinterpret_cast<double2*>(q.sorted) + 2 * (int64_t)pos;
                 out[0] = ra;
                 out[1] = rb;
             }
-            if (q.dest && live) q.dest[i] = pos;
+            if (q.dest && live) q.dest[i] = pos;       // (over the code this lane has just read)
+        } else {
+            const int bin = live ? LB::bin_of(plan.origin, bin_tau0(a, i), nbins) : -1;
+            int rank = 0;
+            unsigned long long todo = __ballot(live);
+            while (todo) {
+                const int b = __builtin_amdgcn_readlane(bin, __builtin_ctzll(todo));      // (wave-uniform)
+                const unsigned long long same = __ballot(bin == b);
+                const int figure = __builtin_amdgcn_readlane(b < kWave ? c0 : c1, b & (kWave - 1));
+                if (bin == b) rank = figure + __popcll(same & ((1ull << lane) - 1ull));
+                const int n = __popcll(same);
+                if (lane == (b & (kWave - 1))) {
+                    if (b < kWave) c0 += n;
+                    else c1 += n;
+                }
+                todo &= ~same;
+            }
+            if (live) q.code[i] = bin_code(bin, rank);
         }
     }
     if constexpr (!SCATTER) {
@@ -931,40 +962,33 @@ __global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t 
     }
 }
 
-// OBE_SWEEP_BINS_KEPT, in place of sweep_pack_kernel and the five launches above: sweep_pack_kernel<Lorentz<1>>'s record of
-// draw p (full mode), written where bin_group_kernel<true> put it when the keep buffer was made.  Nothing is written
-// unless the head fits the call (bin_keep_refused: that is what keeps dest[p] inside `sorted`), and a draw goes
-// nowhere unless it still belongs to the bin whose run holds its kept position: a tau0 that is not finite, lies outside
-// the plan or in another bin stores the call's number into the head, and bin_eval_kernel answers NaN for the whole
-// call, as for a poisoned plan.  (A draw that moved WITHIN its bin gives what a rebuild would: the order of a stable
-// sort by bin does not change.)
+// OBE_SWEEP_BINS_KEPT, in place of the four launches above: the record of draw p (full mode), written where
+// bin_group_kernel<true> put it when the keep buffer was made.  Nothing is written unless the head fits the call
+// (bin_keep_refused: that is what keeps dest[p] inside `sorted`), and a draw goes nowhere unless it still belongs to
+// the bin whose run holds its kept position: a tau0 that is not finite, lies outside the plan or in another bin stores
+// the call's number into the head, and bin_eval_kernel answers NaN for the whole call, as for a poisoned plan.  (A
+// draw that moved WITHIN its bin gives what a rebuild would: the order of a stable sort by bin does not change.)
 __global__ __launch_bounds__(kBlock) void bin_scatter_pack_kernel(SweepArgs a, BinSweepPtrs q) {
-    using M = Lorentz<1>;
     using LB = LorentzBins;
-    static_assert(packed_width<M>() == 4, "the sorted records are 32 bytes");
     if (sweep_aborted(a.abort)) return;
     if (bin_keep_refused(q)) return;
     const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
     if (nbins <= 0 || nbins > LB::kMaxBins) return;
     const double origin = q.plan->origin;
-    const double* __restrict__ thbar = a.moments + 2;
     for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < a.nd; p += (int64_t)gridDim.x * kBlock) {
-        double pk[4];
-        const double w = a.weights[p];
-        const double sw = sqrt(w);
-        M::pack(ParamRef{a.particles + p, a.ld_p}, thbar, a.m, sw, pk);
-        pk[M::NPK] = sw;
+        double2 ra, rb;
+        bin_record(a, p, ra, rb);
         const int pos = q.dest[p];
-        const double t = (pk[0] - origin) * (1.0 / LB::kWidth);      // (bin_of's expression; a NaN fails the test)
+        const double t = (ra.x - origin) * (1.0 / LB::kWidth);       // (bin_of's expression; a NaN fails the test)
         bool ok = t >= 0.0 && t < (double)nbins && pos >= 0 && pos < a.nd;
         if (ok) {
-            const int b = LB::bin_of(origin, pk[0], nbins);
+            const int b = LB::bin_of(origin, ra.x, nbins);
             ok = q.binstart[b] <= pos && pos < q.binstart[b + 1];
         }
         if (ok) {
             double2* __restrict__ out = reinterpret_cast<double2*>(q.sorted) + 2 * (int64_t)pos;
-            out[0] = double2{pk[0], pk[1]};
-            out[1] = double2{pk[2], pk[3]};
+            out[0] = ra;
+            out[1] = rb;
         } else {
             q.keep->mismatch = q.call;
         }
@@ -1127,151 +1151,6 @@ __global__ __launch_bounds__(kBinFoldGroups * kWave) void bin_fold_kernel(BinSwe
     if (threadIdx.x < kWave && live) q.coef[(int64_t)bin * LB::kRow + co] = t;
 }
 
-// `ran` receives `seq`, as in cell_eval_kernel.  A bin's row is the same for the 64 settings of a wavefront, so it is
-// held in registers across the lanes and named lane by lane where it is used (obe_models.h: LorentzBins::LaneRow): a
-// wavefront fetches the rows of its own bins from q.coef (at most OBE_BIN_MAX rows of 688 bytes, the same lines for
-// every wavefront of the chip), the row of its next occupied bin before it evaluates the current one, and the series
-// sums wait for no memory.  (The rows used to come through an LDS tile: one exposed LDS round trip per series step,
-// DESIGN.md.)  Two register sets take turns, so that no row register is ever copied.  The occupied bins are two
-// ballots over binstart (lane <-> bin), walked lowest first.
-// A workgroup holds G groups of 64 settings (lane <-> setting) and W wavefronts for each of them.
-// <4, 1>: a workgroup of kBlock threads, every wavefront walks every occupied bin of its own group; no LDS, no barrier.
-// W > 1: of every tile of kBinTile bins wavefront w of a group evaluates the occupied bins t = w, w + W, ... and leaves
-// their t1, t2 in LDS, and behind a barrier wavefront 0 of the group adds them in bin order, as the one wavefront of
-// W = 1 does: the same numbers in the same order, the same bits, and the one dependent chain per bin is walked by W
-// wavefronts at once (plan_bin_eval_waves; DESIGN.md, "Several wavefronts per group of settings").  Every wavefront of
-// a workgroup passes two barriers per tile of the plan, whichever bins it owns: nbins and the abort word (read once
-// per workgroup where W > 1) are the same for all.  All 64 lanes stay active to the end (LaneRow).
-constexpr int kBinTile = 16;
-template <int G, int W>
-__global__ __launch_bounds__(G * W * kWave, W == 1 ? 1 : 3)           // (W > 1: registers for three wavefronts per SIMD)
-void bin_eval_kernel(SweepArgs a, BinSweepPtrs q, unsigned seq) {
-    using LB = LorentzBins;
-    constexpr int kThreads = G * W * kWave;
-    static_assert(W > 1 || kThreads == kBlock, "W = 1 is the workgroup of four groups");
-    static_assert((G * W) % 4 == 0, "whole wavefronts for every SIMD of the CU (plan_bin_eval_waves)");
-    static_assert(LB::kMaxBins <= 2 * kWave && kWave % kBinTile == 0, "two ballots name the occupied bins");
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
-    const int grp = wave % G, wid = wave / G;             // wavefront `wid` of group `grp`
-    double* term = nullptr;                               // W > 1, the group's: t1 at [t][lane], t2 at [kBinTile + t][lane]
-    if constexpr (W == 1) {
-        if (sweep_aborted(a.abort)) return;
-    } else {
-        __shared__ double terms[G * 2 * kBinTile * kWave];
-        __shared__ int stop;
-        term = terms + grp * (2 * kBinTile * kWave);
-        if (threadIdx.x == 0) stop = sweep_aborted(a.abort);
-        __syncthreads();
-        if (stop) return;
-    }
-    const int64_t s = ((int64_t)blockIdx.x * G + grp) * kWave + lane;
-    // (a reuse whose keep buffer does not fit the call, or one of whose draws has left its kept bin: as if poisoned)
-    const bool refused = bin_keep_refused(q) || (q.reuse && q.keep->mismatch == q.call);
-    const int nbins = refused ? 0 : __builtin_amdgcn_readfirstlane(q.plan->nbins);
-    double S1 = __builtin_nan(""), S2 = __builtin_nan("");        // poisoned: kappa = NaN, the caller repeats without the bit
-    if (nbins > 0) {
-        double tau;
-        Lorentz<1>::prep_setting(a.settings + (s < a.ns ? s : a.ns - 1), a.m, &tau);
-        const double origin = q.plan->origin;
-        const double* __restrict__ coef = q.coef;
-        // (the row of an empty bin was never written: it is never fetched)
-        const int* __restrict__ start = q.binstart;
-        const bool here0 = lane < nbins && start[lane + 1] != start[lane];
-        const bool here1 = kWave + lane < nbins && start[kWave + lane + 1] != start[kWave + lane];
-        const uint64_t occ0 = __ballot(here0), occ1 = __ballot(here1);            // bins 0-63, 64-127
-        uint64_t own0 = occ0, own1 = occ1;                                        // ... that this wavefront evaluates
-        double c1col[2] = {0.0, 0.0}, c2col[2] = {0.0, 0.0};                      // W > 1, wavefront 0: lane <-> bin
-        if constexpr (W > 1) {
-            uint64_t mine = 0;
-            for (int t = wid; t < kBinTile; t += W) mine |= (uint64_t)1 << t;
-            mine |= mine << 16;
-            mine |= mine << 32;
-            own0 &= mine;
-            own1 &= mine;
-            if (wid == 0) {
-                if (here0) {
-                    c1col[0] = coef[lane * LB::kRow + 3 * LB::kOrder];
-                    c2col[0] = coef[lane * LB::kRow + 3 * LB::kOrder + 1];
-                }
-                if (here1) {
-                    c1col[1] = coef[(kWave + lane) * LB::kRow + 3 * LB::kOrder];
-                    c2col[1] = coef[(kWave + lane) * LB::kRow + 3 * LB::kOrder + 1];
-                }
-            }
-        }
-        auto next_bin = [&]() {                                   // the lowest bin left, or -1 (wave-uniform)
-            int b = -1;
-            if (own0) {
-                b = __builtin_ctzll(own0);
-                own0 &= own0 - 1;
-            } else if (own1) {
-                b = kWave + __builtin_ctzll(own1);
-                own1 &= own1 - 1;
-            }
-            return b;
-        };
-        double a1 = 0.0, a2 = 0.0, C1 = 0.0, C2 = 0.0;
-        int tile = 0;                                             // W > 1: the tile whose terms are being written
-        auto close_tile = [&]() {
-            __syncthreads();                                      // the tile's terms are in LDS
-            if (wid == 0) {
-                const int half = tile * kBinTile / kWave;
-                const uint64_t occ = half ? occ1 : occ0;
-                for (int t = 0; t < kBinTile; ++t) {
-                    const int l = (tile * kBinTile + t) & (kWave - 1);
-                    if (!((occ >> l) & 1)) continue;              // skipped, not added as zero
-                    a1 += term[t * kWave + lane];
-                    a2 += term[(kBinTile + t) * kWave + lane];
-                    C1 += readlane_f64(half ? c1col[1] : c1col[0], l);
-                    C2 += readlane_f64(half ? c2col[1] : c2col[0], l);
-                }
-            }
-            __syncthreads();                                      // ... and summed: the next tile's may replace them
-            ++tile;
-        };
-        auto evaluate = [&](const LB::LaneRow& row, int b) {
-            double t1, t2;
-            if constexpr (W == 1) {
-                LB::evaluate(row, LB::centre(origin, b) - tau, t1, t2);
-                a1 += t1;
-                a2 += t2;
-                LB::add_constants(row, C1, C2);
-            } else {
-                while (tile < b / kBinTile) close_tile();
-                LB::evaluate(row, LB::centre(origin, b) - tau, t1, t2);
-                term[(b % kBinTile) * kWave + lane] = t1;
-                term[(kBinTile + b % kBinTile) * kWave + lane] = t2;
-            }
-        };
-        LB::LaneRow row0, row1;
-        // (behind the last bin its own row is fetched once more: a fetch under a condition would make the wait for
-        // the current row a wait for every load in flight)
-        int b0 = next_bin();
-        if (b0 >= 0) {
-            LB::load_row(coef + b0 * LB::kRow, lane, row0);
-            for (;;) {
-                const int b1 = next_bin();
-                LB::load_row(coef + (b1 >= 0 ? b1 : b0) * LB::kRow, lane, row1);
-                evaluate(row0, b0);
-                if (b1 < 0) break;
-                b0 = next_bin();
-                LB::load_row(coef + (b0 >= 0 ? b0 : b1) * LB::kRow, lane, row0);
-                evaluate(row1, b1);
-                if (b0 < 0) break;
-            }
-        }
-        if constexpr (W > 1)
-            while (tile < (nbins + kBinTile - 1) / kBinTile) close_tile();
-        S1 = a1 + C1;
-        S2 = a2 + C2;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *q.ran = seq;
-    if (s >= a.ns || (W > 1 && wid != 0)) return;
-    a.part1[s] = S1;
-    a.part2[s] = S2;
-    a.cs_out[s] = 0.0;
-}
 #endif  // !OBE_PLUGIN_MODEL_HEADER
 
 struct UtilArgs {
@@ -1542,6 +1421,192 @@ __global__ __launch_bounds__(FG * WS) void sweep_finalize(const double* __restri
         bk[blockIdx.x] = kappa;
     }
 }
+
+// what bin_eval_kernel finishes its settings with and where the results go; yvar = NULL: it ends with part1 / part2 /
+// cs_out, and finishes nothing (obe_sweep_kernel_time)
+struct BinFinish {
+    UtilArgs ua;
+    int full_mode;
+    double* yvar;
+    double* utility;
+    double* bv;
+    int64_t* bi;
+    double* bk;
+};
+
+#ifndef OBE_PLUGIN_MODEL_HEADER
+// `ran` receives `seq`, as in cell_eval_kernel.  A bin's row is the same for the 64 settings of a wavefront, so it is
+// held in registers across the lanes and named lane by lane where it is used (obe_models.h: LorentzBins::LaneRow): a
+// wavefront fetches the rows of its own bins from q.coef (at most OBE_BIN_MAX rows of 688 bytes, the same lines for
+// every wavefront of the chip), the row of its next occupied bin before it evaluates the current one, and the series
+// sums wait for no memory.  (The rows used to come through an LDS tile: one exposed LDS round trip per series step,
+// DESIGN.md.)  Two register sets take turns, so that no row register is ever copied.  The occupied bins are two
+// ballots over binstart (lane <-> bin), walked lowest first.
+// A workgroup holds G groups of 64 settings (lane <-> setting) and W wavefronts for each of them.
+// <4, 1>: a workgroup of kBlock threads, every wavefront walks every occupied bin of its own group; no LDS, no barrier.
+// W > 1: of every tile of kBinTile bins wavefront w of a group evaluates the occupied bins t = w, w + W, ... and leaves
+// their t1, t2 in LDS, and behind a barrier wavefront 0 of the group adds them in bin order, as the one wavefront of
+// W = 1 does: the same numbers in the same order, the same bits, and the one dependent chain per bin is walked by W
+// wavefronts at once (plan_bin_eval_waves; DESIGN.md, "Several wavefronts per group of settings").  Every wavefront of
+// a workgroup passes two barriers per tile of the plan, whichever bins it owns: nbins and the abort word (read once
+// per workgroup where W > 1) are the same for all.  All 64 lanes stay active to the end (LaneRow).
+// The bin form makes ONE chunk of moments, and the wavefront that holds S1 / S2 of a group is the group of 64 settings
+// of a workgroup of sweep_finalize<kFinGroupsFew>: it finishes its own settings (BinFinish) with finalize's device
+// functions on finalize's operands, and argmax_fold receives the partials finalize would have written.
+constexpr int kBinTile = 16;
+template <int G, int W>
+__global__ __launch_bounds__(G * W * kWave, W == 1 ? 1 : 3)           // (W > 1: registers for three wavefronts per SIMD)
+void bin_eval_kernel(SweepArgs a, BinSweepPtrs q, unsigned seq, BinFinish f) {
+    using LB = LorentzBins;
+    constexpr int kThreads = G * W * kWave;
+    static_assert(W > 1 || kThreads == kBlock, "W = 1 is the workgroup of four groups");
+    static_assert((G * W) % 4 == 0, "whole wavefronts for every SIMD of the CU (plan_bin_eval_waves)");
+    static_assert(LB::kMaxBins <= 2 * kWave && kWave % kBinTile == 0, "two ballots name the occupied bins");
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
+    const int grp = wave % G, wid = wave / G;             // wavefront `wid` of group `grp`
+    double* term = nullptr;                               // W > 1, the group's: t1 at [t][lane], t2 at [kBinTile + t][lane]
+    if constexpr (W == 1) {
+        if (sweep_aborted(a.abort)) return;
+    } else {
+        __shared__ double terms[G * 2 * kBinTile * kWave];
+        __shared__ int stop;
+        term = terms + grp * (2 * kBinTile * kWave);
+        if (threadIdx.x == 0) stop = sweep_aborted(a.abort);
+        __syncthreads();
+        if (stop) return;
+    }
+    const int64_t s = ((int64_t)blockIdx.x * G + grp) * kWave + lane;
+    // (a reuse whose keep buffer does not fit the call, or one of whose draws has left its kept bin: as if poisoned)
+    const bool refused = bin_keep_refused(q) || (q.reuse && q.keep->mismatch == q.call);
+    const int nbins = refused ? 0 : __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    double S1 = __builtin_nan(""), S2 = __builtin_nan("");        // poisoned: kappa = NaN, the caller repeats without the bit
+    if (nbins > 0) {
+        double tau;
+        Lorentz<1>::prep_setting(a.settings + (s < a.ns ? s : a.ns - 1), a.m, &tau);
+        const double origin = q.plan->origin;
+        const double* __restrict__ coef = q.coef;
+        // (the row of an empty bin was never written: it is never fetched)
+        const int* __restrict__ start = q.binstart;
+        const bool here0 = lane < nbins && start[lane + 1] != start[lane];
+        const bool here1 = kWave + lane < nbins && start[kWave + lane + 1] != start[kWave + lane];
+        const uint64_t occ0 = __ballot(here0), occ1 = __ballot(here1);            // bins 0-63, 64-127
+        uint64_t own0 = occ0, own1 = occ1;                                        // ... that this wavefront evaluates
+        double c1col[2] = {0.0, 0.0}, c2col[2] = {0.0, 0.0};                      // W > 1, wavefront 0: lane <-> bin
+        if constexpr (W > 1) {
+            uint64_t mine = 0;
+            for (int t = wid; t < kBinTile; t += W) mine |= (uint64_t)1 << t;
+            mine |= mine << 16;
+            mine |= mine << 32;
+            own0 &= mine;
+            own1 &= mine;
+            if (wid == 0) {
+                if (here0) {
+                    c1col[0] = coef[lane * LB::kRow + 3 * LB::kOrder];
+                    c2col[0] = coef[lane * LB::kRow + 3 * LB::kOrder + 1];
+                }
+                if (here1) {
+                    c1col[1] = coef[(kWave + lane) * LB::kRow + 3 * LB::kOrder];
+                    c2col[1] = coef[(kWave + lane) * LB::kRow + 3 * LB::kOrder + 1];
+                }
+            }
+        }
+        auto next_bin = [&]() {                                   // the lowest bin left, or -1 (wave-uniform)
+            int b = -1;
+            if (own0) {
+                b = __builtin_ctzll(own0);
+                own0 &= own0 - 1;
+            } else if (own1) {
+                b = kWave + __builtin_ctzll(own1);
+                own1 &= own1 - 1;
+            }
+            return b;
+        };
+        double a1 = 0.0, a2 = 0.0, C1 = 0.0, C2 = 0.0;
+        int tile = 0;                                             // W > 1: the tile whose terms are being written
+        auto close_tile = [&]() {
+            __syncthreads();                                      // the tile's terms are in LDS
+            if (wid == 0) {
+                const int half = tile * kBinTile / kWave;
+                const uint64_t occ = half ? occ1 : occ0;
+                for (int t = 0; t < kBinTile; ++t) {
+                    const int l = (tile * kBinTile + t) & (kWave - 1);
+                    if (!((occ >> l) & 1)) continue;              // skipped, not added as zero
+                    a1 += term[t * kWave + lane];
+                    a2 += term[(kBinTile + t) * kWave + lane];
+                    C1 += readlane_f64(half ? c1col[1] : c1col[0], l);
+                    C2 += readlane_f64(half ? c2col[1] : c2col[0], l);
+                }
+            }
+            __syncthreads();                                      // ... and summed: the next tile's may replace them
+            ++tile;
+        };
+        auto evaluate = [&](const LB::LaneRow& row, int b) {
+            double t1, t2;
+            if constexpr (W == 1) {
+                LB::evaluate(row, LB::centre(origin, b) - tau, t1, t2);
+                a1 += t1;
+                a2 += t2;
+                LB::add_constants(row, C1, C2);
+            } else {
+                while (tile < b / kBinTile) close_tile();
+                LB::evaluate(row, LB::centre(origin, b) - tau, t1, t2);
+                term[(b % kBinTile) * kWave + lane] = t1;
+                term[(kBinTile + b % kBinTile) * kWave + lane] = t2;
+            }
+        };
+        LB::LaneRow row0, row1;
+        // (behind the last bin its own row is fetched once more: a fetch under a condition would make the wait for
+        // the current row a wait for every load in flight)
+        int b0 = next_bin();
+        if (b0 >= 0) {
+            LB::load_row(coef + b0 * LB::kRow, lane, row0);
+            for (;;) {
+                const int b1 = next_bin();
+                LB::load_row(coef + (b1 >= 0 ? b1 : b0) * LB::kRow, lane, row1);
+                evaluate(row0, b0);
+                if (b1 < 0) break;
+                b0 = next_bin();
+                LB::load_row(coef + (b0 >= 0 ? b0 : b1) * LB::kRow, lane, row0);
+                evaluate(row1, b1);
+                if (b0 < 0) break;
+            }
+        }
+        if constexpr (W > 1)
+            while (tile < (nbins + kBinTile - 1) / kBinTile) close_tile();
+        S1 = a1 + C1;
+        S2 = a2 + C2;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *q.ran = seq;
+    if (W > 1 && wid != 0) return;
+    if (!f.yvar) {
+        if (s >= a.ns) return;
+        a.part1[s] = S1;
+        a.part2[s] = S2;
+        a.cs_out[s] = 0.0;
+        return;
+    }
+    // sweep_finalize's workgroup blockIdx.x * G + grp, with one chunk, one channel and the shift 0: its chain of
+    // additions from 0.0 comes to 0.0 + S (a -0 becomes +0, a NaN stays)
+    const int64_t group = (int64_t)blockIdx.x * G + grp;
+    if (group * kWave >= a.ns) return;
+    double kappa = 0.0;
+    Best best{-INFINITY, INT64_MAX};
+    if (s < a.ns) {
+        const double var = variance_of_moments(0.0 + S1, 0.0 + S2, f.full_mode ? a.moments[0] : 1.0, 0.0, kappa);
+        f.yvar[s] = var;
+        const double u = utility_of(&var, 1, 1, s, f.ua);
+        f.utility[s] = u;
+        best = Best{u, s};
+    }
+    wave_best(best, kappa);
+    if (lane == 0) {
+        f.bv[group] = best.v;
+        f.bi[group] = best.i;
+        f.bk[group] = kappa;
+    }
+}
+#endif  // !OBE_PLUGIN_MODEL_HEADER
 
 __global__ __launch_bounds__(kBlock) void utility_kernel(const double* __restrict__ yvar, int nc, int64_t ns,
                                                          UtilArgs ua, double* __restrict__ utility,
@@ -1931,22 +1996,20 @@ static bool bin_form_selected(const obe_model& m, int flags, int64_t ns, const i
 }
 
 #ifndef OBE_PLUGIN_MODEL_HEADER
-// once per call, behind the pack: the draws grouped by bin and the bins' folded rows (they depend on the cloud alone)
+// once per call: the draws grouped by bin and the bins' folded rows (they depend on the cloud alone)
 // (a reuse has the grouping already: bin_scatter_pack_kernel has put the records where it says)
 static int launch_bin_plan(const SweepArgs& a, const BinSweep& b, hipStream_t st) {
     using LB = LorentzBins;
     if (!b.reuse) {
         const int mm_blocks = static_cast<int>(std::min<int64_t>(kBinMinmaxBlocks, (a.nd + kBlock - 1) / kBlock));
-        bin_minmax_kernel<<<mm_blocks, kBlock, 0, st>>>(a, b.q.minmax);
+        bin_minmax_kernel<<<mm_blocks, kBlock, 0, st>>>(a, b.q);
         OBE_CHECK_LAUNCH("bin_minmax_kernel");
-        bin_plan_kernel<<<1, kBinMinmaxBlocks, 0, st>>>(a, b.q.minmax, mm_blocks, b.q.plan, b.q.keep);
-        OBE_CHECK_LAUNCH("bin_plan_kernel");
         const unsigned group_blocks = (unsigned)((b.units.nunits + kBlock / kWave - 1) / (kBlock / kWave));
-        bin_group_kernel<false><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, b.q);
+        bin_group_kernel<false><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, mm_blocks, b.q);
         OBE_CHECK_LAUNCH("bin_group_kernel<count>");
         bin_scan_kernel<<<LB::kMaxBins, kBlock, 0, st>>>(b.units.nunits, b.q, a.abort);
         OBE_CHECK_LAUNCH("bin_scan_kernel");
-        bin_group_kernel<true><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, b.q);
+        bin_group_kernel<true><<<group_blocks, kBlock, 0, st>>>(a, b.units.per, b.units.nunits, mm_blocks, b.q);
         OBE_CHECK_LAUNCH("bin_group_kernel<scatter>");
     }
     bin_moments_kernel<<<(unsigned)b.items, kWave, 0, st>>>(b.q, a.abort);
@@ -1955,15 +2018,16 @@ static int launch_bin_plan(const SweepArgs& a, const BinSweep& b, hipStream_t st
     OBE_CHECK_LAUNCH("bin_fold_kernel");
     return 0;
 }
-// in place of launch_sweep: one chunk of moments in part1 / part2, cs_out = 0
-static int launch_bin_sweep(SweepPlan& p, SweepArgs& a, const BinSweep& b, hipStream_t st) {
+// in place of launch_sweep and sweep_finalize (f.yvar = NULL: of launch_sweep, one chunk of moments in part1 / part2,
+// cs_out = 0)
+static int launch_bin_sweep(SweepPlan& p, SweepArgs& a, const BinSweep& b, const BinFinish& f, hipStream_t st) {
     p.nchunks = 1;
     const unsigned groups = (unsigned)((a.ns + kWave - 1) / kWave);
     switch (plan_bin_eval_waves(a.ns)) {             // (the shapes of kBinEvalShapes)
-        case 8: bin_eval_kernel<1, 8><<<groups, 8 * kWave, 0, st>>>(a, b.q, b.seq); break;
-        case 6: bin_eval_kernel<2, 6><<<(groups + 1) / 2, 12 * kWave, 0, st>>>(a, b.q, b.seq); break;
-        case 3: bin_eval_kernel<4, 3><<<(groups + 3) / 4, 12 * kWave, 0, st>>>(a, b.q, b.seq); break;
-        default: bin_eval_kernel<4, 1><<<(groups + 3) / 4, kBlock, 0, st>>>(a, b.q, b.seq);
+        case 8: bin_eval_kernel<1, 8><<<groups, 8 * kWave, 0, st>>>(a, b.q, b.seq, f); break;
+        case 6: bin_eval_kernel<2, 6><<<(groups + 1) / 2, 12 * kWave, 0, st>>>(a, b.q, b.seq, f); break;
+        case 3: bin_eval_kernel<4, 3><<<(groups + 3) / 4, 12 * kWave, 0, st>>>(a, b.q, b.seq, f); break;
+        default: bin_eval_kernel<4, 1><<<(groups + 3) / 4, kBlock, 0, st>>>(a, b.q, b.seq, f);
     }
     OBE_CHECK_LAUNCH("bin_eval_kernel");
     return 0;
@@ -1976,7 +2040,7 @@ static int launch_bin_scatter_pack(const SweepArgs& a, const BinSweep& b, hipStr
 }
 #else
 static int launch_bin_plan(const SweepArgs&, const BinSweep&, hipStream_t) { return 0; }
-static int launch_bin_sweep(SweepPlan&, SweepArgs&, const BinSweep&, hipStream_t) { return 0; }
+static int launch_bin_sweep(SweepPlan&, SweepArgs&, const BinSweep&, const BinFinish&, hipStream_t) { return 0; }
 static int launch_bin_scatter_pack(const SweepArgs&, const BinSweep&, hipStream_t) { return 0; }
 #endif
 
@@ -2067,6 +2131,7 @@ static int prepare_sweep(const obe_model* m, obe_model& mm, const double* d_sett
             q.coef = base + BL::kCoef;
             q.part = base + BL::kPart;
             q.sorted = base + BL::sorted(nd);
+            q.code = reinterpret_cast<int*>(w.packed);        // (no plain packed copy in this form: nd ints of its room)
             bins->units = plan_bin_units(nd);
             bins->items = bin_max_items(nd);
             // a keep buffer of the caller's (full sweeps only: draws are drawn anew for every call), large enough
@@ -2079,6 +2144,7 @@ static int prepare_sweep(const obe_model* m, obe_model& mm, const double* d_sett
                 q.binstart = ints + BinKeepLayout::kStarts;
                 q.itemstart = q.binstart + LorentzBins::kMaxBins + 2;
                 q.dest = ints + BinKeepLayout::kDest;
+                q.code = q.dest;
                 q.reuse = bins->reuse = (flags & OBE_SWEEP_BINS_KEPT) != 0;
                 q.keep_nd = static_cast<int>(nd);
                 memcpy(&q.keep_dbits, &mm.consts[0], sizeof q.keep_dbits);
@@ -2252,9 +2318,13 @@ static int sweep_utility(const obe_model* m, const double* d_settings, int64_t l
             g_timing.device = dev;
         }
     }
+    int nb = static_cast<int>((n_settings + kFinSettings - 1) / kFinSettings);
+    if (nb > kFinMaxBlocks) return bad_arg("obe_sweep_utility: more than 4 194 304 settings per call");
+    const BinFinish fin{ua, d_draw_idx == nullptr, d_yvar, d_utility, w.bv, w.bi, w.bk};
     int rc = dispatch_model(mm, [&](auto M) -> int {
-        // (a reuse of a kept grouping packs every draw straight to its sorted position; nothing reads the plain copy)
-        if (int e = bins.on && bins.reuse ? launch_bin_scatter_pack(a, bins, st) : launch_pack<decltype(M)>(a, st)) return e;
+        // (the bin form has no plain packed copy: a rebuild of the grouping packs every draw straight to its sorted
+        // position, and so does a reuse of a kept one, here)
+        if (int e = !bins.on ? launch_pack<decltype(M)>(a, st) : bins.reuse ? launch_bin_scatter_pack(a, bins, st) : 0) return e;
         if (cells.on || bins.on) {
             const unsigned seq = timed && nowait ? (++g_timing.seq ? g_timing.seq : ++g_timing.seq) : 0u;      // (never 0)
             cells.seq = bins.seq = seq;
@@ -2265,15 +2335,13 @@ static int sweep_utility(const obe_model* m, const double* d_settings, int64_t l
         // (the bins are a function of the cloud: grouping it is part of the sweep, and of its time)
         if (bins.on)
             if (int e = launch_bin_plan(a, bins, st)) return e;
-        const int e = bins.on    ? launch_bin_sweep(plan, a, bins, st)
+        const int e = bins.on    ? launch_bin_sweep(plan, a, bins, fin, st)
                       : cells.on ? launch_cell_sweep(plan, a, cells, st)
                                  : launch_sweep<decltype(M)>(plan, a, shifted, st);
         if (timed) (void)hipEventRecord(g_timing.e1, st);
         return e;
     });
     if (rc) return rc;
-    int nb = static_cast<int>((n_settings + kFinSettings - 1) / kFinSettings);
-    if (nb > kFinMaxBlocks) return bad_arg("obe_sweep_utility: more than 4 194 304 settings per call");
     // (FG chunk groups x WS settings per workgroup: see sweep_finalize)
     auto finalize = [&](auto FG, auto WS) {
         sweep_finalize<decltype(FG)::value, decltype(WS)::value><<<nb, decltype(FG)::value * decltype(WS)::value, 0, st>>>(
@@ -2281,7 +2349,9 @@ static int sweep_utility(const obe_model* m, const double* d_settings, int64_t l
             d_yvar, d_utility, w.bv, w.bi, w.bk, a.abort);
     };
     using std::integral_constant;
-    if (plan.nchunks >= kFinManyChunks && nb < kFinNarrowBelow) {
+    if (bins.on) {
+        // (bin_eval_kernel has finished its own settings: the nb partials are there)
+    } else if (plan.nchunks >= kFinManyChunks && nb < kFinNarrowBelow) {
         nb = static_cast<int>((n_settings + kFinNarrow - 1) / kFinNarrow);       // (< 512: within the argmax slots)
         finalize(integral_constant<int, kFinGroupsMany>{}, integral_constant<int, kFinNarrow>{});
     } else if (plan.nchunks >= kFinManyChunks)
@@ -2363,12 +2433,12 @@ int obe_sweep_kernel_time(const obe_model* m, const double* d_settings, int64_t 
         // the rebuild's, whatever a caller of obe_sweep_utility_keep may have kept)
         if (bins.on) {
             if (int e = launch_bin_plan(a, bins, st)) return e;
-            return launch_bin_sweep(plan, a, bins, st);
+            return launch_bin_sweep(plan, a, bins, BinFinish{}, st);
         }
         if (cells.on) return launch_cell_sweep(plan, a, cells, st);
         return dispatch_model(mm, [&](auto M) -> int { return launch_sweep<decltype(M)>(plan, a, shifted, st); });
     };
-    int rc = dispatch_model(mm, [&](auto M) -> int { return launch_pack<decltype(M)>(a, st); });
+    int rc = bins.on ? 0 : dispatch_model(mm, [&](auto M) -> int { return launch_pack<decltype(M)>(a, st); });
     if (!rc && cells.on) rc = launch_cell_plan(a, cells, st);
     if (rc) {
         (void)hipEventDestroy(e0);
