@@ -625,10 +625,11 @@ OBE_API int64_t obe_sweep_bins_keep_bytes(int64_t n_draws);
  *   OBE_SWEEP_BINS_KEPT clear: the sweep of OBE_SWEEP_BINS, which leaves its plan, its tables and every draw's
  *     sorted position in d_keep and marks the buffer complete with its last grouping launch (a poisoned plan is kept
  *     as such; a speculative call that is aborted leaves the buffer as it was);
- *   OBE_SWEEP_BINS_KEPT set: the pack and the five grouping launches are replaced by ONE launch that writes every
- *     draw's packed record straight to its kept position — the same records in the same places, so the same bits as a
- *     rebuild.  The caller's word alone decides nothing: every kernel first checks the head (complete, made for
- *     n_particles draws and this d), and the pack checks of every draw that its x0/d is finite and still lies in the
+ *   OBE_SWEEP_BINS_KEPT set: the four grouping launches of a rebuild (it has no pack of its own: the last of them
+ *     forms the records) are replaced by ONE launch that writes every draw's packed record straight to its kept
+ *     position — the same records in the same places, so the same bits as a rebuild.  The caller's word alone decides
+ *     nothing: every kernel first checks the head (complete, made for n_particles draws and this d), and that one
+ *     launch checks of every draw that its x0/d is finite and still lies in the
  *     bin whose run holds its kept position.  A buffer that fails either check makes the call return *h_factor = NaN
  *     and NaN variances, as a poisoned plan does, and nothing is written through it: the caller repeats the call
  *     without the bit.  (A particle that moved within its bin passes, and gives what a rebuild gives.)

@@ -1,5 +1,5 @@
 """obe_sweep_bins_eval_waves(): how many wavefronts share a group of 64 settings in bin_eval_kernel, as a function of
-the settings of the call (csrc/obe_sweep.hip: plan_bin_eval_waves; DESIGN.md, "Several wavefronts per group of
+the settings of the call (csrc/obe_sweep_bins.h: plan_bin_eval_waves; DESIGN.md, "Several wavefronts per group of
 settings").  Host only, no GPU."""
 import numpy as np
 import pytest

@@ -1,6 +1,6 @@
 """The bin form of the one-peak Lorentzian's unshifted sweep (include/obe_hip.h: OBE_SWEEP_BINS), on the host: a
 NumPy statement of the scheme of csrc/obe_models.h (LorentzBins) in the summation order of the kernels of
-csrc/obe_sweep.hip — the draws grouped stably by bin, items of 1024 draws summed lane by lane and by a butterfly,
+csrc/obe_sweep_bins.h — the draws grouped stably by bin, items of 1024 draws summed lane by lane and by a butterfly,
 the items of a bin folded by 16 strided groups, each series from the highest order down, the bins in order, C1 and
 C2 last — against a long-double two-pass variance, and the decisions of obe_sweep_bins_plan().  No GPU.
 
@@ -15,7 +15,7 @@ from optbayesexpt_amd import _lib
 RHO = 1.0 / _lib.OBE_CELL_RHO_INV
 P = _lib.OBE_CELL_ORDER
 WIDTH = 2.0 * RHO
-ITEM, LANES, GROUPS = 1024, 64, 16          # csrc/obe_sweep.hip: kBinChunk, kWave, kBinFoldGroups
+ITEM, LANES, GROUPS = 1024, 64, 16          # csrc/obe_sweep_bins.h: kBinChunk, kBinFoldGroups; obe_common.h: kWave
 
 
 def item_sums(terms):

@@ -1,4 +1,4 @@
-"""bin_eval_kernel finishing its own settings (csrc/obe_sweep.hip: BinFinish) - variance, utility, and the first maximum
+"""bin_eval_kernel finishing its own settings (csrc/obe_sweep_bins.h: bin_eval_kernel; csrc/obe_sweep_common.h: BinFinish) - variance, utility, and the first maximum
 and worst kappa of every group of 64 settings, which used to be a launch of sweep_finalize over one chunk of moments -
 against the bits of that launch: tests/golden/bin_chain_parent_bits.npz (see test_gpu_bin_rebuild.py for how and from
 which commit it was recorded).

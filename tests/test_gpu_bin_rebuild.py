@@ -1,4 +1,4 @@
-"""The rebuild of the bin grouping in four launches (csrc/obe_sweep.hip: bin_minmax_kernel, bin_group_kernel<false>
+"""The rebuild of the bin grouping in four launches (csrc/obe_sweep_bins.h: bin_minmax_kernel, bin_group_kernel<false>
 with the plan, bin_scan_kernel, bin_group_kernel<true> as the scatter-pack; no sweep_pack_kernel) against the bits of
 the six launches behind a pack that it replaces: tests/golden/bin_chain_parent_bits.npz, recorded on one MI355X with
 tools/record_bin_chain_bits.py (which imports the cases from this file and from test_gpu_bin_eval_finalize.py) from the
@@ -34,10 +34,12 @@ HEAD_BYTES = 4096
 
 
 def sweep_call(o, n_settings, s_begin=0, particles=None, n_particles=None, w=None, draw_idx=None, flags=None,
-               keep=None, noise=("scalar", 250000.0), cost=None):
+               keep=None, noise=("scalar", 250000.0), cost=None, ws_bytes=None, refused=False):
     """One obe_sweep_utility[_keep] call on settings [s_begin, s_begin + n_settings) of the object, with its moments:
     {yvar, utility, best, idx, kappa}.  particles: a (3, ld_p) device tensor in place of the object's cloud;
-    noise: ("scalar", v), ("rows", array of n_settings) or ("moments", row); cost: None (1.0) or an array."""
+    noise: ("scalar", v), ("rows", array of n_settings) or ("moments", row); cost: None (1.0) or an array.
+    ws_bytes: the size the call is TOLD the object's workspace has (the buffer itself is what it is); refused: the call
+    must fail, and its error text is returned."""
     import torch
     from optbayesexpt_amd import _lib
     from optbayesexpt_amd.particlepdf import _ptr, _P
@@ -49,13 +51,13 @@ def sweep_call(o, n_settings, s_begin=0, particles=None, n_particles=None, w=Non
     dev = w0.device
     f64 = dict(dtype=torch.float64, device=dev)
     if noise[0] == "scalar":
-        noise_t, noise_ld = torch.full((1,), noise[1], **f64), 0
+        noise_t, noise_ld = torch.full((o.n_channels,), noise[1], **f64), 0
     elif noise[0] == "rows":
         noise_t, noise_ld = torch.from_numpy(np.ascontiguousarray(noise[1])).to(dev), n_settings
     else:
         noise_t, noise_ld = mom, -(int(noise[1]) + 1)
     cost_t = None if cost is None else torch.from_numpy(np.ascontiguousarray(cost)).to(dev)
-    yvar = torch.zeros((1, n_settings), **f64)
+    yvar = torch.zeros((o.n_channels, n_settings), **f64)
     util = torch.zeros(n_settings, **f64)
     out = _lib.pinned_array(4)
     best, idx, kappa = out[0:1], out.view(np.int64)[1:2], out[2:3]
@@ -65,14 +67,18 @@ def sweep_call(o, n_settings, s_begin=0, particles=None, n_particles=None, w=Non
             n_particles, _ptr(w), None if draw_idx is None else _ptr(draw_idx),
             0 if draw_idx is None else draw_idx.numel(), _ptr(mom), flags, _ptr(noise_t), noise_ld,
             None if cost_t is None else _ptr(cost_t), 1.0, _ptr(yvar), _ptr(util), hp(best), hp(idx), hp(kappa),
-            _ptr(o._ws), o._ws_bytes, o._stream())
+            _ptr(o._ws), o._ws_bytes if ws_bytes is None else ws_bytes, o._stream())
     if keep is None:
         rc = o._mlib.cdll.obe_sweep_utility(*head)
     else:
         rc = o._mlib.cdll.obe_sweep_utility_keep(*head, _ptr(keep), keep.numel() * 4)
     torch.cuda.synchronize()
+    if refused:
+        assert rc != 0, "the call was accepted"
+        return o._mlib.last_error()
     assert rc == 0, o._mlib.last_error()
-    return {"yvar": yvar.cpu().numpy()[0], "utility": util.cpu().numpy(), "best": np.array(float(best[0])),
+    yvar = yvar.cpu().numpy()
+    return {"yvar": yvar[0] if o.n_channels == 1 else yvar, "utility": util.cpu().numpy(), "best": np.array(float(best[0])),
             "idx": np.array(int(idx[0])), "kappa": np.array(float(kappa[0]))}
 
 

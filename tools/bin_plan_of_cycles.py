@@ -25,7 +25,7 @@ sim = np.random.default_rng(4321)
 
 def plan():
     """(nbins, poison, occupied bins) of the head of the keep buffer: BinPlan {double origin; int nbins; unsigned
-    poison}, then binstart[OBE_BIN_MAX + 2] from int 16 on (csrc/obe_sweep.hip: BinKeep, BinKeepLayout)."""
+    poison}, then binstart[OBE_BIN_MAX + 2] from int 16 on (csrc/obe_sweep_bins.h: BinKeep, BinKeepLayout)."""
     keep = obe.__dict__.get("_bins_keep")
     if keep is None:
         return None

@@ -2,6 +2,7 @@
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -Ioptbayesexpt_amd/csrc \
           --cuda-device-only -S optbayesexpt_amd/csrc/obe_sweep.hip -o /tmp/sweep.s
+    (obe_sweep.hip includes obe_sweep_cells.h and obe_sweep_bins.h: the kernels of every form are in its output)
     python tools/count_isa.py /tmp/sweep.s 'LorentzILi1EEELi8ELb0' 16
 
 prints the instruction mix of the basic block with the most FP64 instructions and the issue
