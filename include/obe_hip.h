@@ -613,6 +613,13 @@ OBE_API int obe_sweep_utility(const obe_model* m,
  * obe_sweep_bins_keep_bytes(n_particles) bytes, 16-byte aligned, used by one sweep at a time (a head of 16 ints, the
  * two tables of OBE_BIN_MAX + 2 ints and one int32 position per draw; host only, nothing is launched). */
 OBE_API int64_t obe_sweep_bins_keep_bytes(int64_t n_draws);
+/* The records form of the same buffer: obe_sweep_bins_keep_bytes(n) bytes as above, unchanged, and behind them, each
+ * 16-byte aligned, the particle part of every draw in sorted order (24 bytes: x0/d, a, b) and a dense array of the
+ * draws' sqrt(w) in the same order; at least obe_sweep_bins_keep_bytes(n) + 32 n bytes, a multiple of 16 (host only,
+ * nothing is launched).  The keep_bytes of a call selects the form: a call that is told at least this size keeps the
+ * draws' records in d_keep instead of the workspace, and says so in the head (the first of its seven pad words: the
+ * only byte of the first obe_sweep_bins_keep_bytes(n) that differs from what a call told the smaller size leaves). */
+OBE_API int64_t obe_sweep_bins_keep_records_bytes(int64_t n_draws);
 /* OBE_SWEEP_BINS_KEPT (a bit of `shifted`): the caller says that d_keep was filled by an earlier call of
  * obe_sweep_utility_keep() with the same d_particles, ld_p, n_particles and d, and that no particle value has
  * changed since.  Honoured only together with OBE_SWEEP_BINS where that bit is, in a full sweep (d_draw_idx == NULL:
@@ -633,6 +640,15 @@ OBE_API int64_t obe_sweep_bins_keep_bytes(int64_t n_draws);
  *     bin whose run holds its kept position.  A buffer that fails either check makes the call return *h_factor = NaN
  *     and NaN variances, as a poisoned plan does, and nothing is written through it: the caller repeats the call
  *     without the bit.  (A particle that moved within its bin passes, and gives what a rebuild gives.)
+ *   OBE_SWEEP_BINS_KEPT set and keep_bytes >= obe_sweep_bins_keep_records_bytes(n_particles), the records form: the
+ *     call RELIES on what the bit says, "no particle value has changed since".  That one launch writes only sqrt(w) of
+ *     every draw to its kept position: it reads no particle and checks no bin, and the records are formed from the
+ *     kept particle parts, the new weights and d_moments - the bits of a rebuild if the caller's word holds.  What
+ *     is read and written through the buffer still rests on the head alone (the library wrote every position itself,
+ *     and checks its range all the same); the validity of the RESULT rests on the caller's word, as it does for
+ *     d_moments in every sweep: a changed particle gives the sweep of the old particles with the new weights,
+ *     unspecified but finite.  A caller who wants every draw checked passes obe_sweep_bins_keep_bytes(n_particles).
+ *     (A buffer whose last rebuild was told the smaller size has no records: the call takes the checking path.)
  * OBE_SWEEP_SPECULATIVE, OBE_SWEEP_NOWAIT, obe_sweep_timing() and the result records work as in obe_sweep_utility().
  * obe_sweep_kernel_time() has no keep buffer: it times the whole rebuild. */
 OBE_API int obe_sweep_utility_keep(const obe_model* m,

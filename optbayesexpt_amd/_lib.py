@@ -135,7 +135,7 @@ MODEL_ENTRY_POINTS = ("obe_model_validate", "obe_workspace_bytes", "obe_sweep_se
                       "obe_bayes_update_sweep",
                       "obe_eval_over_particles",
                       "obe_eval_over_settings", "obe_sweep_utility", "obe_sweep_kernel_time", "obe_sweep_timing",
-                      "obe_sweep_utility_keep", "obe_sweep_bins_keep_bytes",
+                      "obe_sweep_utility_keep", "obe_sweep_bins_keep_bytes", "obe_sweep_bins_keep_records_bytes",
                       "obe_eval_draws",
                       "obe_predictive_workspace_bytes", "obe_predictive_moments", "obe_predictive_quantiles",
                       "obe_predictive_score_workspace_bytes", "obe_predictive_logpdf", "obe_predictive_tails",

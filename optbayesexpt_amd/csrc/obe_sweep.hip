@@ -853,6 +853,9 @@ int64_t obe_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_c
 }
 
 int64_t obe_sweep_bins_keep_bytes(int64_t n_draws) { return BinKeepLayout::bytes(n_draws < 1 ? 1 : n_draws); }
+int64_t obe_sweep_bins_keep_records_bytes(int64_t n_draws) {
+    return BinKeepLayout::records_bytes(n_draws < 1 ? 1 : n_draws);
+}
 
 int obe_sweep_utility(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
                       const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,

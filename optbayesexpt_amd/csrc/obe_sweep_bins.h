@@ -1,7 +1,8 @@
 // The bin form of the utility sweep (OBE_SWEEP_BINS, and the kept grouping of obe_sweep_utility_keep): its constants,
 // workspace and keep-buffer layout, its kernels, and BinForm, the host half of one call.  The first part is plain host
-// code and serves every build (obe_sweep_bins_plan, obe_sweep_bins_eval_waves and obe_sweep_bins_keep_bytes answer from
-// it whatever the model); the kernels and BinForm exist where the library has the one-peak Lorentzian.
+// code and serves every build (obe_sweep_bins_plan, obe_sweep_bins_eval_waves, obe_sweep_bins_keep_bytes and
+// obe_sweep_bins_keep_records_bytes answer from it whatever the model); the kernels and BinForm exist where the library
+// has the one-peak Lorentzian.
 #pragma once
 #include "obe_sweep_common.h"
 
@@ -83,7 +84,8 @@ struct BinKeep {           // head of the buffer
     int nd;                // the draws it was made for ...
     unsigned long long dbits;      // ... and the bits of d
     unsigned mismatch;     // the `call` of the last reuse that found a draw outside its kept bin
-    unsigned pad[7];
+    unsigned records;      // kBinKeepMark once the records behind the grouping are complete too (BinKeepLayout)
+    unsigned pad[6];
 };
 static_assert(sizeof(BinKeep) == 64, "the head of the keep buffer is 16 ints");
 constexpr unsigned kBinKeepMark = 0x6b455042u;
@@ -91,6 +93,14 @@ struct BinKeepLayout {      // in ints
     static constexpr int64_t kStarts = sizeof(BinKeep) / sizeof(int);                       // 2 x 130 ints
     static constexpr int64_t kDest = (kStarts + 2 * (LorentzBins::kMaxBins + 2) + 3) & ~(int64_t)3;
     static int64_t bytes(int64_t nd) { return ((kDest + nd) * (int64_t)sizeof(int) + 15) & ~(int64_t)15; }
+    // The records form (obe_sweep_bins_keep_records_bytes): behind the grouping, each piece 16-byte aligned, the
+    // particle part of every draw in sorted order, {x0 / d, a, b}, and a dense array of sqrt(w) in the same order: the
+    // only piece a sweep of the same particles with other weights has to write (it shares no line with the records
+    // but the one at the seam).
+    static constexpr int64_t kRecord = 3;                                                  // doubles per draw
+    static int64_t records_at(int64_t nd) { return bytes(nd); }                            // in bytes
+    static int64_t sw_at(int64_t nd) { return records_at(nd) + ((kRecord * 8 * nd + 15) & ~(int64_t)15); }
+    static int64_t records_bytes(int64_t nd) { return sw_at(nd) + ((8 * nd + 15) & ~(int64_t)15); }
 };
 
 #ifndef OBE_PLUGIN_MODEL_HEADER
@@ -115,7 +125,11 @@ struct BinKeepLayout {      // in ints
 // leaves every draw's sorted position; a later call with OBE_SWEEP_BINS_KEPT runs, in place of the four grouping
 // launches,
 //   bin_scatter_pack_kernel   the record of draw p (bin_record), written to sorted[dest[p]]
-// and then bin_moments_kernel onwards: the same records in the same places, hence the same bits.
+// and then bin_moments_kernel onwards: the same records in the same places, hence the same bits.  With a keep buffer
+// of the records form (BinKeepLayout::records_bytes) the particle part of every record and sqrt(w) live in the buffer
+// too, in sorted order; such a later call runs
+//   bin_refresh_kernel        sqrt(w) of draw p, written to sw[dest[p]]
+// and bin_moments_kernel<true> forms every packed record from those pieces.
 struct BinSweepPtrs {
     BinPlan* plan;
     unsigned* ran;
@@ -136,6 +150,15 @@ struct BinSweepPtrs {
     double* sorted;
 };
 
+// The records form of the keep buffer (a call whose keep_bytes reaches BinKeepLayout::records_bytes): where a rebuild
+// leaves the particle part of every draw and sqrt(w), and where bin_moments_kernel<true> reads them; rec == NULL
+// otherwise, and the packed records go through the workspace's `sorted`.
+struct BinRecords {
+    double* rec;           // [nd][kRecord] x0 / d, a, b in sorted order
+    double* sw;            // [nd] sqrt(w) in sorted order
+    const double* bbar;    // the mean of b: element K + 1 of the mean parameters in d_moments
+};
+
 // OBE_SWEEP_BINS_KEPT: the caller's word that the buffer fits this cloud does not decide what is read through it.  Every
 // kernel of a reuse first looks at the head: a complete grouping (the mark) of this many draws at this d.  (A rebuild
 // reads what its own kernels have just written.)
@@ -146,22 +169,51 @@ __device__ __forceinline__ bool bin_keep_refused(const BinSweepPtrs& q) {
 }
 
 // tau0 of draw p as the sorted record holds it: Lorentz<1>::pack's division, on the draw's own particle
-__device__ __forceinline__ double bin_tau0(const SweepArgs& a, int64_t p) {
+__device__ __forceinline__ double bin_x0(const SweepArgs& a, int64_t p) {
     double w;
     const int64_t src = draw_source(a, p, w);
-    return a.particles[src] / a.m.consts[0];
+    return a.particles[src];
 }
+__device__ __forceinline__ double bin_tau0(const SweepArgs& a, int64_t p) { return bin_x0(a, p) / a.m.consts[0]; }
 
-// the sorted record of draw p: what sweep_pack_kernel<Lorentz<1>> makes of it
-__device__ __forceinline__ void bin_record(const SweepArgs& a, int64_t p, double2& ra, double2& rb) {
+// The packed record of a draw from its particle part {x0 / d, a, b}, sqrt(w) and the mean of b: the expressions of
+// Lorentz<1>::pack behind its division, stated once for the record that is stored (bin_record) and the one that
+// bin_moments_kernel<true> forms from the kept particle part.  (-ffp-contract=off: the same bits in either place.)
+__device__ __forceinline__ void bin_pk(double tau0, double amp, double b, double bbar, double sw, double (&pk)[4]) {
+    pk[0] = tau0;
+    pk[1] = sw * amp;
+    pk[2] = sw * (b - bbar);
+    pk[3] = sw;
+}
+// the particle part of draw p and sqrt of its weight
+__device__ __forceinline__ void bin_particle(const SweepArgs& a, int64_t p, double (&part)[3], double& sw) {
     using M = Lorentz<1>;
     static_assert(packed_width<M>() == 4 && M::NPK == 3, "the sorted records are 32 bytes");
-    double w, pk[4];
+    double w;
     const int64_t src = draw_source(a, p, w);
-    const double sw = sqrt(w);
-    M::pack(ParamRef{a.particles + src, a.ld_p}, a.moments + 2, a.m, sw, pk);
+    sw = sqrt(w);
+    part[0] = a.particles[src] / a.m.consts[0];               // (Lorentz<1>::pack's division)
+    part[1] = a.particles[src + a.ld_p];
+    part[2] = a.particles[src + 2 * a.ld_p];
+}
+// the sorted record of draw p: what sweep_pack_kernel<Lorentz<1>> makes of it
+__device__ __forceinline__ void bin_record(const SweepArgs& a, int64_t p, double2& ra, double2& rb) {
+    double part[3], sw, pk[4];
+    bin_particle(a, p, part, sw);
+    bin_pk(part[0], part[1], part[2], a.moments[4], sw, pk);
     ra = double2{pk[0], pk[1]};
-    rb = double2{pk[2], sw};
+    rb = double2{pk[2], pk[3]};
+}
+
+// the records form: the particle part of draw p and sqrt(w) to their sorted position `pos` in the keep buffer
+__device__ __forceinline__ void bin_store_particle(const SweepArgs& a, int64_t p, int pos, const BinRecords& r) {
+    double part[3], sw;
+    bin_particle(a, p, part, sw);
+    double* __restrict__ out = r.rec + BinKeepLayout::kRecord * (int64_t)pos;
+    out[0] = part[0];
+    out[1] = part[1];
+    out[2] = part[2];
+    r.sw[pos] = sw;
 }
 
 // a draw between the two grouping passes of a rebuild: its bin, and its rank among its unit's draws of that bin
@@ -170,6 +222,9 @@ static_assert((((int64_t)1 << 30) + kBinMaxUnits - 1) / kBinMaxUnits <= ((int64_
                   && LorentzBins::kMaxBins <= (1 << (31 - kBinRankBits)),
               "a unit of a cloud of 2^30 draws (BinForm::selected) has at most 2^19 draws: rank and bin share an int");
 __device__ __forceinline__ int bin_code(int bin, int rank) { return (bin << kBinRankBits) | rank; }
+constexpr int kBinIndexBits = 7;
+constexpr int kBinGroupAhead = 8;         // trips of the counting pass whose loads are in flight together
+static_assert(LorentzBins::kMaxBins == 1 << kBinIndexBits, "a bin index is matched bit by bit (bin_group_kernel<false>)");
 
 // (the first launch of a rebuild: with a keep buffer, no grouping stands behind its head until the scatter pass says so)
 __global__ __launch_bounds__(kBlock) void bin_minmax_kernel(SweepArgs a, BinSweepPtrs q) {
@@ -177,7 +232,10 @@ __global__ __launch_bounds__(kBlock) void bin_minmax_kernel(SweepArgs a, BinSwee
     __shared__ double slo[NW], shi[NW];
     __shared__ int sbad[NW];
     if (sweep_aborted(a.abort)) return;
-    if (q.keep && blockIdx.x == 0 && threadIdx.x == 0) q.keep->mark = 0u;
+    if (q.keep && blockIdx.x == 0 && threadIdx.x == 0) {
+        q.keep->mark = 0u;
+        q.keep->records = 0u;
+    }
     double* __restrict__ minmax = q.minmax;
     double lo = INFINITY, hi = -INFINITY;
     int bad = 0;
@@ -252,15 +310,19 @@ __device__ __forceinline__ int wave_exclusive(int v, int& total) {
 
 // The two grouping passes of a rebuild; a wavefront owns a unit of `per` consecutive draws in both.
 // SCATTER = false, the counting pass: the plan first (bin_plan_of).  Then the wavefront walks its unit in order, 64 draws
-// at a time.  Lane l keeps the count of bins l and l + 64 (c0, c1); per trip the distinct bins of the 64 draws are taken
-// one by one (ballot), and a draw's rank is its bin's count so far plus the number of lower lanes with the same bin.
+// at a time.  The unit's count of every bin is a table in LDS; per trip every lane finds the lanes that hold its own bin
+// (kBinIndexBits ballots, whatever the number of distinct bins among the 64 draws), and a draw's rank is its bin's count
+// so far plus the number of lower lanes with the same bin; the lowest of them adds their number to the count.
 // The counts end as the unit's, and every draw leaves its bin_code.
 // SCATTER = true: lane l holds the first sorted position of (bin l, unit) and of (bin l + 64, unit); every draw's
 // record (bin_record) is formed from the cloud and written at its bin's first position plus its rank.
-template <bool SCATTER>
+// RECORDS (with SCATTER, a keep buffer of the records form): in place of the packed record in the workspace, the
+// draw's particle part and sqrt(w) go to the keep buffer (BinRecords), and the head says that they are complete.
+template <bool SCATTER, bool RECORDS = false>
 __global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t per, int nunits, int mm_blocks,
-                                                           BinSweepPtrs q) {
+                                                           BinSweepPtrs q, BinRecords r) {
     using LB = LorentzBins;
+    static_assert(SCATTER || !RECORDS, "the counting pass stores no record");
     if (sweep_aborted(a.abort)) return;
     const int lane = threadIdx.x & (kWave - 1);
     const int unit = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
@@ -273,6 +335,7 @@ __global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t 
             q.keep->dbits = q.keep_dbits;
             q.keep->mismatch = 0u;
             q.keep->mark = kBinKeepMark;
+            if constexpr (RECORDS) q.keep->records = kBinKeepMark;
         }
     } else {
         plan = bin_plan_of(a, q.minmax, mm_blocks);
@@ -305,45 +368,76 @@ __global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t 
     if (unit >= nunits) return;
     const int64_t begin = (int64_t)unit * per;
     const int64_t end = begin + per < a.nd ? begin + per : a.nd;
-    for (int64_t i0 = begin; i0 < end; i0 += kWave) {
-        const int64_t i = i0 + lane;
-        const bool live = i < end;
-        if constexpr (SCATTER) {
+    if constexpr (SCATTER) {
+        for (int64_t i0 = begin; i0 < end; i0 += kWave) {
+            const int64_t i = i0 + lane;
+            const bool live = i < end;
             const int code = live ? q.code[i] : 0;
             const int bin = code >> kBinRankBits;
             // (every lane takes part in the exchange: a lane without a draw asks for bin 0)
             const int first0 = __shfl(c0, bin & (kWave - 1), kWave), first1 = __shfl(c1, bin & (kWave - 1), kWave);
             const int pos = (bin < kWave ? first0 : first1) + (code & ((1 << kBinRankBits) - 1));
             if (live && pos >= 0 && pos < a.nd) {
-                double2 ra, rb;
-                bin_record(a, i, ra, rb);
-                double2* __restrict__ out = reinterpret_cast<double2*>(q.sorted) + 2 * (int64_t)pos;
-                out[0] = ra;
-                out[1] = rb;
+                if constexpr (RECORDS) {
+                    bin_store_particle(a, i, pos, r);
+                } else {
+                    double2 ra, rb;
+                    bin_record(a, i, ra, rb);
+                    double2* __restrict__ out = reinterpret_cast<double2*>(q.sorted) + 2 * (int64_t)pos;
+                    out[0] = ra;
+                    out[1] = rb;
+                }
             }
             if (q.dest && live) q.dest[i] = pos;       // (over the code this lane has just read)
-        } else {
-            const int bin = live ? LB::bin_of(plan.origin, bin_tau0(a, i), nbins) : -1;
-            int rank = 0;
-            unsigned long long todo = __ballot(live);
-            while (todo) {
-                const int b = __builtin_amdgcn_readlane(bin, __builtin_ctzll(todo));      // (wave-uniform)
-                const unsigned long long same = __ballot(bin == b);
-                const int figure = __builtin_amdgcn_readlane(b < kWave ? c0 : c1, b & (kWave - 1));
-                if (bin == b) rank = figure + __popcll(same & ((1ull << lane) - 1ull));
-                const int n = __popcll(same);
-                if (lane == (b & (kWave - 1))) {
-                    if (b < kWave) c0 += n;
-                    else c1 += n;
-                }
-                todo &= ~same;
-            }
-            if (live) q.code[i] = bin_code(bin, rank);
         }
-    }
-    if constexpr (!SCATTER) {
-        q.counts[lane * kBinMaxUnits + unit] = c0;
-        q.counts[(lane + kWave) * kBinMaxUnits + unit] = c1;
+    } else {
+        // the unit's count of every bin so far: a table of the wavefront's own (same-wavefront LDS accesses execute in
+        // order; the fence keeps the compiler from moving one trip's read above the trip before's stores)
+        __shared__ int tally[kBlock / kWave][LB::kMaxBins];
+        int* count = tally[threadIdx.x / kWave];
+        count[lane] = 0;
+        count[lane + kWave] = 0;
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        const double d = a.m.consts[0];
+        const unsigned long long below = (1ull << lane) - 1ull;
+        // One trip: the 64 draws from i0 on, lane <-> draw, x0 the lane's own.
+        auto trip = [&](int64_t i0, double x0) {
+            const int64_t i = i0 + lane;
+            const bool live = i < end;
+            const int bin = live ? LB::bin_of(plan.origin, x0 / d, nbins) : -1;        // (bin_tau0's division)
+            // the live lanes that hold this lane's bin: one ballot per bit of a bin index, kept where the lane's own
+            // bit agrees.  (A lane without a draw has every bit set and is in the ballots of the set bits; the live
+            // lanes drop it with the first mask, and it matches nobody itself.)
+            unsigned long long same = __ballot(live);
+#pragma unroll
+            for (int k = 0; k < kBinIndexBits; ++k) {
+                const bool bit = (bin >> k) & 1;
+                const unsigned long long have = __ballot(bit);
+                same &= bit ? have : ~have;
+            }
+            if (!live) same = 0ull;
+            const int sofar = live ? count[bin] : 0;
+            // (one leader per bin and trip: no two lanes store to one word)
+            if (live && (same & below) == 0ull) count[bin] = sofar + __popcll(same);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            if (live) q.code[i] = bin_code(bin, sofar + __popcll(same & below));
+        };
+        // The x0 of kBinGroupAhead trips are asked for together, before the first of them is matched: a unit of a
+        // cloud of 2^20 draws is eight trips, and a trip's arithmetic is short against one round trip to memory.  A lane
+        // without a draw asks for the unit's last one (a load under a condition would be waited for where it stands).
+        for (int64_t i0 = begin; i0 < end; i0 += kBinGroupAhead * kWave) {
+            double x0[kBinGroupAhead];
+#pragma unroll
+            for (int k = 0; k < kBinGroupAhead; ++k) {
+                const int64_t i = i0 + k * kWave + lane;
+                x0[k] = bin_x0(a, i < end ? i : end - 1);
+            }
+#pragma unroll
+            for (int k = 0; k < kBinGroupAhead; ++k)
+                if (i0 + k * kWave < end) trip(i0 + k * kWave, x0[k]);
+        }
+        q.counts[lane * kBinMaxUnits + unit] = count[lane];
+        q.counts[(lane + kWave) * kBinMaxUnits + unit] = count[lane + kWave];
     }
 }
 
@@ -353,6 +447,32 @@ __global__ __launch_bounds__(kBlock) void bin_group_kernel(SweepArgs a, int64_t 
 // the bin whose run holds its kept position: a tau0 that is not finite, lies outside the plan or in another bin stores
 // the call's number into the head, and bin_eval_kernel answers NaN for the whole call, as for a poisoned plan.  (A
 // draw that moved WITHIN its bin gives what a rebuild would: the order of a stable sort by bin does not change.)
+// (RECORDS: the verified draw's particle part and sqrt(w) go to the keep buffer's records instead)
+template <bool RECORDS>
+__device__ __forceinline__ void bin_scatter_pack_draw(const SweepArgs& a, const BinSweepPtrs& q, const BinRecords& r,
+                                                      double origin, int nbins, int64_t p) {
+    using LB = LorentzBins;
+    double2 ra, rb;
+    bin_record(a, p, ra, rb);
+    const int pos = q.dest[p];
+    const double t = (ra.x - origin) * (1.0 / LB::kWidth);       // (bin_of's expression; a NaN fails the test)
+    bool ok = t >= 0.0 && t < (double)nbins && pos >= 0 && pos < a.nd;
+    if (ok) {
+        const int b = LB::bin_of(origin, ra.x, nbins);
+        ok = q.binstart[b] <= pos && pos < q.binstart[b + 1];
+    }
+    if (ok) {
+        if constexpr (RECORDS) {
+            bin_store_particle(a, p, pos, r);
+        } else {
+            double2* __restrict__ out = reinterpret_cast<double2*>(q.sorted) + 2 * (int64_t)pos;
+            out[0] = ra;
+            out[1] = rb;
+        }
+    } else {
+        q.keep->mismatch = q.call;
+    }
+}
 __global__ __launch_bounds__(kBlock) void bin_scatter_pack_kernel(SweepArgs a, BinSweepPtrs q) {
     using LB = LorentzBins;
     if (sweep_aborted(a.abort)) return;
@@ -360,23 +480,35 @@ __global__ __launch_bounds__(kBlock) void bin_scatter_pack_kernel(SweepArgs a, B
     const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
     if (nbins <= 0 || nbins > LB::kMaxBins) return;
     const double origin = q.plan->origin;
-    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < a.nd; p += (int64_t)gridDim.x * kBlock) {
-        double2 ra, rb;
-        bin_record(a, p, ra, rb);
-        const int pos = q.dest[p];
-        const double t = (ra.x - origin) * (1.0 / LB::kWidth);       // (bin_of's expression; a NaN fails the test)
-        bool ok = t >= 0.0 && t < (double)nbins && pos >= 0 && pos < a.nd;
-        if (ok) {
-            const int b = LB::bin_of(origin, ra.x, nbins);
-            ok = q.binstart[b] <= pos && pos < q.binstart[b + 1];
+    for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < a.nd; p += (int64_t)gridDim.x * kBlock)
+        bin_scatter_pack_draw<false>(a, q, BinRecords{}, origin, nbins, p);
+}
+
+// OBE_SWEEP_BINS_KEPT with a keep buffer of the records form, in place of bin_scatter_pack_kernel: the particles have
+// not changed (the caller's word, as for d_moments), so of a draw's record only sqrt(w) is new, and it goes to
+// sw[dest[p]]: no particle is read, nothing is divided and no bin is checked.  What is written through still rests on
+// the head alone (bin_keep_refused, and the library wrote dest itself: 0 <= dest[p] < nd is checked all the same).
+// A buffer whose grouping is complete but whose records are not (its last rebuild was told the smaller size) takes the
+// verifying path of bin_scatter_pack_kernel, into the records.  A workgroup owns `per` consecutive draws: the draws of
+// one bin in it are neighbours in sw, and a line of sw is not split over the L2s of several XCDs more than it must.
+__global__ __launch_bounds__(kBlock) void bin_refresh_kernel(SweepArgs a, BinSweepPtrs q, BinRecords r, int64_t per) {
+    using LB = LorentzBins;
+    if (sweep_aborted(a.abort)) return;
+    if (bin_keep_refused(q)) return;
+    const int nbins = __builtin_amdgcn_readfirstlane(q.plan->nbins);
+    if (nbins <= 0 || nbins > LB::kMaxBins) return;
+    const int64_t begin = (int64_t)blockIdx.x * per;
+    const int64_t end = begin + per < a.nd ? begin + per : a.nd;
+    if (q.keep->records == kBinKeepMark) {
+        const double* __restrict__ w = a.weights;
+        const int* __restrict__ dest = q.dest;
+        for (int64_t p = begin + threadIdx.x; p < end; p += kBlock) {
+            const int pos = dest[p];
+            if (pos >= 0 && pos < a.nd) r.sw[pos] = sqrt(w[p]);
         }
-        if (ok) {
-            double2* __restrict__ out = reinterpret_cast<double2*>(q.sorted) + 2 * (int64_t)pos;
-            out[0] = ra;
-            out[1] = rb;
-        } else {
-            q.keep->mismatch = q.call;
-        }
+    } else {
+        const double origin = q.plan->origin;
+        for (int64_t p = begin + threadIdx.x; p < end; p += kBlock) bin_scatter_pack_draw<true>(a, q, r, origin, nbins, p);
     }
 }
 
@@ -458,8 +590,11 @@ __device__ __forceinline__ int halving_index(int lane, int e) {
     return real ? j : -1;
 }
 
-// one wavefront per item: kBinChunk consecutive sorted draws of one bin
-__global__ __launch_bounds__(kWave) void bin_moments_kernel(BinSweepPtrs q, const unsigned* abort) {
+// one wavefront per item: kBinChunk consecutive sorted draws of one bin.  RECORDS: the keep buffer's records form
+// (BinRecords) in place of the packed records of `sorted`: a draw's packed record is formed here, from its kept particle
+// part, sqrt(w) and the mean of b (bin_pk: the stored record's expressions on its operands, hence its bits).
+template <bool RECORDS>
+__global__ __launch_bounds__(kWave) void bin_moments_kernel(BinSweepPtrs q, const unsigned* abort, BinRecords r) {
     using LB = LorentzBins;
     if (sweep_aborted(abort)) return;
     if (bin_keep_refused(q)) return;
@@ -474,28 +609,62 @@ __global__ __launch_bounds__(kWave) void bin_moments_kernel(BinSweepPtrs q, cons
     const int last = q.binstart[bin + 1];
     const int end = first + kBinChunk < last ? first + kBinChunk : last;
     const double tb = LB::centre(q.plan->origin, bin);
-    const double2* __restrict__ rec = reinterpret_cast<const double2*>(q.sorted);
     LB::Sums z;
     z.clear();
-    // the records of the next trip are asked for before this trip's arithmetic: the wait for them sits behind it
-    int i = first + lane;
-    double2 ra = double2{0.0, 0.0}, rb = ra;
-    if (i < end) {
-        ra = rec[2 * (int64_t)i];
-        rb = rec[2 * (int64_t)i + 1];
-    }
-    while (i < end) {
-        const int in = i + kWave;
-        double2 na = ra, nb = rb;
-        if (in < end) {
-            na = rec[2 * (int64_t)in];
-            nb = rec[2 * (int64_t)in + 1];
+    if constexpr (!RECORDS) {
+        const double2* __restrict__ rec = reinterpret_cast<const double2*>(q.sorted);
+        // the records of the next trip are asked for before this trip's arithmetic: the wait for them sits behind it
+        int i = first + lane;
+        double2 ra = double2{0.0, 0.0}, rb = ra;
+        if (i < end) {
+            ra = rec[2 * (int64_t)i];
+            rb = rec[2 * (int64_t)i + 1];
         }
-        const double pk[4] = {ra.x, ra.y, rb.x, rb.y};
-        LB::add_draw(tb, pk, z);
-        ra = na;
-        rb = nb;
-        i = in;
+        while (i < end) {
+            const int in = i + kWave;
+            double2 na = ra, nb = rb;
+            if (in < end) {
+                na = rec[2 * (int64_t)in];
+                nb = rec[2 * (int64_t)in + 1];
+            }
+            const double pk[4] = {ra.x, ra.y, rb.x, rb.y};
+            LB::add_draw(tb, pk, z);
+            ra = na;
+            rb = nb;
+            i = in;
+        }
+    } else {
+        // the same draws in the same order, lane by lane, the next trip's pieces asked for before this trip's arithmetic
+        const double bbar = *r.bbar;
+        const double* __restrict__ rec = r.rec;
+        const double* __restrict__ rsw = r.sw;
+        constexpr int64_t R = BinKeepLayout::kRecord;
+        int i = first + lane;
+        double tau0 = 0.0, amp = 0.0, b = 0.0, sw = 0.0;
+        if (i < end) {
+            tau0 = rec[R * i];
+            amp = rec[R * i + 1];
+            b = rec[R * i + 2];
+            sw = rsw[i];
+        }
+        while (i < end) {
+            const int in = i + kWave;
+            double ntau0 = tau0, namp = amp, nb = b, nsw = sw;
+            if (in < end) {
+                ntau0 = rec[R * in];
+                namp = rec[R * in + 1];
+                nb = rec[R * in + 2];
+                nsw = rsw[in];
+            }
+            double pk[4];
+            bin_pk(tau0, amp, b, bbar, sw, pk);
+            LB::add_draw(tb, pk, z);
+            tau0 = ntau0;
+            amp = namp;
+            b = nb;
+            sw = nsw;
+            i = in;
+        }
     }
     // the 64 lanes' sums of coefficient j (M1_k at k, M2_k at kOrder + k, M3_k at 2 kOrder + k, c1, c2), each through
     // the tree (l, l ^ 32), then ^ 16, ... ^ 1 of a butterfly, of which a lane keeps only the half it will store
@@ -713,6 +882,7 @@ void bin_eval_kernel(SweepArgs a, BinSweepPtrs q, unsigned seq, BinFinish f) {
 struct BinForm {
     bool on = false;
     BinSweepPtrs q{};              // (q.ran: bin_eval_kernel's marker; q.reuse: OBE_SWEEP_BINS_KEPT honoured)
+    BinRecords r{};                // (r.rec: the keep buffer has the records form)
 
     // OBE_SWEEP_BINS is honoured where the cell form would be, for clouds whose positions fit an int
     static bool selected(const obe_model& m, int flags, int64_t ns, const int64_t* d_draw_idx, int64_t n_draws,
@@ -750,12 +920,26 @@ struct BinForm {
             memcpy(&q.keep_dbits, &m.consts[0], sizeof q.keep_dbits);
             q.call = ++calls;
             if (q.call == 0u) q.call = ++calls;
+            // ... and large enough for the records form too: the draws' records live there, not in `sorted`
+            if (keep_bytes >= BinKeepLayout::records_bytes(nd)) {
+                char* bytes = static_cast<char*>(d_keep);
+                r.rec = reinterpret_cast<double*>(bytes + BinKeepLayout::records_at(nd));
+                r.sw = reinterpret_cast<double*>(bytes + BinKeepLayout::sw_at(nd));
+            }
         }
     }
     // in place of the pack.  A rebuild of the grouping packs every draw straight to its sorted position, as part of
-    // the sweep; a reuse of a kept one does so here: bin_scatter_pack_kernel puts the records where the buffer says
+    // the sweep; a reuse of a kept one does so here: bin_scatter_pack_kernel puts the records where the buffer says,
+    // or, where the buffer holds the records themselves, bin_refresh_kernel renews their sqrt(w)
     int before(const SweepArgs& a, hipStream_t st) const {
         if (!q.reuse) return 0;
+        if (r.rec) {
+            // (a workgroup's run of draws: those of its four wavefronts in the grouping passes)
+            const int64_t per = plan_bin_units(a.nd).per * (kBlock / kWave);
+            bin_refresh_kernel<<<(unsigned)((a.nd + per - 1) / per), kBlock, 0, st>>>(a, q, r, per);
+            OBE_CHECK_LAUNCH("bin_refresh_kernel");
+            return 0;
+        }
         bin_scatter_pack_kernel<<<stream_blocks(a.nd, kBlock), kBlock, 0, st>>>(a, q);
         OBE_CHECK_LAUNCH("bin_scatter_pack_kernel");
         return 0;
@@ -771,15 +955,24 @@ struct BinForm {
             bin_minmax_kernel<<<mm_blocks, kBlock, 0, st>>>(a, q);
             OBE_CHECK_LAUNCH("bin_minmax_kernel");
             const unsigned group_blocks = (unsigned)((units.nunits + kBlock / kWave - 1) / (kBlock / kWave));
-            bin_group_kernel<false><<<group_blocks, kBlock, 0, st>>>(a, units.per, units.nunits, mm_blocks, q);
+            bin_group_kernel<false><<<group_blocks, kBlock, 0, st>>>(a, units.per, units.nunits, mm_blocks, q, r);
             OBE_CHECK_LAUNCH("bin_group_kernel<count>");
             bin_scan_kernel<<<LB::kMaxBins, kBlock, 0, st>>>(units.nunits, q, a.abort);
             OBE_CHECK_LAUNCH("bin_scan_kernel");
-            bin_group_kernel<true><<<group_blocks, kBlock, 0, st>>>(a, units.per, units.nunits, mm_blocks, q);
+            if (r.rec)
+                bin_group_kernel<true, true><<<group_blocks, kBlock, 0, st>>>(a, units.per, units.nunits, mm_blocks, q, r);
+            else
+                bin_group_kernel<true><<<group_blocks, kBlock, 0, st>>>(a, units.per, units.nunits, mm_blocks, q, r);
             OBE_CHECK_LAUNCH("bin_group_kernel<scatter>");
         }
         // (one wavefront per item: at least as many as any cloud makes)
-        bin_moments_kernel<<<(unsigned)bin_max_items(a.nd), kWave, 0, st>>>(q, a.abort);
+        if (r.rec) {
+            BinRecords rr = r;
+            rr.bbar = a.moments + 4;          // (Lorentz<1>::pack's thbar[K + 1] of thbar = d_moments + 2)
+            bin_moments_kernel<true><<<(unsigned)bin_max_items(a.nd), kWave, 0, st>>>(q, a.abort, rr);
+        } else {
+            bin_moments_kernel<false><<<(unsigned)bin_max_items(a.nd), kWave, 0, st>>>(q, a.abort, r);
+        }
         OBE_CHECK_LAUNCH("bin_moments_kernel");
         bin_fold_kernel<<<2 * LB::kMaxBins, kBinFoldGroups * kWave, 0, st>>>(q, a.abort);
         OBE_CHECK_LAUNCH("bin_fold_kernel");

@@ -151,7 +151,8 @@ class OptBayesExpt(ParticlePDF):
     ``tuning_parameters['sweep_shift']`` (``'auto'``, ``'always'``, ``'never'``), ``['sweep_cells']`` (``'auto'``,
     ``'always'``, ``'never'``: the one-peak Lorentzian's unshifted sweep by cell expansions), ``['sweep_bins']`` (the
     same values: that sweep by bin expansions of the particles), ``['sweep_bins_keep']`` (default True: the bins'
-    grouping of the cloud is kept from sweep to sweep until the particles change), ``['fused_moments']``,
+    grouping of the cloud and its sorted records are kept from sweep to sweep until the particles change;
+    ``'grouping'``: the grouping alone, 32 bytes per particle less; False: neither), ``['fused_moments']``,
     ``['replica_check_every']``
         see ``_sweep_device``, ``pdf_update``, ``check_replicas``.
     """
@@ -1294,11 +1295,16 @@ class OptBayesExpt(ParticlePDF):
 
     def _bins_keep_buffer(self):
         """This object's keep buffer (one per rank of a sharded object; a copy or a restored object starts without
-        one and rebuilds on its first sweep)."""
+        one and rebuilds on its first sweep).  ``tuning_parameters['sweep_bins_keep']``: True (default) - the
+        records form (include/obe_hip.h: obe_sweep_bins_keep_records_bytes; 32 bytes per particle more: a sweep of
+        the same particles renews only the square roots of the weights); ``'grouping'`` - the grouping alone, and
+        every reusing sweep reads and checks every particle; False - no buffer is passed at all."""
         keep = self.__dict__.get("_bins_keep")
-        if keep is None or keep[0] != self.n_particles:
-            nbytes = int(self._mlib.cdll.obe_sweep_bins_keep_bytes(self.n_particles))
-            keep = self._bins_keep = (self.n_particles,
+        size = ("obe_sweep_bins_keep_bytes" if self.tuning_parameters.get("sweep_bins_keep", True) == "grouping"
+                else "obe_sweep_bins_keep_records_bytes")
+        if keep is None or keep[0] != (self.n_particles, size):
+            nbytes = int(getattr(self._mlib.cdll, size)(self.n_particles))
+            keep = self._bins_keep = ((self.n_particles, size),
                                       torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self._device))
             self._sweeps.keep_buffer_replaced()
         return keep[1]

@@ -17,7 +17,7 @@ import numpy as np
 
 CYCLES = 20
 GROUPING = ("sweep_pack_kernel", "bin_minmax_kernel", "bin_plan_kernel", "bin_group_kernel", "bin_scan_kernel",
-            "bin_scatter_pack_kernel", "sweep_finalize")
+            "bin_scatter_pack_kernel", "bin_refresh_kernel", "sweep_finalize")
 
 
 def short(name):

@@ -5,8 +5,8 @@ Compile the parent's and the candidate's source as tools/count_isa.py's docstrin
 
     python tools/compare_isa.py parent.s candidate.s
 
-prints whether both hold the same kernels, how many are identical line for line (local labels, which carry the
-function's position in the file, are made anonymous first), and for every kernel that differs its registers, scratch,
+prints whether both hold the same kernels, how many are identical line for line (local labels and the loop comments that name them, which carry
+the function's position in the file, are made anonymous first), and for every kernel that differs its registers, scratch,
 LDS and instruction count on both sides; then the instantiations and instruction lines per kernel name."""
 import re
 import subprocess
@@ -18,7 +18,7 @@ STATS = r"; (NumSgprs|NumVgprs|NumAgprs|ScratchSize|LDSByteSize|Occupancy|SGPRSp
 def kernels(path):
     text = open(path).read()
     for pattern, anonymous in ((r"\.LBB\d+_", ".LBB_"), (r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1"), (r"\.LJTI\d+_", ".LJTI_"),
-                               (r"\.Ltmp\d+", ".Ltmp")):
+                               (r"\.Ltmp\d+", ".Ltmp"), (r"(Header=|Loop )BB\d+_", r"\1BB_")):
         text = re.sub(pattern, anonymous, text)
     lines = text.split("\n")
     start = {l.split(":")[0]: i for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l)}

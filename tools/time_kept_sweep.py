@@ -1,6 +1,9 @@
 """The whole obe_sweep_utility_keep call on a prior cloud, rebuilding into the keep buffer and reusing it (developer
-aid; the table of profiles/kept_bins.txt and profiles/bin_waves.txt).  Every call starts on a drained stream and ends
-with the wait for its result; host clock, median of CALLS calls, three rounds in one process, microseconds.
+aid; the table of profiles/kept_bins.txt, profiles/bin_waves.txt and profiles/keep_records.txt).  Every call starts on a
+drained stream and ends with the wait for its result; host clock, median of CALLS calls, three rounds in one process,
+microseconds.  Two clouds per shape: the prior (uniform x0: 41 bins), and the prior after one measurement and one
+resample, as a cycle's rebuild finds it.  The keep buffer has the records form where the library knows it
+(obe_sweep_bins_keep_records_bytes), so the same file times a checkout from before it.
 
     python tools/time_kept_sweep.py [NSxN ...]          # default: the four shapes of the profiles
 
@@ -25,13 +28,19 @@ if os.environ.get("OBE_VARIANT"):      # a library built by tools/build_variant.
 
 CALLS = 200
 SHAPES = [(64, 64), (4096, 262144), (65536, 262144), (65536, 1048576)]
+if os.environ.get("OBE_KEPT_SWEEP_CALLS"):
+    CALLS = int(os.environ["OBE_KEPT_SWEEP_CALLS"])
 
 
-def caller(ns, n):
+def caller(ns, n, resampled=False):
     g = np.random.default_rng(5)
     cloud = np.array([g.uniform(2, 4, n), g.uniform(-2000, -400, n), g.normal(50000, 1000, n)])
     o = obe.OptBayesExpt(obe.models.lorentzian(1), (np.linspace(1.5, 4.5, ns),), cloud, (0.1,),
                          utility_method="variance_full", auto_resample=False, default_noise_std=500.0)
+    if resampled:
+        o.rng = np.random.default_rng(6)
+        o.pdf_update(((3.0,), 49500.0, 500.0))
+        o.resample()
     p, w = o._pw_tensors()
     mom = o._moments_on_device()
     dev = w.device
@@ -40,7 +49,8 @@ def caller(ns, n):
     util = torch.zeros(ns, dtype=torch.float64, device=dev)
     out = _lib.pinned_array(4)
     best, idx, kappa = out[0:1], out.view(np.int64)[1:2], out[2:3]
-    keep = torch.zeros(int(o._mlib.cdll.obe_sweep_bins_keep_bytes(n)) // 4, dtype=torch.int32, device=dev)
+    size = getattr(o._mlib.cdll, "obe_sweep_bins_keep_records_bytes", o._mlib.cdll.obe_sweep_bins_keep_bytes)
+    keep = torch.zeros(int(size(n)) // 4, dtype=torch.int32, device=dev)
     hp = _lib.host_ptr
 
     def call(flags):
@@ -65,14 +75,16 @@ def median_us(call, flags):
 def main(shapes):
     print(f"{'shape':>20}  rebuild {'':>22}|   reuse      (waves per group of settings)")
     for ns, n in shapes:
-        o, call = caller(ns, n)
-        for _ in range(20):
-            call(_lib.OBE_SWEEP_BINS)
-        rebuild = [median_us(call, _lib.OBE_SWEEP_BINS) for _ in range(3)]
-        reuse = [median_us(call, _lib.OBE_SWEEP_BINS | _lib.OBE_SWEEP_BINS_KEPT) for _ in range(3)]
-        waves = getattr(o._mlib.cdll, "obe_sweep_bins_eval_waves", lambda n_settings: 1)(ns)
-        print(f"{ns:>8} x {n:>9}  " + " ".join(f"{t:8.2f}" for t in rebuild) + "   |  "
-              + " ".join(f"{t:8.2f}" for t in reuse) + f"      ({waves})", flush=True)
+        for resampled in (False, True):
+            o, call = caller(ns, n, resampled)
+            for _ in range(20):
+                call(_lib.OBE_SWEEP_BINS)
+            rebuild = [median_us(call, _lib.OBE_SWEEP_BINS) for _ in range(3)]
+            reuse = [median_us(call, _lib.OBE_SWEEP_BINS | _lib.OBE_SWEEP_BINS_KEPT) for _ in range(3)]
+            waves = getattr(o._mlib.cdll, "obe_sweep_bins_eval_waves", lambda n_settings: 1)(ns)
+            print(f"{ns:>8} x {n:>9}  " + " ".join(f"{t:8.2f}" for t in rebuild) + "   |  "
+                  + " ".join(f"{t:8.2f}" for t in reuse) + f"      ({waves})"
+                  + ("  resampled" if resampled else "  prior"), flush=True)
 
 
 if __name__ == "__main__":
