@@ -10,7 +10,8 @@ Python model function into the HIP kernels (models.from_function); without it th
 host-callable model.  The names are those the reference exports (optbayesexpt/__init__.py:1-6)
 without the TCP server and socket, which are outside this package's scope.
 """
-from optbayesexpt_amd import (MeasurementSimulator, OptBayesExpt, OptBayesExptNoiseParameter,      # noqa: F401
-                              OptBayesExptSignalNoise, OptBayesExptSweeper, ParticlePDF, models, obe_base,
-                              obe_noiseparam, obe_signalnoise, obe_utils, particlepdf, trace_sort)
+from optbayesexpt_amd import (MeasurementSimulator, OptBayesExpt, OptBayesExptBinomial,            # noqa: F401
+                              OptBayesExptNoiseParameter, OptBayesExptSignalNoise, OptBayesExptSweeper, ParticlePDF,
+                              models, obe_base, obe_binomial, obe_noiseparam, obe_signalnoise, obe_utils, particlepdf,
+                              trace_sort)
 from optbayesexpt_amd import __version__                                                            # noqa: F401

@@ -1066,6 +1066,44 @@ OBE_API int obe_signal_noise_variance(const obe_model* m, const double* d_settin
                               const double* h_noise_coef, double* d_noise_var, void* d_ws, int64_t ws_bytes,
                               void* stream);
 
+/* ---- yes/no outcomes: binomial likelihood and information-gain design (extension) ----
+ * Every likelihood above is Gaussian.  Here the model's channel c gives a success probability p_c = f_c(x; theta) and a
+ * record holds k_c successes in n_c shots per channel (a click or no click; k clicks in n shots).  Models of at most
+ * OBE_BINOMIAL_MAX_CHANNELS channels (else -1 before any launch).  p_c,i = what obe_eval_over_particles writes, bit for
+ * bit.  All results land in the caller's DEVICE buffers, nothing is waited for.
+ * d_lik (n_particles,): what obe_bayes_update_lik multiplies the weights by,
+ *   L_i = exp(sum_{c < n_lik_channels} [k_c log p_c,i + (n_c - k_c) log1p(-p_c,i)])
+ * with k_c = h_successes[c], n_c = h_shots[c] (n_lik_channels values each: finite, integer-valued, 0 <= k_c <= n_c,
+ * n_c >= 1, else -1), a term whose count is 0 skipped (p = 0 with k = 0 contributes the factor 1), then L^choke unless
+ * choke is NaN.  No binomial coefficient: it is the same for every particle.  A particle with any p_c — of all the
+ * model's channels — that is NaN or outside [0, 1] gets L = 0.  d_y, d_particles, h_setting: as
+ * obe_signal_noise_likelihood takes them, but h_setting == NULL with d_y == NULL is -1 here (no setting to evaluate the
+ * model at); both forms give the same bits.  Lane <-> particle, one stream over the cloud. */
+#define OBE_BINOMIAL_MAX_CHANNELS 3
+OBE_API int obe_binomial_likelihood(const obe_model* m, const double* d_y, int64_t ld_y, const double* d_particles,
+                            int64_t ld_p, int64_t n_particles, const double* h_setting, const double* h_successes,
+                            const double* h_shots, int32_t n_lik_channels, double choke, double* d_lik, void* stream);
+/* d_information (n_settings,): the exact mutual information, in nats, between theta and the joint outcome
+ * o in {0 .. 2^C - 1} of ONE shot in every channel (independent given theta, not marginally: enumerated), per unit cost,
+ *   Pbar_o = sum_i w_i prod_c (bit c of o ? p_c,i : 1 - p_c,i) / W
+ *   hbar   = sum_i w_i sum_c h2(p_c,i) / W,   h2(p) = -p log p - (1 - p) log1p(-p),  0 log 0 = 0
+ *   U      = max(-sum_o Pbar_o log Pbar_o - hbar, 0) / cost       (the clamp covers rounding; NaN stays NaN)
+ * d_noise_var (C, n_settings) = sum_i w_i p_c,i (1 - p_c,i) / W / shots: the variance of the fraction k / n of `shots`
+ * (finite, >= 1) shots, the noise variance a Gaussian utility divides by (obe_sweep_utility's d_noise_var with
+ * noise_ld = n_settings).  Either output may be NULL, not both; what is written has the same bits whichever other output
+ * is asked for.  W sums the contributing particles only: NaN and negative weights count as zero, a particle of zero
+ * weight contributes nothing whatever its p is, and neither does, at a setting, a particle with a p_c there that is NaN or
+ * outside [0, 1]; W == 0 gives NaN.  cost = cost if d_cost == NULL else d_cost[s] (obe_utility_argmax's convention).
+ * d_settings, the geometry, the chunk partials folded in chunk order (no atomics: the same bits from run to run, and for
+ * a slice the bits of those columns of the whole grid's call while the cloud decides the number of chunks) and d_ws:
+ * as obe_signal_noise_variance, with 2^C + C + 2 sums per lane and obe_binomial_workspace_bytes(n_particles, n_settings,
+ * the model's channels) bytes; the size does not depend on n_particles and does not shrink when an argument grows. */
+OBE_API int64_t obe_binomial_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels);
+OBE_API int obe_binomial_information(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                             const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                             double shots, const double* d_cost, double cost, double* d_information,
+                             double* d_noise_var, void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

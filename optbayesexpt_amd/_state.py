@@ -51,16 +51,22 @@ LIBRARY_ATTRIBUTES = frozenset((
     "cost_of_new_sweep", "last_sweep_batches",
 ))
 
-_SELECTION = {"opt_setting": "optimal", "good_setting": "good", "random_setting": "random"}
+#: ... and what an OptBayesExptBinomial sets besides: the library's own on an object of that class only (``shots`` is a
+#: likely name for an attribute of the user's own on any other class, where it travels as it always did)
+BINOMIAL_ATTRIBUTES = frozenset(("shots",))
+
+_SELECTION ={"opt_setting": "optimal", "good_setting": "good", "random_setting": "random"}
 
 
 def _library_classes():
     from .obe_base import OptBayesExpt
+    from .obe_binomial import OptBayesExptBinomial
     from .obe_noiseparam import OptBayesExptNoiseParameter
     from .obe_signalnoise import OptBayesExptSignalNoise
     from .particlepdf import ParticlePDF
     from .sweeper import OptBayesExptSweeper
-    return OptBayesExptSweeper, OptBayesExptNoiseParameter, OptBayesExptSignalNoise, OptBayesExpt, ParticlePDF
+    return (OptBayesExptSweeper, OptBayesExptNoiseParameter, OptBayesExptSignalNoise, OptBayesExptBinomial, OptBayesExpt,
+            ParticlePDF)
 
 
 def library_class(cls):
@@ -140,6 +146,7 @@ def snapshot(obj, on_device=False):
     arguments and the user's own attributes are the object's own (``pickle`` and ``copy.deepcopy`` copy them).
     ``on_device``: the cloud, the weights and the moment block as device-side clones instead of host arrays
     (``copy.deepcopy``)."""
+    from . import obe_binomial
     from .obe_base import OptBayesExpt
     from .obe_noiseparam import OptBayesExptNoiseParameter
     from .obe_signalnoise import OptBayesExptSignalNoise, state_fields
@@ -192,13 +199,23 @@ def snapshot(obj, on_device=False):
         st["constraint_count"] = obj.last_constraint_count
     if isinstance(obj, OptBayesExptSignalNoise):
         st["signal_noise"] = state_fields(obj)
+    if isinstance(obj, obe_binomial.OptBayesExptBinomial):
+        st["binomial"] = obe_binomial.state_fields(obj)
     if isinstance(obj, OptBayesExptSweeper):
         st["sweeper"] = {k: getattr(obj, k) for k in ("sweep_settings", "start_stop_subsample", "start_stop_indices",
                                                       "start_stop_choice_indices", "start_stop_values",
                                                       "cost_of_new_sweep")}
         st["sweeper"]["last_sweep_batches"] = list(obj.__dict__.get("last_sweep_batches", []))
-    st["user"] = {k: v for k, v in obj.__dict__.items() if not k.startswith("_") and k not in LIBRARY_ATTRIBUTES}
+    st["user"] = user_attributes(obj)
     return st
+
+
+def user_attributes(obj):
+    """The public names in ``obj.__dict__`` that the library did not set on an object of this class: the user's own,
+    which travel with the snapshot as they are."""
+    from .obe_binomial import OptBayesExptBinomial
+    own = LIBRARY_ATTRIBUTES | BINOMIAL_ATTRIBUTES if isinstance(obj, OptBayesExptBinomial) else LIBRARY_ATTRIBUTES
+    return {k: v for k, v in obj.__dict__.items() if not k.startswith("_") and k not in own}
 
 
 # ---------------------------------------------------------------------------------------------- restore
@@ -222,6 +239,7 @@ def restore(state, device=None, settings_shard=None, into=None):
     constructor on the saved arguments, then the saved state.  ``device``: where (default: the current torch
     device); ``settings_shard``: a :class:`~optbayesexpt_amd.dist.SettingsShard` of the world it becomes part of
     (collective: every rank restores the same state)."""
+    from . import obe_binomial
     from .obe_base import OptBayesExpt
     from .obe_noiseparam import OptBayesExptNoiseParameter
     from .obe_signalnoise import OptBayesExptSignalNoise, kwargs_from_state
@@ -257,6 +275,8 @@ def restore(state, device=None, settings_shard=None, into=None):
             base.__init__(obj, *args, noise_parameter_index=state["noise_parameter_index"], **kw)
         elif base is OptBayesExptSignalNoise:
             base.__init__(obj, *args, **kwargs_from_state(state["signal_noise"]), **kw)
+        elif base is obe_binomial.OptBayesExptBinomial:
+            base.__init__(obj, *args, **obe_binomial.kwargs_from_state(state["binomial"]), **kw)
         else:
             base.__init__(obj, *args, **kw)
     dev = obj._device
