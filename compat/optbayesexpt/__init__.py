@@ -11,7 +11,7 @@ host-callable model.  The names are those the reference exports (optbayesexpt/__
 without the TCP server and socket, which are outside this package's scope.
 """
 from optbayesexpt_amd import (MeasurementSimulator, OptBayesExpt, OptBayesExptBinomial,            # noqa: F401
-                              OptBayesExptNoiseParameter, OptBayesExptSignalNoise, OptBayesExptSweeper, ParticlePDF,
-                              models, obe_base, obe_binomial, obe_noiseparam, obe_signalnoise, obe_utils, particlepdf,
-                              trace_sort)
+                              OptBayesExptNoiseParameter, OptBayesExptPoisson, OptBayesExptSignalNoise,
+                              OptBayesExptSweeper, ParticlePDF, models, obe_base, obe_binomial, obe_noiseparam,
+                              obe_poisson, obe_signalnoise, obe_utils, particlepdf, trace_sort)
 from optbayesexpt_amd import __version__                                                            # noqa: F401

@@ -1104,6 +1104,60 @@ OBE_API int obe_binomial_information(const obe_model* m, const double* d_setting
                              double shots, const double* d_cost, double cost, double* d_information,
                              double* d_noise_var, void* d_ws, int64_t ws_bytes, void* stream);
 
+/* ---- counted events: Poisson likelihood and exact information design (extension) ----
+ * The model's channel c gives a RATE r_c = f_c(x; theta) in counts per unit exposure; a record holds k_c counted events
+ * (whole numbers >= 0) in the exposure t_c (finite, > 0) per channel, lambda_c,i = t_c r_c,i.  r_c,i = what
+ * obe_eval_over_particles writes, bit for bit.  All results land in the caller's DEVICE buffers, nothing is waited for.
+ * d_lik (n_particles,): what obe_bayes_update_lik multiplies the weights by,
+ *   L_i = exp(sum_{c < n_lik_channels} [k_c log lambda_c,i - lambda_c,i - log k_c!])
+ * with k_c = h_counts[c], t_c = h_exposure[c], log k_c! = h_logfact[c] (the host's lgamma(k_c + 1); n_lik_channels values
+ * each, n_lik_channels in 0..the model's channels; a count that is not a whole number >= 0 or an exposure that is not
+ * finite and > 0 is -1), then L^choke unless choke is NaN.  log k! is kept although it is the same for every particle:
+ * every exponent is then <= 0 and L is the Poisson pmf itself (k = lambda = 1000 would otherwise ask for exp(5908)).  A
+ * channel with k_c = 0 contributes -lambda alone, no log: lambda = 0 with k = 0 is the factor 1, lambda = 0 with k > 0
+ * gives L = 0.  A particle with any r_c — of all the model's channels — that is NaN, negative or +inf (or whose t_c r_c
+ * overflows) gets L = 0.  d_y, d_particles, h_setting: as obe_binomial_likelihood takes them; both forms give the same
+ * bits.  Lane <-> particle, one stream over the cloud.
+ *
+ * obe_poisson_information, models of ONE channel: the exact mutual information, in nats, between theta and the next
+ * reading's count CENSORED at cap, outcomes {0, 1, .., cap - 1, ">= cap"}, per unit cost.  With lambda_i = exposure r_i,
+ *   p_k,i  = Pois(k; lambda_i) for k < cap,   tau_i = max(1 - sum_{k < cap} p_k,i, 0)
+ *   Pbar_k = sum_i w_i p_k,i / W,             taubar = sum_i w_i tau_i / W
+ *   h_i    = -sum_{k < cap} p_k,i (k log lambda_i - lambda_i - log k!) - tau_i log tau_i
+ *            (log lambda reads as 0 at lambda = 0; 0 log 0 = 0)
+ *   U      = max(-sum_k Pbar_k log Pbar_k - taubar log taubar - sum_i w_i h_i / W, 0) / cost
+ * (the clamp covers rounding; NaN stays NaN).  Exact for the censored reading; by data processing a lower bound of the
+ * uncensored reading's information, tight when taubar is small: taubar is an output, so that a cap too small for the
+ * rates shows.  cap is 16, 32 or 64 (OBE_POISSON_MAX_CAP; compile-time sizes: the outcome sums stay in registers), else
+ * -1.  The kernel forms p_0 = exp(-lambda), p_k = p_k-1 (lambda (1 / k)) and, since k p_k = lambda p_k-1, the sum in h_i
+ * as log lambda . lambda sum_{k < cap - 1} p_k - lambda sum_k p_k - sum_k p_k log k!: one exp and two log per evaluation.
+ * (Beyond lambda ~ 708, where exp(-lambda) is subnormal, the p_k — all below 1e-200 — lose relative accuracy; tau = 1.)
+ *   d_information (n_settings,) = U;  d_tail (n_settings,) = taubar;
+ *   d_pmf (cap + 1, n_settings): the rows Pbar_0 .. Pbar_cap-1, then taubar — the predicted histogram of the next reading;
+ *   d_noise_var (C, n_settings) = sum_i w_i r_c,i / W / exposure: the variance of the reading k / t in the model's units,
+ *     the noise variance a Gaussian utility divides by (obe_sweep_utility's d_noise_var with noise_ld = n_settings).
+ * Any output may be NULL, not all of them; what is written has the same bits whichever other outputs are asked for.
+ * d_information, d_tail or d_pmf with a model of more than one channel is -1; d_noise_var alone works for every channel
+ * count (an instantiation that carries no outcome sums).  W sums the contributing particles only: NaN and negative
+ * weights count as zero, a particle of zero weight contributes nothing whatever its rate is, and neither does, at a
+ * setting, a particle with an r_c there that is not a rate (NaN, negative, +inf, or exposure r_c overflows); W == 0 gives
+ * NaN.  cost = cost if d_cost == NULL else d_cost[s] (obe_utility_argmax's convention).  d_settings, the geometry, the
+ * chunk partials folded in chunk order (no atomics: the same bits from run to run, and for a slice the bits of those
+ * columns of the whole grid's call while the cloud decides the number of chunks) and d_ws: as obe_binomial_information,
+ * with cap + C + 3 sums per lane and obe_poisson_workspace_bytes(n_particles, n_settings, the model's channels, cap)
+ * bytes; the size does not depend on n_particles and does not shrink when an argument grows. */
+#define OBE_POISSON_MAX_CAP 64
+OBE_API int obe_poisson_likelihood(const obe_model* m, const double* d_y, int64_t ld_y, const double* d_particles,
+                           int64_t ld_p, int64_t n_particles, const double* h_setting, const double* h_counts,
+                           const double* h_exposure, const double* h_logfact, int32_t n_lik_channels, double choke,
+                           double* d_lik, void* stream);
+OBE_API int64_t obe_poisson_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels, int32_t cap);
+OBE_API int obe_poisson_information(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                            const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                            double exposure, int32_t cap, const double* d_cost, double cost, double* d_information,
+                            double* d_tail, double* d_pmf, double* d_noise_var, void* d_ws, int64_t ws_bytes,
+                            void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

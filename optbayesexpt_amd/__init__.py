@@ -18,6 +18,7 @@ from .obe_base import OptBayesExpt                          # noqa: F401
 from .obe_noiseparam import OptBayesExptNoiseParameter      # noqa: F401
 from .obe_signalnoise import OptBayesExptSignalNoise        # noqa: F401
 from .obe_binomial import OptBayesExptBinomial              # noqa: F401
+from .obe_poisson import OptBayesExptPoisson                # noqa: F401
 from .sweeper import OptBayesExptSweeper                    # noqa: F401
 from .obe_utils import MeasurementSimulator, trace_sort     # noqa: F401
 from .dist import SettingsShard                             # noqa: F401

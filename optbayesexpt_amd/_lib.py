@@ -32,6 +32,7 @@ OBE_MAX_DIMS = _H["OBE_MAX_DIMS"]
 OBE_FAST_DIMS = _H["OBE_FAST_DIMS"]                  # cloud kernels compiled for the exact row count up to here
 OBE_CLOUD_MAX_DIMS = _H["OBE_CLOUD_MAX_DIMS"]        # what the tiled cloud kernels take (ParticlePDF alone)
 OBE_BINOMIAL_MAX_CHANNELS = _H["OBE_BINOMIAL_MAX_CHANNELS"]      # channels of a model of yes/no outcomes
+OBE_POISSON_MAX_CAP = _H["OBE_POISSON_MAX_CAP"]      # the largest censoring count of a counted reading's information
 OBE_WS_RESULT_OFFSET = _H["OBE_WS_RESULT_OFFSET"]    # doubles
 # bits of obe_sweep_utility's `shifted` argument
 OBE_SWEEP_SHIFTED, OBE_SWEEP_SAFE = _H["OBE_SWEEP_SHIFTED"], _H["OBE_SWEEP_SAFE"]
@@ -145,7 +146,8 @@ MODEL_ENTRY_POINTS = ("obe_model_validate", "obe_workspace_bytes", "obe_sweep_se
                       "obe_records_loglik_workspace_bytes", "obe_records_loglik",
                       "obe_output_cross_covariance_workspace_bytes", "obe_output_cross_covariance",
                       "obe_signal_noise_likelihood", "obe_signal_noise_workspace_bytes", "obe_signal_noise_variance",
-                      "obe_binomial_likelihood", "obe_binomial_workspace_bytes", "obe_binomial_information")
+                      "obe_binomial_likelihood", "obe_binomial_workspace_bytes", "obe_binomial_information",
+                      "obe_poisson_likelihood", "obe_poisson_workspace_bytes", "obe_poisson_information")
 
 
 class HipLib:

@@ -54,6 +54,8 @@ LIBRARY_ATTRIBUTES = frozenset((
 #: ... and what an OptBayesExptBinomial sets besides: the library's own on an object of that class only (``shots`` is a
 #: likely name for an attribute of the user's own on any other class, where it travels as it always did)
 BINOMIAL_ATTRIBUTES = frozenset(("shots",))
+#: ... and an OptBayesExptPoisson, in the same way
+POISSON_ATTRIBUTES = frozenset(("exposure", "count_cap", "last_information"))
 
 _SELECTION ={"opt_setting": "optimal", "good_setting": "good", "random_setting": "random"}
 
@@ -62,11 +64,12 @@ def _library_classes():
     from .obe_base import OptBayesExpt
     from .obe_binomial import OptBayesExptBinomial
     from .obe_noiseparam import OptBayesExptNoiseParameter
+    from .obe_poisson import OptBayesExptPoisson
     from .obe_signalnoise import OptBayesExptSignalNoise
     from .particlepdf import ParticlePDF
     from .sweeper import OptBayesExptSweeper
-    return (OptBayesExptSweeper, OptBayesExptNoiseParameter, OptBayesExptSignalNoise, OptBayesExptBinomial, OptBayesExpt,
-            ParticlePDF)
+    return (OptBayesExptSweeper, OptBayesExptNoiseParameter, OptBayesExptSignalNoise, OptBayesExptBinomial,
+            OptBayesExptPoisson, OptBayesExpt, ParticlePDF)
 
 
 def library_class(cls):
@@ -146,7 +149,7 @@ def snapshot(obj, on_device=False):
     arguments and the user's own attributes are the object's own (``pickle`` and ``copy.deepcopy`` copy them).
     ``on_device``: the cloud, the weights and the moment block as device-side clones instead of host arrays
     (``copy.deepcopy``)."""
-    from . import obe_binomial
+    from . import obe_binomial, obe_poisson
     from .obe_base import OptBayesExpt
     from .obe_noiseparam import OptBayesExptNoiseParameter
     from .obe_signalnoise import OptBayesExptSignalNoise, state_fields
@@ -201,6 +204,8 @@ def snapshot(obj, on_device=False):
         st["signal_noise"] = state_fields(obj)
     if isinstance(obj, obe_binomial.OptBayesExptBinomial):
         st["binomial"] = obe_binomial.state_fields(obj)
+    if isinstance(obj, obe_poisson.OptBayesExptPoisson):
+        st["poisson"] = obe_poisson.state_fields(obj)
     if isinstance(obj, OptBayesExptSweeper):
         st["sweeper"] = {k: getattr(obj, k) for k in ("sweep_settings", "start_stop_subsample", "start_stop_indices",
                                                       "start_stop_choice_indices", "start_stop_values",
@@ -214,7 +219,10 @@ def user_attributes(obj):
     """The public names in ``obj.__dict__`` that the library did not set on an object of this class: the user's own,
     which travel with the snapshot as they are."""
     from .obe_binomial import OptBayesExptBinomial
+    from .obe_poisson import OptBayesExptPoisson
     own = LIBRARY_ATTRIBUTES | BINOMIAL_ATTRIBUTES if isinstance(obj, OptBayesExptBinomial) else LIBRARY_ATTRIBUTES
+    if isinstance(obj, OptBayesExptPoisson):
+        own = own | POISSON_ATTRIBUTES
     return {k: v for k, v in obj.__dict__.items() if not k.startswith("_") and k not in own}
 
 
@@ -239,7 +247,7 @@ def restore(state, device=None, settings_shard=None, into=None):
     constructor on the saved arguments, then the saved state.  ``device``: where (default: the current torch
     device); ``settings_shard``: a :class:`~optbayesexpt_amd.dist.SettingsShard` of the world it becomes part of
     (collective: every rank restores the same state)."""
-    from . import obe_binomial
+    from . import obe_binomial, obe_poisson
     from .obe_base import OptBayesExpt
     from .obe_noiseparam import OptBayesExptNoiseParameter
     from .obe_signalnoise import OptBayesExptSignalNoise, kwargs_from_state
@@ -277,6 +285,8 @@ def restore(state, device=None, settings_shard=None, into=None):
             base.__init__(obj, *args, **kwargs_from_state(state["signal_noise"]), **kw)
         elif base is obe_binomial.OptBayesExptBinomial:
             base.__init__(obj, *args, **obe_binomial.kwargs_from_state(state["binomial"]), **kw)
+        elif base is obe_poisson.OptBayesExptPoisson:
+            base.__init__(obj, *args, **obe_poisson.kwargs_from_state(state["poisson"]), **kw)
         else:
             base.__init__(obj, *args, **kw)
     dev = obj._device

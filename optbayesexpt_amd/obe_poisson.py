@@ -1,0 +1,294 @@
+"""OptBayesExptPoisson — counted events and exact information design.
+
+A photon-counting or NV-centre experiment reads a whole number of events per reading, often a handful.  A Gaussian whose
+variance follows the signal (OptBayesExptSignalNoise) puts mass on negative counts there, and its design rule is not the
+information of a count.  Here the model's channel ``c`` gives a RATE ``r_c = f_c(x; theta)`` in counts per unit exposure
+and a record is ``(setting, k[, t])``: ``k_c`` counted events in the exposure ``t_c``, ``lambda_c = t_c r_c``:
+
+    likelihood   L_i = exp(sum_c [k_c log lambda_c,i - lambda_c,i - log k_c!])       (the Poisson pmf itself)
+    design       U(x) = I(theta; the next reading's count censored at count_cap) / cost_estimate(),
+
+the exact mutual information, in nats, of the outcomes ``{0, .., count_cap - 1, ">= count_cap"}`` (models of one channel):
+exact for the censored reading, a lower bound of the uncensored one's, tight when the tail mass is small — which
+``last_information["tail_max"]`` reports after every pass.  One settings x particles pass that never leaves the chip
+(csrc/obe_poisson.hip) gives the information, the predicted histogram of the next reading (``count_distribution()``) and
+``nu_bar_c(x) = sum w r_c / W / exposure_c``, the variance of the reading k / t, which ``yvar_noise_model()`` returns: the
+inherited variance utilities then mean the Gaussian approximation of these counts.  The argument checks are plain
+functions of this module (no device needed).
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .models import DeviceModel
+from .obe_base import OptBayesExpt, _overridden
+from .obe_signalnoise import OptBayesExptSignalNoise
+from .particlepdf import _P, _ptr
+
+MAX_CHANNELS = _lib.OBE_MAX_CHANNELS
+CAPS = (16, 32, 64)
+INFORMATION = "mutual_information"
+VARIANCE_METHODS = ("variance_approx", "variance_full", "parameter_variance", "max_min", "pseudo_utility")
+
+
+# ---------------------------------------------------------------------------------------- argument checks (host)
+def _values(name, value, n_channels):
+    try:
+        v = np.asarray(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number or {n_channels} numbers") from None
+    if v.ndim > 1 or v.size == 0:
+        raise ValueError(f"{name} must be a scalar or one value per channel, got shape {v.shape}")
+    return v
+
+
+def check_cap(count_cap):
+    """The censoring count of the information, or ``ValueError``: 16, 32 or 64 (compile-time sizes of the kernel)."""
+    if isinstance(count_cap, (bool, np.bool_)) or count_cap not in CAPS or int(count_cap) != count_cap:
+        raise ValueError(f"count_cap must be one of {CAPS} (OBE_POISSON_MAX_CAP = {_lib.OBE_POISSON_MAX_CAP}), "
+                         f"got {count_cap!r}")
+    return int(count_cap)
+
+
+def check_exposure(exposure, n_channels):
+    """``(C,)`` float64 exposure per channel from a scalar or ``(C,)``: finite and > 0."""
+    v = _values("exposure", exposure, n_channels)
+    if v.ndim == 1 and v.size != n_channels:
+        raise ValueError(f"exposure must be a scalar or have one value per channel ({n_channels}), got shape {v.shape}")
+    if not np.all(np.isfinite(v)) or np.any(v <= 0):
+        raise ValueError("exposure must be finite and > 0")
+    return np.array(np.broadcast_to(v, (n_channels,)))
+
+
+def check_record_counts(counts, exposure, n_channels):
+    """``(n_lik, k, t, log k!)`` of a record: the channels that enter the likelihood (the reference's truncation of a
+    record to the shorter of its values and the model's channels), their counted events, exposures and
+    ``lgamma(k + 1)``, float64 arrays of ``MAX_CHANNELS``.  ``counts``: a scalar or one value per channel, whole
+    numbers >= 0; ``exposure``: a scalar (for every channel) or one value per channel, finite and > 0."""
+    k = np.atleast_1d(_values("the counts of a record", counts, n_channels))
+    t = _values("the exposure of a record", exposure, n_channels)
+    n_lik = min(n_channels, k.size, MAX_CHANNELS)
+    if t.ndim == 1:
+        n_lik = min(n_lik, t.size)
+    k, t = k[:n_lik], np.broadcast_to(t, (n_lik,)) if t.ndim == 0 else t[:n_lik]
+    if not np.all(np.isfinite(k)) or np.any(k != np.floor(k)) or np.any(k < 0):
+        raise ValueError("the counts of a record must be whole numbers >= 0: the readings are counted events")
+    if not np.all(np.isfinite(t)) or np.any(t <= 0):
+        raise ValueError("the exposure of a record must be finite and > 0")
+    kk, tt, lf = np.zeros(MAX_CHANNELS), np.ones(MAX_CHANNELS), np.zeros(MAX_CHANNELS)
+    kk[:n_lik], tt[:n_lik] = k, t
+    lf[:n_lik] = [math.lgamma(v + 1.0) for v in k]
+    return n_lik, kk, tt, lf
+
+
+def state_fields(obj):
+    """What a snapshot keeps of this class besides the base class's (_state.py): ``exposure`` and ``count_cap``."""
+    return {"exposure": np.array(obj.exposure, dtype=np.float64), "count_cap": int(obj.count_cap)}
+
+
+def kwargs_from_state(fields):
+    """The constructor's keyword arguments from ``state_fields()``'s dict."""
+    return {"exposure": np.array(fields["exposure"], dtype=np.float64), "count_cap": int(fields["count_cap"])}
+
+
+class OptBayesExptPoisson(OptBayesExpt):
+    """``exposure``: the exposure per reading, a scalar or one value per channel; the ``t`` of a record that brings
+    none, and what ``yvar_noise_model()`` divides by.  ``count_cap``: 16, 32 or 64, the count the information's reading
+    is censored at.  Both are public attributes and may be reassigned between calls.  Needs a DeviceModel whose outputs
+    are rates (>= 0).
+
+    ``utility_method``: ``"mutual_information"`` (default, models of one channel; ``utility_information()``) or any name
+    the base class knows, which then works on the Gaussian approximation ``yvar_noise_model()`` gives.
+    ``pdf_update((setting, k))`` or ``((setting, k, t))``.  ``last_information`` holds ``{"cap", "tail_max"}`` of the last
+    information pass: ``tail_max``, the largest mass of the outcome ">= cap" over this rank's settings, says whether
+    ``count_cap`` is large enough for the rates.  The summaries that take a per-record Gaussian ``sigma`` raise
+    ``NotImplementedError``."""
+
+    def __init__(self, measurement_model, setting_values, parameter_samples, constants, exposure=1.0, count_cap=32,
+                 utility_method=INFORMATION, **kwargs):
+        if not isinstance(measurement_model, DeviceModel):
+            raise ValueError("OptBayesExptPoisson needs a DeviceModel (a built-in model, models.from_expression or "
+                             "models.from_function): the information is summed over settings x particles on the device")
+        if utility_method == INFORMATION and measurement_model.n_channels != 1:
+            raise ValueError(f"utility_method=\"{INFORMATION}\" takes a model of one channel (the joint information of "
+                             f"several counted channels is not built), got {measurement_model.n_channels}; the variance "
+                             f"utilities work on every channel count: {', '.join(VARIANCE_METHODS)}")
+        check_exposure(exposure, measurement_model.n_channels)
+        check_cap(count_cap)
+        base_method = "variance_approx" if utility_method == INFORMATION else utility_method
+        OptBayesExpt.__init__(self, measurement_model, setting_values, parameter_samples, constants,
+                              utility_method=base_method, **kwargs)
+        if self._device_model is None:
+            raise ValueError("OptBayesExptPoisson needs a DeviceModel that runs on the device")
+        self.exposure = exposure
+        self.count_cap = count_cap
+        self.last_information = None
+        if utility_method == INFORMATION:
+            self.utility_method = INFORMATION
+            self.utility = self.utility_information
+        self._nu_bar = {}         # settings slice -> (key, device (C, e - b)): _noise_variance()
+
+    # -- likelihood: the counts of a record against every particle's rates ---------------
+    def _likelihood_overridden(self):
+        return _overridden(self, "likelihood", OptBayesExpt, OptBayesExptPoisson)
+
+    def likelihood(self, y_model, measurement_record):
+        """``L_i = exp(sum_c [k_c log lambda_c,i - lambda_c,i - log k_c!])``, ``lambda = t r``, from ``y_model`` (C x N_p
+        rates) on the device; 0 for a particle with a rate that is NaN, negative or infinite."""
+        return self._likelihood_device(y_model, measurement_record).cpu().numpy()
+
+    def _likelihood_device(self, y_model, measurement_record):
+        """The likelihood as a device tensor; ``y_model`` None: the model is evaluated at the record's setting inside
+        the same kernel."""
+        given = measurement_record[2] if len(measurement_record) > 2 else None
+        exposure = check_exposure(self.exposure, self.n_channels) if given is None else given
+        n, kk, tt, lf = check_record_counts(measurement_record[1], exposure, self.n_channels)
+        if y_model is None:
+            par = self._parameters.tensor()
+            n_p = par.shape[1]
+            y_args = (None, 0, _ptr(par), n_p, n_p, _lib.host_ptr(self._setting_array(measurement_record[0])))
+        else:
+            y_dev = self._y_to_device(y_model)
+            n_p = y_dev.shape[1]
+            y_args = (_ptr(y_dev), n_p, None, 0, n_p, None)
+        out = torch.empty(n_p, dtype=torch.float64, device=self._device)
+        self._mlib.call("obe_poisson_likelihood", self._model_struct, *y_args, _lib.host_ptr(kk), _lib.host_ptr(tt),
+                        _lib.host_ptr(lf), n, self._choke_value(), _ptr(out), self._stream())
+        return out
+
+    # (the order OptBayesExptSignalNoise established for a class whose likelihood is a kernel of its own)
+    _pdf_update = OptBayesExptSignalNoise._pdf_update
+
+    # -- one pass over settings x particles ----------------------------------------------
+    def _call(self, x, ld_s, n, exposure, cost_t, cost_s, info, tail, pmf, nu):
+        """obe_poisson_information on the ``n`` settings whose first column ``x`` addresses; the outputs that are not
+        None are written."""
+        cap = check_cap(self.count_cap)
+        p, w = self._pw_tensors()
+        n_p = p.shape[1]
+        # (a workspace of the call's own: the object's workspace keeps the record of a sweep enqueued ahead)
+        nbytes = int(self._mlib.cdll.obe_poisson_workspace_bytes(n_p, n, self.n_channels, cap))
+        ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self._device)
+        opt = [None if t is None else _ptr(t) for t in (info, tail, pmf, nu)]
+        self._mlib.call("obe_poisson_information", self._model_struct, x, ld_s, n, _ptr(p), n_p, n_p, _ptr(w),
+                        float(exposure), cap, cost_t, float(cost_s), *opt, _ptr(ws), nbytes, self._stream())
+
+    def _pass(self, begin, end, want_information):
+        """Device ``(information (end - begin,) or None, nu_bar (C, end - begin))`` of the settings [begin, end) of the
+        design grid.  ``nu_bar`` is cached until the particles, the weights or ``exposure`` change; the information,
+        divided by a ``cost_estimate()`` that may depend on anything, is formed anew by every call that wants it, and
+        leaves ``last_information`` behind."""
+        exposure = check_exposure(self.exposure, self.n_channels)
+        cap = check_cap(self.count_cap)
+        key = (self._particles.version, self._weights.version, exposure.tobytes())
+        hit = self._nu_bar.get((begin, end))
+        if hit is not None and hit[0] == key and not want_information:
+            return None, hit[1]
+        n = end - begin
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self._device)      # noqa: E731
+        nu = new(self.n_channels, max(n, 1))
+        info, tail = (new(max(n, 1)), new(max(n, 1))) if want_information else (None, None)
+        if n > 0:
+            cost_t, cost_s = self._cost_device(whole_grid=True) if want_information else (None, 1.0)
+            # one exposure for all channels goes into the call; exposures per channel divide the rows afterwards
+            uniform = bool(np.all(exposure == exposure[0]))
+            self._call(_P(self._settings_dev.data_ptr() + 8 * begin), self._n_settings, n,
+                       exposure[0] if uniform else 1.0, None if cost_t is None else _P(cost_t.data_ptr() + 8 * begin),
+                       cost_s, info, tail, None, nu)
+            if not uniform:
+                nu /= torch.from_numpy(exposure.reshape(-1, 1)).to(self._device)
+        if want_information:
+            # (NaN where nobody contributes: such a setting says nothing about the cap)
+            worst = float(torch.nan_to_num(tail[:n], nan=0.0).max().item()) if n > 0 else 0.0
+            self.last_information = {"cap": cap, "tail_max": worst}
+        self._nu_bar = {k: v for k, v in self._nu_bar.items() if v[0] == key}
+        self._nu_bar[(begin, end)] = (key, nu)
+        return info, nu
+
+    def _noise_variance(self, begin, end):
+        return self._pass(begin, end, False)[1]
+
+    def utility_information(self):
+        """``U (N_s,)`` over the design grid: the mutual information, in nats, between the parameters and the next
+        reading's count censored at ``count_cap``, divided by ``cost_estimate()``; NaN where no particle contributes.
+        On a sharded object every rank sums its slice of the settings and the slices are gathered.  Afterwards
+        ``last_information`` holds the cap and the largest tail mass over this rank's settings."""
+        if self.n_channels != 1:
+            raise ValueError("utility_information() takes a model of one channel; the variance utilities work on every "
+                             f"channel count: {', '.join(VARIANCE_METHODS)}")
+        info, _ = self._pass(self._s_begin, self._s_end, True)
+        n = self._s_end - self._s_begin
+        return self._gather_settings(info[:n].reshape(1, -1))[0]
+
+    def count_distribution(self, settings=None):
+        """``(n_settings, count_cap + 1)``: the predicted histogram of the next reading's count over the weighted cloud,
+        ``Pbar_k = sum w Pois(k; exposure r) / W`` for k < ``count_cap`` and the mass of ">= count_cap" last, at the
+        design grid or at ``settings`` (points, as ``predict()`` takes them).  What one draws against recorded counts,
+        and what an outlier check sums a tail of.  Models of one channel."""
+        from . import _predictive
+        if self.n_channels != 1:
+            raise ValueError("count_distribution() takes a model of one channel")
+        exposure = check_exposure(self.exposure, 1)
+        cap = check_cap(self.count_cap)
+        x, _, _ = _predictive._inputs(self, settings)
+        n = x.shape[1]
+        pmf = torch.empty((cap + 1, n), dtype=torch.float64, device=self._device)
+        self._call(_ptr(x), n, n, exposure[0], None, 1.0, None, None, pmf, None)
+        return np.ascontiguousarray(pmf.cpu().numpy().T)
+
+    def yvar_noise_model(self):
+        """``(C, n_settings)`` float64: ``nu_bar_c(s) = sum w r_c / W / exposure_c`` over the whole weighted cloud, the
+        variance of the reading k / t at every setting of the design grid (on a sharded object too)."""
+        return self._noise_variance(0, self._n_settings).cpu().numpy()
+
+    def _noise_token(self):
+        # (the noise variance is a pass over the cloud of its own: no sweep is enqueued ahead for this class)
+        return None
+
+    def _noise_var_device(self, values=False):
+        """What a sweep takes as its noise variance: the device ``(C, n_local)`` array of this rank's settings slice."""
+        if _overridden(self, "yvar_noise_model", OptBayesExptPoisson):
+            return OptBayesExpt._noise_var_device(self)
+        t = self._noise_variance(self._s_begin, self._s_end)
+        return t, t.shape[1]
+
+    # -- what takes a Gaussian sigma per record -------------------------------------------
+    def expected_variance_reduction(self, settings=None, dims=None, sigma=None):
+        if sigma is not None:
+            raise ValueError("expected_variance_reduction(): the readings are counts, their noise is the object's own "
+                             "(yvar_noise_model(), from exposure): leave sigma out")
+        return OptBayesExpt.expected_variance_reduction(self, settings, dims, None)
+
+    def opt_setting_batch(self, n, sigma=None, distinct=False, interest=None, interest_weights=None):
+        if sigma is not None:
+            raise ValueError("opt_setting_batch(): the readings are counts, their noise is the object's own "
+                             "(yvar_noise_model(), from exposure): leave sigma out")
+        return OptBayesExpt.opt_setting_batch(self, n, None, distinct, interest, interest_weights)
+
+    def _refuse(self, name):
+        raise NotImplementedError(f"{name}() takes readings with a Gaussian sigma per record, but this object's "
+                                  "readings are counts (k events in an exposure t): count-aware scoring, reading bands "
+                                  "and batch assimilation are not built")
+
+    def predictive_logpdf(self, settings, y_meas, sigma=None):
+        self._refuse("predictive_logpdf")
+
+    def predictive_cdf(self, settings, y_meas, sigma=None, upper=False):
+        self._refuse("predictive_cdf")
+
+    def predictive_pvalue(self, settings, y_meas, sigma=None):
+        self._refuse("predictive_pvalue")
+
+    def reading_quantile(self, q, settings=None, sigma=None, max_passes=48, full_output=False):
+        self._refuse("reading_quantile")
+
+    def reading_interval(self, level=0.95, settings=None, sigma=None, max_passes=48, full_output=False):
+        self._refuse("reading_interval")
+
+    def records_loglik(self, settings, y_meas, sigma=None):
+        self._refuse("records_loglik")
+
+    def pdf_update_batch(self, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None):
+        self._refuse("pdf_update_batch")
