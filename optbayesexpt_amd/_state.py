@@ -51,25 +51,27 @@ LIBRARY_ATTRIBUTES = frozenset((
     "cost_of_new_sweep", "last_sweep_batches",
 ))
 
-#: ... and what an OptBayesExptBinomial sets besides: the library's own on an object of that class only (``shots`` is a
-#: likely name for an attribute of the user's own on any other class, where it travels as it always did)
-BINOMIAL_ATTRIBUTES = frozenset(("shots",))
-#: ... and an OptBayesExptPoisson, in the same way
-POISSON_ATTRIBUTES = frozenset(("exposure", "count_cap", "last_information"))
+#: The classes whose likelihood and noise variance are passes of their own (_ownnoise.py): (key of the snapshot,
+#: module).  Each module has ``CLASS``, ``state_fields(obj)`` (what the snapshot keeps under the key),
+#: ``kwargs_from_state(fields)`` (the constructor's keywords from it) and ``OWN_ATTRIBUTES``: what the library sets
+#: besides LIBRARY_ATTRIBUTES on an object of that class only.
+OWN_NOISE = (("signal_noise", "obe_signalnoise"), ("binomial", "obe_binomial"), ("poisson", "obe_poisson"))
 
 _SELECTION ={"opt_setting": "optimal", "good_setting": "good", "random_setting": "random"}
 
 
+def _own_noise():
+    """(key, module) of OWN_NOISE, the modules imported."""
+    return [(key, importlib.import_module(f"{__package__}.{name}")) for key, name in OWN_NOISE]
+
+
 def _library_classes():
     from .obe_base import OptBayesExpt
-    from .obe_binomial import OptBayesExptBinomial
     from .obe_noiseparam import OptBayesExptNoiseParameter
-    from .obe_poisson import OptBayesExptPoisson
-    from .obe_signalnoise import OptBayesExptSignalNoise
     from .particlepdf import ParticlePDF
     from .sweeper import OptBayesExptSweeper
-    return (OptBayesExptSweeper, OptBayesExptNoiseParameter, OptBayesExptSignalNoise, OptBayesExptBinomial,
-            OptBayesExptPoisson, OptBayesExpt, ParticlePDF)
+    return (OptBayesExptSweeper, OptBayesExptNoiseParameter, *[m.CLASS for _, m in _own_noise()], OptBayesExpt,
+            ParticlePDF)
 
 
 def library_class(cls):
@@ -149,10 +151,8 @@ def snapshot(obj, on_device=False):
     arguments and the user's own attributes are the object's own (``pickle`` and ``copy.deepcopy`` copy them).
     ``on_device``: the cloud, the weights and the moment block as device-side clones instead of host arrays
     (``copy.deepcopy``)."""
-    from . import obe_binomial, obe_poisson
     from .obe_base import OptBayesExpt
     from .obe_noiseparam import OptBayesExptNoiseParameter
-    from .obe_signalnoise import OptBayesExptSignalNoise, state_fields
     from .sweeper import OptBayesExptSweeper
     settle(obj)
     cls = type(obj)
@@ -200,12 +200,9 @@ def snapshot(obj, on_device=False):
     if isinstance(obj, OptBayesExptNoiseParameter):
         st["noise_parameter_index"] = np.array(obj.noise_parameter_index)
         st["constraint_count"] = obj.last_constraint_count
-    if isinstance(obj, OptBayesExptSignalNoise):
-        st["signal_noise"] = state_fields(obj)
-    if isinstance(obj, obe_binomial.OptBayesExptBinomial):
-        st["binomial"] = obe_binomial.state_fields(obj)
-    if isinstance(obj, obe_poisson.OptBayesExptPoisson):
-        st["poisson"] = obe_poisson.state_fields(obj)
+    for key, module in _own_noise():
+        if isinstance(obj, module.CLASS):
+            st[key] = module.state_fields(obj)
     if isinstance(obj, OptBayesExptSweeper):
         st["sweeper"] = {k: getattr(obj, k) for k in ("sweep_settings", "start_stop_subsample", "start_stop_indices",
                                                       "start_stop_choice_indices", "start_stop_values",
@@ -218,11 +215,7 @@ def snapshot(obj, on_device=False):
 def user_attributes(obj):
     """The public names in ``obj.__dict__`` that the library did not set on an object of this class: the user's own,
     which travel with the snapshot as they are."""
-    from .obe_binomial import OptBayesExptBinomial
-    from .obe_poisson import OptBayesExptPoisson
-    own = LIBRARY_ATTRIBUTES | BINOMIAL_ATTRIBUTES if isinstance(obj, OptBayesExptBinomial) else LIBRARY_ATTRIBUTES
-    if isinstance(obj, OptBayesExptPoisson):
-        own = own | POISSON_ATTRIBUTES
+    own = LIBRARY_ATTRIBUTES.union(*[m.OWN_ATTRIBUTES for _, m in _own_noise() if isinstance(obj, m.CLASS)])
     return {k: v for k, v in obj.__dict__.items() if not k.startswith("_") and k not in own}
 
 
@@ -247,10 +240,8 @@ def restore(state, device=None, settings_shard=None, into=None):
     constructor on the saved arguments, then the saved state.  ``device``: where (default: the current torch
     device); ``settings_shard``: a :class:`~optbayesexpt_amd.dist.SettingsShard` of the world it becomes part of
     (collective: every rank restores the same state)."""
-    from . import obe_binomial, obe_poisson
     from .obe_base import OptBayesExpt
     from .obe_noiseparam import OptBayesExptNoiseParameter
-    from .obe_signalnoise import OptBayesExptSignalNoise, kwargs_from_state
     from .sweeper import OptBayesExptSweeper
     check_version(state)
     cls = type(into) if into is not None else _resolve(state["cls"])
@@ -281,13 +272,10 @@ def restore(state, device=None, settings_shard=None, into=None):
             base.__init__(obj, *args, state["noise_parameter_index"], **kw)
         elif base is OptBayesExptNoiseParameter:
             base.__init__(obj, *args, noise_parameter_index=state["noise_parameter_index"], **kw)
-        elif base is OptBayesExptSignalNoise:
-            base.__init__(obj, *args, **kwargs_from_state(state["signal_noise"]), **kw)
-        elif base is obe_binomial.OptBayesExptBinomial:
-            base.__init__(obj, *args, **obe_binomial.kwargs_from_state(state["binomial"]), **kw)
-        elif base is obe_poisson.OptBayesExptPoisson:
-            base.__init__(obj, *args, **obe_poisson.kwargs_from_state(state["poisson"]), **kw)
         else:
+            for key, module in _own_noise():
+                if base is module.CLASS:
+                    kw.update(module.kwargs_from_state(state[key]))
             base.__init__(obj, *args, **kw)
     dev = obj._device
 

@@ -21,8 +21,6 @@ struct TrialExponents {
     double a[kTrials];
 };
 
-__device__ __forceinline__ double clean_weight(double w) { return w > 0.0 ? w : 0.0; }      // NaN, negative -> 0
-
 // Maximum of v over the block; valid in thread 0.  `red` = kBlock / kWave doubles of LDS.  (max is exact: any order)
 __device__ __forceinline__ double block_max(double v, double* red) {
 #pragma unroll

@@ -5,50 +5,34 @@
 //                model (M::eval, the bits obe_eval_over_particles writes) or from given model values.  HBM bound.
 //   information  the exact mutual information, in nats, between theta and the joint outcome of ONE shot in every
 //                channel, for every setting: U = H(mean outcome distribution) - mean of sum_c h2(p_c), over the whole
-//                weighted cloud.  signal_noise_moment_kernel's geometry (obe_signal_noise.hip): one wave per workgroup,
+//                weighted cloud.  cloud_pass_kernel's geometry (obe_cloud_pass.h): one wave per workgroup,
 //                lane <-> setting, the particle axis streamed (the same particle for all lanes), grid = setting tiles x
 //                particle chunks, chunk partials folded in chunk order.  Per lane 2^C outcome sums, one sum of
 //                w sum_c h2, C sums of w p (1 - p) — the variance of a shot, what the Gaussian utilities divide by —
 //                and W.  No atomics: the same bits from run to run.  FP64-issue bound (C log and C log1p per
 //                evaluation).
-#include <algorithm>
 #include <cmath>
 
-#include "obe_models.h"
-#include "obe_select.h"
+#include "obe_cloud_pass.h"
 
 namespace obe {
 namespace {
 
 constexpr int kInfoWaves = 8192;                   // waves the pass aims at (32 per CU): chunks = this / setting tiles
-constexpr int kInfoMinChunk = 256;                 // particles per chunk at least
 constexpr int kBinMaxCh = OBE_BINOMIAL_MAX_CHANNELS;
 constexpr double kInf = __builtin_huge_val();
 constexpr double kNaN = __builtin_nan("");
 
-inline int64_t info_tiles(int64_t n_settings) { return (n_settings + kWave - 1) / kWave; }
-inline int info_chunks(int64_t n_particles, int64_t n_settings) {
-    const int64_t by_size = (n_particles + kInfoMinChunk - 1) / kInfoMinChunk;
-    const int64_t by_grid = std::max<int64_t>(1, kInfoWaves / info_tiles(n_settings));
-    return (int)std::max<int64_t>(1, std::min(by_size, by_grid));
-}
 // 2^C outcome sums; sum w sum_c h2; per channel sum w p (1 - p); then W
 constexpr int info_slots(int n_channels) { return (1 << n_channels) + 1 + n_channels + 1; }
-// chunks x padded settings <= kInfoWaves x 64 + the padded settings, whatever the cloud
-inline int64_t info_words(int64_t n_settings, int n_channels) {
-    return ((int64_t)kInfoWaves + info_tiles(n_settings)) * kWave * info_slots(n_channels);
-}
+
+__device__ __forceinline__ bool is_probability(double p) { return p >= 0.0 && p <= 1.0; }      // (NaN fails)
 
 struct BinLikArg {
-    int n_ch;          // channels entering the product
-    int use_choke;
-    double choke;
-    double x[OBE_MAX_SETDIMS];
+    LikHead head;
     double k[kBinMaxCh];       // successes
     double f[kBinMaxCh];       // failures, n - k
 };
-
-__device__ __forceinline__ bool is_probability(double p) { return p >= 0.0 && p <= 1.0; }      // (NaN fails)
 
 // GIVEN: the model values come from y_in (C, n) rows ld_y apart; neither the cloud nor the setting is read
 template <class M, bool GIVEN>
@@ -62,51 +46,34 @@ __global__ __launch_bounds__(kBlock) void binomial_lik_kernel(obe_model m, BinLi
 #pragma unroll
             for (int c = 0; c < M::NC; ++c) y[c] = y_in[(int64_t)c * ld_y + p];
         } else {
-            M::eval(a.x, ParamRef{particles + p, ld_p}, m, y);
+            M::eval(a.head.x, ParamRef{particles + p, ld_p}, m, y);
         }
         double arg = 0.0;
         bool ok = true;
 #pragma unroll
         for (int c = 0; c < M::NC; ++c) {
             ok = ok && is_probability(y[c]);
-            if (c < a.n_ch) {
+            if (c < a.head.n_ch) {
                 if (a.k[c] > 0.0) arg += a.k[c] * log(y[c]);               // (p = 0 with k > 0: -inf, L = 0)
                 if (a.f[c] > 0.0) arg += a.f[c] * log1p(-y[c]);
             }
         }
         double l = ok ? exp(arg) : 0.0;
-        if (a.use_choke) l = pow(l, a.choke);
+        if (a.head.use_choke) l = pow(l, a.head.choke);
         lik[p] = l;
     }
 }
 
-// partials (chunk, info_slots(C), padded settings), sums over the chunk's contributing particles.  A particle
-// contributes to a lane when its clean weight is > 0 and every p_c of that lane's setting is in [0, 1]; one that does
-// not is carried through the arithmetic with weight 0 and p = 1/2, which leaves every sum's bits as they were.
-template <class M>
-__global__ __launch_bounds__(kWave) void binomial_info_kernel(obe_model m, const double* __restrict__ settings,
-                                                              int64_t ld_s, int64_t n_s,
-                                                              const double* __restrict__ particles, int64_t ld_p,
-                                                              int64_t n, const double* __restrict__ w, int64_t chunk_len,
-                                                              double* __restrict__ partials) {
-    constexpr int C = M::NC, NO = 1 << C;
+// A lane's sums, info_slots(C) of them, over the chunk's contributing particles.  A particle contributes to a lane when
+// its clean weight is > 0 and every p_c of that lane's setting is in [0, 1]; one that does not is carried through the
+// arithmetic with weight 0 and p = 1/2, which leaves every sum's bits as they were.
+template <int C>
+struct BinAcc {
     static_assert(C <= kBinMaxCh, "refused on the host");
-    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
-    const int64_t sc = s < n_s ? s : n_s - 1;                    // (the padding lanes repeat the last setting)
-    double x[M::NS], po[NO], sv[C], sh = 0.0, sw = 0.0;
-#pragma unroll
-    for (int k = 0; k < M::NS; ++k) x[k] = settings[(int64_t)k * ld_s + sc];
-#pragma unroll
-    for (int o = 0; o < NO; ++o) po[o] = 0.0;
-#pragma unroll
-    for (int c = 0; c < C; ++c) sv[c] = 0.0;
-    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
-    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
-    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p] and the particle are the same for all lanes)
-        const double wp = clean_weight(w[p]);
-        if (wp == 0.0) continue;                                 // (whatever the model gives)
-        double y[C];
-        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+    static constexpr int NO = 1 << C, kSlots = info_slots(C);
+    double po[NO], sv[C], sh, sw;
+
+    __device__ __forceinline__ void add(double wp, const double (&y)[C]) {
         bool ok = true;
 #pragma unroll
         for (int c = 0; c < C; ++c) ok = ok && is_probability(y[c]);
@@ -130,15 +97,15 @@ __global__ __launch_bounds__(kWave) void binomial_info_kernel(obe_model m, const
         }
         sw += wl;
     }
-    const int64_t n_pad = (int64_t)gridDim.x * kWave;
-    double* out = partials + (int64_t)blockIdx.y * info_slots(C) * n_pad + s;
+    __device__ __forceinline__ void store(double* __restrict__ out, int64_t n_pad) const {
 #pragma unroll
-    for (int o = 0; o < NO; ++o) out[o * n_pad] = po[o];
-    out[NO * n_pad] = sh;
+        for (int o = 0; o < NO; ++o) out[o * n_pad] = po[o];
+        out[NO * n_pad] = sh;
 #pragma unroll
-    for (int c = 0; c < C; ++c) out[(NO + 1 + c) * n_pad] = sv[c];
-    out[(NO + 1 + C) * n_pad] = sw;
-}
+        for (int c = 0; c < C; ++c) out[(NO + 1 + c) * n_pad] = sv[c];
+        out[(NO + 1 + C) * n_pad] = sw;
+    }
+};
 
 // The chunk partials added in chunk order, then per setting
 //   info = max(-sum_o Pbar_o log Pbar_o - S_h / W, 0) / cost,  Pbar_o = S_o / W      (NaN stays NaN; W == 0 gives NaN)
@@ -151,17 +118,14 @@ __global__ __launch_bounds__(kBlock) void binomial_fold_kernel(const double* __r
     const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (s >= n_s) return;
     const int n_out = 1 << n_channels, slots = info_slots(n_channels);
-    double sw = 0.0;
-    for (int j = 0; j < chunks; ++j) sw += partials[((int64_t)j * slots + slots - 1) * n_pad + s];
+    const double sw = chunk_order_sum(partials, chunks, slots, slots - 1, n_pad, s);
     if (info) {
-        double hbar = 0.0, sh = 0.0;
+        double hbar = 0.0;
         for (int o = 0; o < n_out; ++o) {
-            double so = 0.0;
-            for (int j = 0; j < chunks; ++j) so += partials[((int64_t)j * slots + o) * n_pad + s];
-            const double pb = so / sw;
+            const double pb = chunk_order_sum(partials, chunks, slots, o, n_pad, s) / sw;
             if (pb > 0.0) hbar -= pb * log(pb);                  // (0 log 0 = 0)
         }
-        for (int j = 0; j < chunks; ++j) sh += partials[((int64_t)j * slots + n_out) * n_pad + s];
+        const double sh = chunk_order_sum(partials, chunks, slots, n_out, n_pad, s);
         double u = hbar - sh / sw;
         if (u < 0.0) u = 0.0;                                    // (rounding; a NaN is kept)
         if (!(sw > 0.0 && sw < kInf)) u = kNaN;
@@ -169,8 +133,7 @@ __global__ __launch_bounds__(kBlock) void binomial_fold_kernel(const double* __r
     }
     if (noise_var) {
         for (int c = 0; c < n_channels; ++c) {
-            double v = 0.0;
-            for (int j = 0; j < chunks; ++j) v += partials[((int64_t)j * slots + n_out + 1 + c) * n_pad + s];
+            const double v = chunk_order_sum(partials, chunks, slots, n_out + 1 + c, n_pad, s);
             noise_var[(int64_t)c * n_s + s] = v / sw / shots;
         }
     }
@@ -201,11 +164,7 @@ int obe_binomial_likelihood(const obe_model* m, const double* d_y, int64_t ld_y,
     if (int rc = obe_model_validate(&mm)) return rc;
     if (n_lik_channels < 0 || n_lik_channels > mm.n_channels)
         return bad_arg("obe_binomial_likelihood: n_lik_channels outside 0..the model's channels");
-    BinLikArg a{};
-    a.n_ch = n_lik_channels;
-    a.use_choke = choke == choke;                                // NaN: no choke
-    a.choke = choke;
-    for (int i = 0; i < mm.n_setdims && i < OBE_MAX_SETDIMS; ++i) a.x[i] = d_y ? 0.0 : h_setting[i];
+    BinLikArg a{lik_head(mm, n_lik_channels, choke, d_y ? nullptr : h_setting), {}, {}};
     for (int c = 0; c < n_lik_channels; ++c) {
         const double k = h_successes[c], n = h_shots[c];
         if (!is_count(k) || !is_count(n) || k < 0.0 || n < 1.0 || k > n)
@@ -232,11 +191,11 @@ int obe_binomial_likelihood(const obe_model* m, const double* d_y, int64_t ld_y,
 }
 
 int64_t obe_binomial_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels) {
-    (void)n_particles;                                           // (the chunks are bounded whatever the cloud: info_words)
+    (void)n_particles;                                           // (the chunks are bounded whatever the cloud)
     if (n_settings < 1) n_settings = 1;
     if (n_channels < 1) n_channels = 1;
     if (n_channels > kBinMaxCh) n_channels = kBinMaxCh;
-    return info_words(n_settings, n_channels) * (int64_t)sizeof(double);
+    return cloud_pass_words(n_settings, info_slots(n_channels), kInfoWaves) * (int64_t)sizeof(double);
 }
 
 int obe_binomial_information(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
@@ -247,22 +206,15 @@ int obe_binomial_information(const obe_model* m, const double* d_settings, int64
         return bad_arg("obe_binomial_information: null pointer");
     if (!d_information && !d_noise_var)
         return bad_arg("obe_binomial_information: null pointer for both d_information and d_noise_var");
-    if (n_settings < 1 || ld_s < n_settings)
-        return bad_arg("obe_binomial_information: n_settings < 1 or a row of settings shorter than that");
-    if (n_particles < 1 || ld_p < n_particles) return bad_arg("obe_binomial_information: bad cloud size");
     if (!(shots >= 1.0 && shots < kInf)) return bad_arg("obe_binomial_information: shots not finite or < 1");
     if (m->n_channels > kBinMaxCh)
         return bad_arg("obe_binomial_information: the model has more than OBE_BINOMIAL_MAX_CHANNELS channels");
     obe_model mm = *m;
     if (int rc = obe_model_validate(&mm)) return rc;
-    if (ws_bytes < obe_binomial_workspace_bytes(n_particles, n_settings, mm.n_channels))
-        return bad_arg("obe_binomial_information: workspace too small");
-    const int64_t tiles = info_tiles(n_settings);
-    if (tiles > 0x7fffffff) return bad_arg("obe_binomial_information: too many settings for one call");
-    const int chunks = info_chunks(n_particles, n_settings);
-    // whole waves of particles per chunk (the count of chunks that are not empty may then be smaller)
-    const int64_t chunk_len = ((n_particles + chunks - 1) / chunks + kWave - 1) / kWave * kWave;
-    const int used = (int)((n_particles + chunk_len - 1) / chunk_len);
+    if (int rc = cloud_pass_refusal("obe_binomial_information", n_settings, ld_s, n_particles, ld_p, ws_bytes,
+                                    obe_binomial_workspace_bytes(n_particles, n_settings, mm.n_channels)))
+        return rc;
+    const CloudPassPlan plan = cloud_pass_plan(n_particles, n_settings, kInfoWaves);
     double* partials = static_cast<double*>(d_ws);
     hipStream_t st = as_stream(stream);
     return dispatch_model(mm, [&](auto M) -> int {
@@ -270,12 +222,11 @@ int obe_binomial_information(const obe_model* m, const double* d_settings, int64
         if constexpr (Model::NC > kBinMaxCh) {
             return bad_arg("obe_binomial_information: the model has more than OBE_BINOMIAL_MAX_CHANNELS channels");
         } else {
-            const dim3 grid((unsigned)tiles, (unsigned)used);
-            binomial_info_kernel<Model><<<grid, kWave, 0, st>>>(mm, d_settings, ld_s, n_settings, d_particles, ld_p,
-                                                                n_particles, d_weights, chunk_len, partials);
-            OBE_CHECK_LAUNCH("binomial_info_kernel");
+            cloud_pass_kernel<Model, BinAcc<Model::NC>><<<plan.grid(), kWave, 0, st>>>(
+                mm, d_settings, ld_s, n_settings, d_particles, ld_p, n_particles, d_weights, plan.chunk_len, partials);
+            OBE_CHECK_LAUNCH("cloud_pass_kernel");
             binomial_fold_kernel<<<(int)((n_settings + kBlock - 1) / kBlock), kBlock, 0, st>>>(
-                partials, used, Model::NC, tiles * kWave, n_settings, shots, d_cost, cost, d_information, d_noise_var);
+                partials, plan.used, Model::NC, plan.n_pad, n_settings, shots, d_cost, cost, d_information, d_noise_var);
             OBE_CHECK_LAUNCH("binomial_fold_kernel");
             return 0;
         }

@@ -233,6 +233,9 @@ inline int64_t resample_wide_ws_bytes(int n_dims) {
     return ((int64_t)n_dims * n_dims + n_dims) * (int64_t)sizeof(double);
 }
 
+// a particle weight as every sum over the cloud takes it
+__device__ __forceinline__ double clean_weight(double w) { return w > 0.0 ? w : 0.0; }      // NaN, negative -> 0
+
 // np.nan_to_num defaults: NaN -> 0, +inf -> DBL_MAX, -inf -> -DBL_MAX
 __device__ __forceinline__ double nan_to_num(double v) {
     if (v != v) return 0.0;

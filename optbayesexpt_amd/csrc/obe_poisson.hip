@@ -6,7 +6,7 @@
 //                obe_eval_over_particles writes) or from given model values.  HBM bound.
 //   information  the exact mutual information, in nats, between theta and the next reading's count censored at CAP
 //                (outcomes 0 .. CAP-1 and ">= CAP"), for every setting, over the whole weighted cloud; models of ONE
-//                channel.  binomial_info_kernel's geometry (obe_binomial.hip): one wave per workgroup, lane <-> setting,
+//                channel.  cloud_pass_kernel's geometry (obe_cloud_pass.h): one wave per workgroup, lane <-> setting,
 //                the particle axis streamed (the same particle for all lanes), grid = setting tiles x particle chunks,
 //                chunk partials folded in chunk order.  Per evaluation one exp (p_0 = e^-lambda), one log lambda, the
 //                recurrence p_k = p_k-1 (lambda / k) unrolled over the compile-time CAP — CAP outcome sums per lane in
@@ -17,14 +17,12 @@
 #include <cmath>
 #include <type_traits>
 
-#include "obe_models.h"
-#include "obe_select.h"
+#include "obe_cloud_pass.h"
 
 namespace obe {
 namespace {
 
 constexpr int kPoisWaves = 4096;                   // waves the pass aims at (2 .. 4 fit a SIMD): chunks = this / tiles
-constexpr int kPoisMinChunk = 256;                 // particles per chunk at least
 constexpr int kPoisMaxCap = OBE_POISSON_MAX_CAP;
 constexpr double kInf = __builtin_huge_val();
 constexpr double kNaN = __builtin_nan("");
@@ -50,32 +48,19 @@ __device__ constexpr double kLogFact[kPoisMaxCap] = {
     188.6281734236716, 192.7390472878449, 196.86618167289, 201.00931639928152,
 };
 
-inline int64_t pois_tiles(int64_t n_settings) { return (n_settings + kWave - 1) / kWave; }
-inline int pois_chunks(int64_t n_particles, int64_t n_settings) {
-    const int64_t by_size = (n_particles + kPoisMinChunk - 1) / kPoisMinChunk;
-    const int64_t by_grid = std::max<int64_t>(1, kPoisWaves / pois_tiles(n_settings));
-    return (int)std::max<int64_t>(1, std::min(by_size, by_grid));
-}
 // cap outcome sums, sum w tau, sum w h (both absent at cap = 0); per channel sum w r; then W
 constexpr int pois_slots(int n_channels, int cap) { return (cap ? cap + 2 : 0) + n_channels + 1; }
-// chunks x padded settings <= kPoisWaves x 64 + the padded settings, whatever the cloud
-inline int64_t pois_words(int64_t n_settings, int n_channels, int cap) {
-    return ((int64_t)kPoisWaves + pois_tiles(n_settings)) * kWave * pois_slots(n_channels, cap);
-}
 inline bool is_cap(int cap) { return cap == 16 || cap == 32 || cap == 64; }
 
+// finite and >= 0 (NaN fails), and so is exposure x rate
+__device__ __forceinline__ bool is_rate(double r, double t) { return r >= 0.0 && r * t < kInf; }
+
 struct PoisLikArg {
-    int n_ch;          // channels entering the product
-    int use_choke;
-    double choke;
-    double x[OBE_MAX_SETDIMS];
+    LikHead head;
     double k[OBE_MAX_CHANNELS];        // counted events
     double t[OBE_MAX_CHANNELS];        // exposure
     double lf[OBE_MAX_CHANNELS];       // log k!
 };
-
-// finite and >= 0 (NaN fails), and so is exposure x rate
-__device__ __forceinline__ bool is_rate(double r, double t) { return r >= 0.0 && r * t < kInf; }
 
 // GIVEN: the model values come from y_in (C, n) rows ld_y apart; neither the cloud nor the setting is read
 template <class M, bool GIVEN>
@@ -88,13 +73,13 @@ __global__ __launch_bounds__(kBlock) void poisson_lik_kernel(obe_model m, PoisLi
 #pragma unroll
             for (int c = 0; c < M::NC; ++c) y[c] = y_in[(int64_t)c * ld_y + p];
         } else {
-            M::eval(a.x, ParamRef{particles + p, ld_p}, m, y);
+            M::eval(a.head.x, ParamRef{particles + p, ld_p}, m, y);
         }
         double arg = 0.0;
         bool ok = true;
 #pragma unroll
         for (int c = 0; c < M::NC; ++c) {
-            const bool in = c < a.n_ch;
+            const bool in = c < a.head.n_ch;
             ok = ok && is_rate(y[c], in ? a.t[c] : 1.0);
             if (in) {
                 const double lam = a.t[c] * y[c];
@@ -104,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void poisson_lik_kernel(obe_model m, PoisLi
             }
         }
         double l = ok ? exp(arg) : 0.0;
-        if (a.use_choke) l = pow(l, a.choke);
+        if (a.head.use_choke) l = pow(l, a.head.choke);
         lik[p] = l;
     }
 }
@@ -116,6 +101,8 @@ __global__ __launch_bounds__(kBlock) void poisson_lik_kernel(obe_model m, PoisLi
 // and s2 = fma(p_k, log k!, s2): the dependent chain is ONE multiplication per outcome among five operations, so a
 // single wave already keeps the FP64 pipe issuing and two particles per trip would only double the live registers.
 //   sum_k p_k (k log lambda - lambda - log k!) = log lambda . lambda (s0 - p_CAP-1) - lambda s0 - s2,  k p_k = lambda p_k-1
+// (cloud_pass_kernel's scaffold restated: with these sums as an Acc of that kernel the schedule holds ten more VGPRs
+// at cap 32 and a wave fewer fits a SIMD — profiles/own_noise_refactor.txt)
 template <class M, int CAP>
 __global__ __launch_bounds__(kWave) void poisson_info_kernel(obe_model m, const double* __restrict__ settings,
                                                              int64_t ld_s, int64_t n_s,
@@ -196,21 +183,19 @@ __global__ __launch_bounds__(kBlock) void poisson_fold_kernel(const double* __re
     const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (s >= n_s) return;
     const int slots = pois_slots(n_channels, cap);
-    double sw = 0.0;
-    for (int j = 0; j < chunks; ++j) sw += partials[((int64_t)j * slots + slots - 1) * n_pad + s];
+    const double sw = chunk_order_sum(partials, chunks, slots, slots - 1, n_pad, s);
     const bool nobody = !(sw > 0.0 && sw < kInf);
     if (cap > 0 && (info || tail || pmf)) {
-        double hbar = 0.0, sh = 0.0;
+        double hbar = 0.0;
         for (int k = 0; k <= cap; ++k) {                         // (slot cap: tau)
-            double so = 0.0;
-            for (int j = 0; j < chunks; ++j) so += partials[((int64_t)j * slots + k) * n_pad + s];
+            const double so = chunk_order_sum(partials, chunks, slots, k, n_pad, s);
             const double pb = nobody ? kNaN : so / sw;
             if (pb > 0.0) hbar -= pb * log(pb);                  // (0 log 0 = 0)
             if (pmf) pmf[(int64_t)k * n_s + s] = pb;
             if (tail && k == cap) tail[s] = pb;
         }
         if (info) {
-            for (int j = 0; j < chunks; ++j) sh += partials[((int64_t)j * slots + cap + 1) * n_pad + s];
+            const double sh = chunk_order_sum(partials, chunks, slots, cap + 1, n_pad, s);
             double u = hbar - sh / sw;
             if (u < 0.0) u = 0.0;                                // (rounding; a NaN is kept)
             if (nobody) u = kNaN;
@@ -220,8 +205,7 @@ __global__ __launch_bounds__(kBlock) void poisson_fold_kernel(const double* __re
     if (noise_var) {
         const int first = cap ? cap + 2 : 0;
         for (int c = 0; c < n_channels; ++c) {
-            double v = 0.0;
-            for (int j = 0; j < chunks; ++j) v += partials[((int64_t)j * slots + first + c) * n_pad + s];
+            const double v = chunk_order_sum(partials, chunks, slots, first + c, n_pad, s);
             noise_var[(int64_t)c * n_s + s] = v / sw / exposure;
         }
     }
@@ -252,11 +236,7 @@ int obe_poisson_likelihood(const obe_model* m, const double* d_y, int64_t ld_y, 
     if (int rc = obe_model_validate(&mm)) return rc;
     if (n_lik_channels < 0 || n_lik_channels > mm.n_channels || n_lik_channels > OBE_MAX_CHANNELS)
         return bad_arg("obe_poisson_likelihood: n_lik_channels outside 0..the model's channels");
-    PoisLikArg a{};
-    a.n_ch = n_lik_channels;
-    a.use_choke = choke == choke;                                // NaN: no choke
-    a.choke = choke;
-    for (int i = 0; i < mm.n_setdims && i < OBE_MAX_SETDIMS; ++i) a.x[i] = d_y ? 0.0 : h_setting[i];
+    PoisLikArg a{lik_head(mm, n_lik_channels, choke, d_y ? nullptr : h_setting), {}, {}, {}};
     for (int c = 0; c < n_lik_channels; ++c) {
         if (!is_count(h_counts[c]))
             return bad_arg("obe_poisson_likelihood: a count is not a whole number >= 0");
@@ -280,11 +260,11 @@ int obe_poisson_likelihood(const obe_model* m, const double* d_y, int64_t ld_y, 
 }
 
 int64_t obe_poisson_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels, int32_t cap) {
-    (void)n_particles;                                           // (the chunks are bounded whatever the cloud: pois_words)
+    (void)n_particles;                                           // (the chunks are bounded whatever the cloud)
     if (n_settings < 1) n_settings = 1;
     n_channels = std::min(std::max(n_channels, 1), OBE_MAX_CHANNELS);
     cap = cap <= 16 ? 16 : cap <= 32 ? 32 : kPoisMaxCap;         // (the next cap there is: the size never shrinks)
-    return pois_words(n_settings, n_channels, cap) * (int64_t)sizeof(double);
+    return cloud_pass_words(n_settings, pois_slots(n_channels, cap), kPoisWaves) * (int64_t)sizeof(double);
 }
 
 int obe_poisson_information(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
@@ -297,9 +277,6 @@ int obe_poisson_information(const obe_model* m, const double* d_settings, int64_
     const bool outcomes = d_information || d_tail || d_pmf;
     if (!outcomes && !d_noise_var)
         return bad_arg("obe_poisson_information: null pointer for all of d_information, d_tail, d_pmf and d_noise_var");
-    if (n_settings < 1 || ld_s < n_settings)
-        return bad_arg("obe_poisson_information: n_settings < 1 or a row of settings shorter than that");
-    if (n_particles < 1 || ld_p < n_particles) return bad_arg("obe_poisson_information: bad cloud size");
     if (!is_exposure(exposure)) return bad_arg("obe_poisson_information: exposure not finite and > 0");
     if (!is_cap(cap)) return bad_arg("obe_poisson_information: cap is not 16, 32 or 64");
     obe_model mm = *m;
@@ -307,24 +284,19 @@ int obe_poisson_information(const obe_model* m, const double* d_settings, int64_
     if (outcomes && mm.n_channels != 1)
         return bad_arg("obe_poisson_information: d_information, d_tail and d_pmf take a model of one channel "
                        "(d_noise_var alone works for every channel count)");
-    if (ws_bytes < obe_poisson_workspace_bytes(n_particles, n_settings, mm.n_channels, cap))
-        return bad_arg("obe_poisson_information: workspace too small");
-    const int64_t tiles = pois_tiles(n_settings);
-    if (tiles > 0x7fffffff) return bad_arg("obe_poisson_information: too many settings for one call");
-    const int chunks = pois_chunks(n_particles, n_settings);
-    // whole waves of particles per chunk (the count of chunks that are not empty may then be smaller)
-    const int64_t chunk_len = ((n_particles + chunks - 1) / chunks + kWave - 1) / kWave * kWave;
-    const int used = (int)((n_particles + chunk_len - 1) / chunk_len);
+    if (int rc = cloud_pass_refusal("obe_poisson_information", n_settings, ld_s, n_particles, ld_p, ws_bytes,
+                                    obe_poisson_workspace_bytes(n_particles, n_settings, mm.n_channels, cap)))
+        return rc;
+    const CloudPassPlan plan = cloud_pass_plan(n_particles, n_settings, kPoisWaves);
     double* partials = static_cast<double*>(d_ws);
     hipStream_t st = as_stream(stream);
     const int run_cap = outcomes ? cap : 0;                      // (no outcome sums where nobody asks for them)
     return dispatch_model(mm, [&](auto M) -> int {
         using Model = decltype(M);
-        const dim3 grid((unsigned)tiles, (unsigned)used);
         auto launch = [&](auto CapTag) {
             constexpr int CAP = decltype(CapTag)::value;
-            poisson_info_kernel<Model, CAP><<<grid, kWave, 0, st>>>(mm, d_settings, ld_s, n_settings, d_particles, ld_p,
-                                                                    n_particles, d_weights, exposure, chunk_len,
+            poisson_info_kernel<Model, CAP><<<plan.grid(), kWave, 0, st>>>(mm, d_settings, ld_s, n_settings, d_particles, ld_p,
+                                                                    n_particles, d_weights, exposure, plan.chunk_len,
                                                                     partials);
         };
         if constexpr (Model::NC == 1) {
@@ -340,7 +312,7 @@ int obe_poisson_information(const obe_model* m, const double* d_settings, int64_
         }
         OBE_CHECK_LAUNCH("poisson_info_kernel");
         poisson_fold_kernel<<<(int)((n_settings + kBlock - 1) / kBlock), kBlock, 0, st>>>(
-            partials, used, Model::NC, run_cap, tiles * kWave, n_settings, exposure, d_cost, cost, d_information, d_tail,
+            partials, plan.used, Model::NC, run_cap, plan.n_pad, n_settings, exposure, d_cost, cost, d_information, d_tail,
             d_pmf, d_noise_var);
         OBE_CHECK_LAUNCH("poisson_fold_kernel");
         return 0;

@@ -18,8 +18,6 @@ constexpr int kDigits = 256;              // radix select: 8 passes of 8 bits ov
 constexpr int kPasses = 8;
 constexpr int kAggregateFrom = 8;         // lanes of a wave that must share a bin before they are summed in registers
 
-__device__ __forceinline__ double clean_weight(double w) { return w > 0.0 ? w : 0.0; }      // NaN, negative -> 0
-
 __device__ __forceinline__ u64 weight_q(double w, int k) {
     const double v = rint(ldexp(clean_weight(w), k));
     return v < 9.2e18 ? (u64)v : (u64)9200000000000000000ull;

@@ -18,13 +18,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from .models import DeviceModel
-from .obe_base import OptBayesExpt, _overridden
-from .obe_signalnoise import OptBayesExptSignalNoise
+from ._ownnoise import INFORMATION, CountReadings
 from .particlepdf import _P, _ptr
 
 MAX_CHANNELS = _lib.OBE_BINOMIAL_MAX_CHANNELS
-INFORMATION = "mutual_information"
+#: the public names the library sets on an object of this class only (_state.py): ``shots`` is a likely name for an
+#: attribute of the user's own on any other class, where it travels as it always did
+OWN_ATTRIBUTES = frozenset(("shots",))
 
 
 # ---------------------------------------------------------------------------------------- argument checks (host)
@@ -88,66 +88,37 @@ def kwargs_from_state(fields):
     return {"shots": np.array(fields["shots"], dtype=np.float64)}
 
 
-class OptBayesExptBinomial(OptBayesExpt):
+class OptBayesExptBinomial(CountReadings):
     """``shots``: the shots per reading, a scalar or one value per channel (a public attribute; it may be reassigned
-    between calls).  It is the ``n`` of a record that brings none, and what ``yvar_noise_model()`` divides by.  Needs a
-    DeviceModel of at most 3 channels whose outputs are probabilities.
+    between calls).  It is the ``n`` of a record that brings none, and what ``yvar_noise_model()`` divides by:
+    ``nu_bar_c(s) = sum w p_c (1 - p_c) / W / shots_c``, the variance of the fraction k / n.  Needs a DeviceModel of at
+    most 3 channels whose outputs are probabilities.
 
     ``utility_method``: ``"mutual_information"`` (default; ``utility_information()``: the information of the NEXT
     SHOT, whatever ``shots`` is) or any name the base class knows, which then works on the Gaussian approximation
-    ``yvar_noise_model()`` gives.  ``pdf_update((setting, k))`` or ``((setting, k, n))``.  The summaries that take a
-    per-record Gaussian ``sigma`` raise ``NotImplementedError``."""
+    ``yvar_noise_model()`` gives.  ``pdf_update((setting, k))`` or ``((setting, k, n))``; ``likelihood()``:
+    ``L_i = exp(sum_c [k_c log p_c,i + (n_c - k_c) log1p(-p_c,i)])``, 0 for a particle with a probability that is NaN
+    or outside [0, 1].  The summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``."""
+    _NOISE_FROM = "shots"
+    _REFUSAL = ("takes readings with a Gaussian sigma per record, but this object's readings are counts (k successes "
+                "in n shots): count-aware scoring, reading bands and batch assimilation are not built")
 
     def __init__(self, measurement_model, setting_values, parameter_samples, constants, shots=1,
                  utility_method=INFORMATION, **kwargs):
-        if not isinstance(measurement_model, DeviceModel):
-            raise ValueError("OptBayesExptBinomial needs a DeviceModel (a built-in model, models.from_expression or "
-                             "models.from_function): the information is summed over settings x particles on the device")
+        self._need_device_model(measurement_model)
         check_channels(measurement_model.n_channels)
         check_shots(shots, measurement_model.n_channels)
-        base_method = "variance_approx" if utility_method == INFORMATION else utility_method
-        OptBayesExpt.__init__(self, measurement_model, setting_values, parameter_samples, constants,
-                              utility_method=base_method, **kwargs)
-        if self._device_model is None:
-            raise ValueError("OptBayesExptBinomial needs a DeviceModel that runs on the device")
+        CountReadings.__init__(self, measurement_model, setting_values, parameter_samples, constants, utility_method,
+                               **kwargs)
         self.shots = shots
-        if utility_method == INFORMATION:
-            self.utility_method = INFORMATION
-            self.utility = self.utility_information
-        self._nu_bar = {}         # settings slice -> (key, device (C, e - b)): _noise_variance()
-
-    # -- likelihood: the counts of a record against every particle's probabilities ------
-    def _likelihood_overridden(self):
-        return _overridden(self, "likelihood", OptBayesExpt, OptBayesExptBinomial)
-
-    def likelihood(self, y_model, measurement_record):
-        """``L_i = exp(sum_c [k_c log p_c,i + (n_c - k_c) log1p(-p_c,i)])`` from ``y_model`` (C x N_p probabilities) on
-        the device; 0 for a particle with a probability that is NaN or outside [0, 1]."""
-        return self._likelihood_device(y_model, measurement_record).cpu().numpy()
 
     def _likelihood_device(self, y_model, measurement_record):
-        """The likelihood as a device tensor; ``y_model`` None: the model is evaluated at the record's setting inside
-        the same kernel."""
+        """The likelihood as a device tensor: the counts of a record against every particle's probabilities.
+        ``y_model`` None: the model is evaluated at the record's setting inside the same kernel."""
         given = measurement_record[2] if len(measurement_record) > 2 else None
         shots = check_shots(self.shots, self.n_channels) if given is None else given
         n, kk, nn = check_counts(measurement_record[1], shots, self.n_channels)
-        if y_model is None:
-            par = self._parameters.tensor()
-            n_p = par.shape[1]
-            y_args = (None, 0, _ptr(par), n_p, n_p, _lib.host_ptr(self._setting_array(measurement_record[0])))
-        else:
-            y_dev = self._y_to_device(y_model)
-            n_p = y_dev.shape[1]
-            y_args = (_ptr(y_dev), n_p, None, 0, n_p, None)
-        out = torch.empty(n_p, dtype=torch.float64, device=self._device)
-        self._mlib.call("obe_binomial_likelihood", self._model_struct, *y_args, _lib.host_ptr(kk), _lib.host_ptr(nn),
-                        n, self._choke_value(), _ptr(out), self._stream())
-        return out
-
-    # (the likelihood — a user's override, or the device's from the model or from given model values —, then
-    # bayesian_update, the constraints after a resample, the drift step and the sweep state: one order for both classes
-    # whose likelihood is a kernel of its own)
-    _pdf_update = OptBayesExptSignalNoise._pdf_update
+        return self._likelihood_call("obe_binomial_likelihood", y_model, measurement_record[0], (kk, nn), n)
 
     # -- one pass over settings x particles: the information and the variance of a shot --
     def _pass(self, begin, end, want_information):
@@ -155,96 +126,36 @@ class OptBayesExptBinomial(OptBayesExpt):
         design grid.  ``nu_bar`` is cached until the particles, the weights or ``shots`` change; the information,
         divided by a ``cost_estimate()`` that may depend on anything, is formed anew by every call that wants it."""
         shots = check_shots(self.shots, self.n_channels)
-        key = (self._particles.version, self._weights.version, shots.tobytes())
-        hit = self._nu_bar.get((begin, end))
-        if hit is not None and hit[0] == key and not want_information:
-            return None, hit[1]
-        p, w = self._pw_tensors()
-        n, n_p = end - begin, p.shape[1]
-        nu = torch.empty((self.n_channels, max(n, 1)), dtype=torch.float64, device=self._device)
-        info = torch.empty(max(n, 1), dtype=torch.float64, device=self._device) if want_information else None
-        if n > 0:
-            cost_t, cost_s = (None, 1.0)
-            if want_information:
-                cost_t, cost_s = self._cost_device(whole_grid=True)
-            # (a workspace of the call's own: the object's workspace keeps the record of a sweep enqueued ahead)
-            nbytes = int(self._mlib.cdll.obe_binomial_workspace_bytes(n_p, n, self.n_channels))
-            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self._device)
-            # one shots for all channels goes into the call; shots per channel divide the rows afterwards (x / 1 is x)
-            uniform = bool(np.all(shots == shots[0]))
-            self._mlib.call("obe_binomial_information", self._model_struct,
-                            _P(self._settings_dev.data_ptr() + 8 * begin), self._n_settings, n, _ptr(p), n_p, n_p,
-                            _ptr(w), float(shots[0]) if uniform else 1.0,
-                            None if cost_t is None else _P(cost_t.data_ptr() + 8 * begin), cost_s,
-                            None if info is None else _ptr(info), _ptr(nu), _ptr(ws), nbytes, self._stream())
-            if not uniform:
-                nu /= torch.from_numpy(shots.reshape(-1, 1)).to(self._device)
-        self._nu_bar = {k: v for k, v in self._nu_bar.items() if v[0] == key}
-        self._nu_bar[(begin, end)] = (key, nu)
-        return info, nu
+        made = {}
 
-    def _noise_variance(self, begin, end):
-        return self._pass(begin, end, False)[1]
+        def compute():
+            p, w = self._pw_tensors()
+            n, n_p = end - begin, p.shape[1]
+            nu = torch.empty((self.n_channels, max(n, 1)), dtype=torch.float64, device=self._device)
+            info = torch.empty(max(n, 1), dtype=torch.float64, device=self._device) if want_information else None
+            if n > 0:
+                cost_t, cost_s = self._cost_device(whole_grid=True) if want_information else (None, 1.0)
+                ws, nbytes = self._pass_workspace("obe_binomial_workspace_bytes", n_p, n, self.n_channels)
+                into_call, rows = self._per_channel(shots)
+                self._mlib.call("obe_binomial_information", self._model_struct,
+                                _P(self._settings_dev.data_ptr() + 8 * begin), self._n_settings, n, _ptr(p), n_p, n_p,
+                                _ptr(w), into_call, None if cost_t is None else _P(cost_t.data_ptr() + 8 * begin),
+                                cost_s, None if info is None else _ptr(info), _ptr(nu), _ptr(ws), nbytes, self._stream())
+                if rows is not None:
+                    nu /= rows
+            made["info"] = info
+            return nu
+
+        if want_information:
+            self._nu_bar.pop((begin, end), None)
+        nu = self._nu_bar_cached(begin, end, shots.tobytes(), compute)
+        return made.get("info"), nu
 
     def utility_information(self):
         """``U (N_s,)`` over the design grid: the mutual information, in nats, between the parameters and the joint
         outcome of the next shot in every channel, divided by ``cost_estimate()``; NaN where no particle contributes.
         On a sharded object every rank sums its slice of the settings and the slices are gathered."""
-        info, _ = self._pass(self._s_begin, self._s_end, True)
-        n = self._s_end - self._s_begin
-        return self._gather_settings(info[:n].reshape(1, -1))[0]
+        return self._information_of_slice()
 
-    def yvar_noise_model(self):
-        """``(C, n_settings)`` float64: ``nu_bar_c(s) = sum w p_c (1 - p_c) / W / shots_c`` over the whole weighted
-        cloud, the variance of the fraction k / n at every setting of the design grid (on a sharded object too)."""
-        return self._noise_variance(0, self._n_settings).cpu().numpy()
 
-    def _noise_token(self):
-        # (the noise variance is a pass over the cloud of its own: no sweep is enqueued ahead for this class)
-        return None
-
-    def _noise_var_device(self, values=False):
-        """What a sweep takes as its noise variance: the device ``(C, n_local)`` array of this rank's settings slice."""
-        if _overridden(self, "yvar_noise_model", OptBayesExptBinomial):
-            return OptBayesExpt._noise_var_device(self)
-        t = self._noise_variance(self._s_begin, self._s_end)
-        return t, t.shape[1]
-
-    # -- what takes a Gaussian sigma per record -------------------------------------------
-    def expected_variance_reduction(self, settings=None, dims=None, sigma=None):
-        if sigma is not None:
-            raise ValueError("expected_variance_reduction(): the readings are counts, their noise is the object's own "
-                             "(yvar_noise_model(), from shots): leave sigma out")
-        return OptBayesExpt.expected_variance_reduction(self, settings, dims, None)
-
-    def opt_setting_batch(self, n, sigma=None, distinct=False, interest=None, interest_weights=None):
-        if sigma is not None:
-            raise ValueError("opt_setting_batch(): the readings are counts, their noise is the object's own "
-                             "(yvar_noise_model(), from shots): leave sigma out")
-        return OptBayesExpt.opt_setting_batch(self, n, None, distinct, interest, interest_weights)
-
-    def _refuse(self, name):
-        raise NotImplementedError(f"{name}() takes readings with a Gaussian sigma per record, but this object's "
-                                  "readings are counts (k successes in n shots): count-aware scoring, reading bands "
-                                  "and batch assimilation are not built")
-
-    def predictive_logpdf(self, settings, y_meas, sigma=None):
-        self._refuse("predictive_logpdf")
-
-    def predictive_cdf(self, settings, y_meas, sigma=None, upper=False):
-        self._refuse("predictive_cdf")
-
-    def predictive_pvalue(self, settings, y_meas, sigma=None):
-        self._refuse("predictive_pvalue")
-
-    def reading_quantile(self, q, settings=None, sigma=None, max_passes=48, full_output=False):
-        self._refuse("reading_quantile")
-
-    def reading_interval(self, level=0.95, settings=None, sigma=None, max_passes=48, full_output=False):
-        self._refuse("reading_interval")
-
-    def records_loglik(self, settings, y_meas, sigma=None):
-        self._refuse("records_loglik")
-
-    def pdf_update_batch(self, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None):
-        self._refuse("pdf_update_batch")
+CLASS = OptBayesExptBinomial

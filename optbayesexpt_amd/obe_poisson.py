@@ -22,14 +22,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from .models import DeviceModel
-from .obe_base import OptBayesExpt, _overridden
-from .obe_signalnoise import OptBayesExptSignalNoise
+from ._ownnoise import INFORMATION, CountReadings
 from .particlepdf import _P, _ptr
 
 MAX_CHANNELS = _lib.OBE_MAX_CHANNELS
 CAPS = (16, 32, 64)
-INFORMATION = "mutual_information"
+#: the public names the library sets on an object of this class only (_state.py)
+OWN_ATTRIBUTES = frozenset(("exposure", "count_cap", "last_information"))
 VARIANCE_METHODS = ("variance_approx", "variance_full", "parameter_variance", "max_min", "pseudo_utility")
 
 
@@ -93,73 +92,45 @@ def kwargs_from_state(fields):
     return {"exposure": np.array(fields["exposure"], dtype=np.float64), "count_cap": int(fields["count_cap"])}
 
 
-class OptBayesExptPoisson(OptBayesExpt):
+class OptBayesExptPoisson(CountReadings):
     """``exposure``: the exposure per reading, a scalar or one value per channel; the ``t`` of a record that brings
-    none, and what ``yvar_noise_model()`` divides by.  ``count_cap``: 16, 32 or 64, the count the information's reading
-    is censored at.  Both are public attributes and may be reassigned between calls.  Needs a DeviceModel whose outputs
-    are rates (>= 0).
+    none, and what ``yvar_noise_model()`` divides by: ``nu_bar_c(s) = sum w r_c / W / exposure_c``, the variance of the
+    reading k / t.  ``count_cap``: 16, 32 or 64, the count the information's reading is censored at.  Both are public
+    attributes and may be reassigned between calls.  Needs a DeviceModel whose outputs are rates (>= 0).
 
     ``utility_method``: ``"mutual_information"`` (default, models of one channel; ``utility_information()``) or any name
     the base class knows, which then works on the Gaussian approximation ``yvar_noise_model()`` gives.
-    ``pdf_update((setting, k))`` or ``((setting, k, t))``.  ``last_information`` holds ``{"cap", "tail_max"}`` of the last
-    information pass: ``tail_max``, the largest mass of the outcome ">= cap" over this rank's settings, says whether
-    ``count_cap`` is large enough for the rates.  The summaries that take a per-record Gaussian ``sigma`` raise
-    ``NotImplementedError``."""
+    ``pdf_update((setting, k))`` or ``((setting, k, t))``; ``likelihood()``:
+    ``L_i = exp(sum_c [k_c log lambda_c,i - lambda_c,i - log k_c!])``, ``lambda = t r``, 0 for a particle with a rate that
+    is NaN, negative or infinite.  ``last_information`` holds ``{"cap", "tail_max"}`` of the last information pass:
+    ``tail_max``, the largest mass of the outcome ">= cap" over this rank's settings, says whether ``count_cap`` is large
+    enough for the rates.  The summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``."""
+    _NOISE_FROM = "exposure"
+    _REFUSAL = ("takes readings with a Gaussian sigma per record, but this object's readings are counts (k events in "
+                "an exposure t): count-aware scoring, reading bands and batch assimilation are not built")
 
     def __init__(self, measurement_model, setting_values, parameter_samples, constants, exposure=1.0, count_cap=32,
                  utility_method=INFORMATION, **kwargs):
-        if not isinstance(measurement_model, DeviceModel):
-            raise ValueError("OptBayesExptPoisson needs a DeviceModel (a built-in model, models.from_expression or "
-                             "models.from_function): the information is summed over settings x particles on the device")
+        self._need_device_model(measurement_model)
         if utility_method == INFORMATION and measurement_model.n_channels != 1:
             raise ValueError(f"utility_method=\"{INFORMATION}\" takes a model of one channel (the joint information of "
                              f"several counted channels is not built), got {measurement_model.n_channels}; the variance "
                              f"utilities work on every channel count: {', '.join(VARIANCE_METHODS)}")
         check_exposure(exposure, measurement_model.n_channels)
         check_cap(count_cap)
-        base_method = "variance_approx" if utility_method == INFORMATION else utility_method
-        OptBayesExpt.__init__(self, measurement_model, setting_values, parameter_samples, constants,
-                              utility_method=base_method, **kwargs)
-        if self._device_model is None:
-            raise ValueError("OptBayesExptPoisson needs a DeviceModel that runs on the device")
+        CountReadings.__init__(self, measurement_model, setting_values, parameter_samples, constants, utility_method,
+                               **kwargs)
         self.exposure = exposure
         self.count_cap = count_cap
         self.last_information = None
-        if utility_method == INFORMATION:
-            self.utility_method = INFORMATION
-            self.utility = self.utility_information
-        self._nu_bar = {}         # settings slice -> (key, device (C, e - b)): _noise_variance()
-
-    # -- likelihood: the counts of a record against every particle's rates ---------------
-    def _likelihood_overridden(self):
-        return _overridden(self, "likelihood", OptBayesExpt, OptBayesExptPoisson)
-
-    def likelihood(self, y_model, measurement_record):
-        """``L_i = exp(sum_c [k_c log lambda_c,i - lambda_c,i - log k_c!])``, ``lambda = t r``, from ``y_model`` (C x N_p
-        rates) on the device; 0 for a particle with a rate that is NaN, negative or infinite."""
-        return self._likelihood_device(y_model, measurement_record).cpu().numpy()
 
     def _likelihood_device(self, y_model, measurement_record):
-        """The likelihood as a device tensor; ``y_model`` None: the model is evaluated at the record's setting inside
-        the same kernel."""
+        """The likelihood as a device tensor: the counts of a record against every particle's rates.  ``y_model``
+        None: the model is evaluated at the record's setting inside the same kernel."""
         given = measurement_record[2] if len(measurement_record) > 2 else None
         exposure = check_exposure(self.exposure, self.n_channels) if given is None else given
         n, kk, tt, lf = check_record_counts(measurement_record[1], exposure, self.n_channels)
-        if y_model is None:
-            par = self._parameters.tensor()
-            n_p = par.shape[1]
-            y_args = (None, 0, _ptr(par), n_p, n_p, _lib.host_ptr(self._setting_array(measurement_record[0])))
-        else:
-            y_dev = self._y_to_device(y_model)
-            n_p = y_dev.shape[1]
-            y_args = (_ptr(y_dev), n_p, None, 0, n_p, None)
-        out = torch.empty(n_p, dtype=torch.float64, device=self._device)
-        self._mlib.call("obe_poisson_likelihood", self._model_struct, *y_args, _lib.host_ptr(kk), _lib.host_ptr(tt),
-                        _lib.host_ptr(lf), n, self._choke_value(), _ptr(out), self._stream())
-        return out
-
-    # (the order OptBayesExptSignalNoise established for a class whose likelihood is a kernel of its own)
-    _pdf_update = OptBayesExptSignalNoise._pdf_update
+        return self._likelihood_call("obe_poisson_likelihood", y_model, measurement_record[0], (kk, tt, lf), n)
 
     # -- one pass over settings x particles ----------------------------------------------
     def _call(self, x, ld_s, n, exposure, cost_t, cost_s, info, tail, pmf, nu):
@@ -168,9 +139,7 @@ class OptBayesExptPoisson(OptBayesExpt):
         cap = check_cap(self.count_cap)
         p, w = self._pw_tensors()
         n_p = p.shape[1]
-        # (a workspace of the call's own: the object's workspace keeps the record of a sweep enqueued ahead)
-        nbytes = int(self._mlib.cdll.obe_poisson_workspace_bytes(n_p, n, self.n_channels, cap))
-        ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self._device)
+        ws, nbytes = self._pass_workspace("obe_poisson_workspace_bytes", n_p, n, self.n_channels, cap)
         opt = [None if t is None else _ptr(t) for t in (info, tail, pmf, nu)]
         self._mlib.call("obe_poisson_information", self._model_struct, x, ld_s, n, _ptr(p), n_p, n_p, _ptr(w),
                         float(exposure), cap, cost_t, float(cost_s), *opt, _ptr(ws), nbytes, self._stream())
@@ -182,33 +151,31 @@ class OptBayesExptPoisson(OptBayesExpt):
         leaves ``last_information`` behind."""
         exposure = check_exposure(self.exposure, self.n_channels)
         cap = check_cap(self.count_cap)
-        key = (self._particles.version, self._weights.version, exposure.tobytes())
-        hit = self._nu_bar.get((begin, end))
-        if hit is not None and hit[0] == key and not want_information:
-            return None, hit[1]
-        n = end - begin
-        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self._device)      # noqa: E731
-        nu = new(self.n_channels, max(n, 1))
-        info, tail = (new(max(n, 1)), new(max(n, 1))) if want_information else (None, None)
-        if n > 0:
-            cost_t, cost_s = self._cost_device(whole_grid=True) if want_information else (None, 1.0)
-            # one exposure for all channels goes into the call; exposures per channel divide the rows afterwards
-            uniform = bool(np.all(exposure == exposure[0]))
-            self._call(_P(self._settings_dev.data_ptr() + 8 * begin), self._n_settings, n,
-                       exposure[0] if uniform else 1.0, None if cost_t is None else _P(cost_t.data_ptr() + 8 * begin),
-                       cost_s, info, tail, None, nu)
-            if not uniform:
-                nu /= torch.from_numpy(exposure.reshape(-1, 1)).to(self._device)
-        if want_information:
-            # (NaN where nobody contributes: such a setting says nothing about the cap)
-            worst = float(torch.nan_to_num(tail[:n], nan=0.0).max().item()) if n > 0 else 0.0
-            self.last_information = {"cap": cap, "tail_max": worst}
-        self._nu_bar = {k: v for k, v in self._nu_bar.items() if v[0] == key}
-        self._nu_bar[(begin, end)] = (key, nu)
-        return info, nu
+        made = {}
 
-    def _noise_variance(self, begin, end):
-        return self._pass(begin, end, False)[1]
+        def compute():
+            n = end - begin
+            new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self._device)      # noqa: E731
+            nu = new(self.n_channels, max(n, 1))
+            info, tail = (new(max(n, 1)), new(max(n, 1))) if want_information else (None, None)
+            if n > 0:
+                cost_t, cost_s = self._cost_device(whole_grid=True) if want_information else (None, 1.0)
+                into_call, rows = self._per_channel(exposure)
+                self._call(_P(self._settings_dev.data_ptr() + 8 * begin), self._n_settings, n, into_call,
+                           None if cost_t is None else _P(cost_t.data_ptr() + 8 * begin), cost_s, info, tail, None, nu)
+                if rows is not None:
+                    nu /= rows
+            if want_information:
+                # (NaN where nobody contributes: such a setting says nothing about the cap)
+                worst = float(torch.nan_to_num(tail[:n], nan=0.0).max().item()) if n > 0 else 0.0
+                self.last_information = {"cap": cap, "tail_max": worst}
+            made["info"] = info
+            return nu
+
+        if want_information:
+            self._nu_bar.pop((begin, end), None)
+        nu = self._nu_bar_cached(begin, end, exposure.tobytes(), compute)
+        return made.get("info"), nu
 
     def utility_information(self):
         """``U (N_s,)`` over the design grid: the mutual information, in nats, between the parameters and the next
@@ -218,9 +185,7 @@ class OptBayesExptPoisson(OptBayesExpt):
         if self.n_channels != 1:
             raise ValueError("utility_information() takes a model of one channel; the variance utilities work on every "
                              f"channel count: {', '.join(VARIANCE_METHODS)}")
-        info, _ = self._pass(self._s_begin, self._s_end, True)
-        n = self._s_end - self._s_begin
-        return self._gather_settings(info[:n].reshape(1, -1))[0]
+        return self._information_of_slice()
 
     def count_distribution(self, settings=None):
         """``(n_settings, count_cap + 1)``: the predicted histogram of the next reading's count over the weighted cloud,
@@ -238,57 +203,5 @@ class OptBayesExptPoisson(OptBayesExpt):
         self._call(_ptr(x), n, n, exposure[0], None, 1.0, None, None, pmf, None)
         return np.ascontiguousarray(pmf.cpu().numpy().T)
 
-    def yvar_noise_model(self):
-        """``(C, n_settings)`` float64: ``nu_bar_c(s) = sum w r_c / W / exposure_c`` over the whole weighted cloud, the
-        variance of the reading k / t at every setting of the design grid (on a sharded object too)."""
-        return self._noise_variance(0, self._n_settings).cpu().numpy()
 
-    def _noise_token(self):
-        # (the noise variance is a pass over the cloud of its own: no sweep is enqueued ahead for this class)
-        return None
-
-    def _noise_var_device(self, values=False):
-        """What a sweep takes as its noise variance: the device ``(C, n_local)`` array of this rank's settings slice."""
-        if _overridden(self, "yvar_noise_model", OptBayesExptPoisson):
-            return OptBayesExpt._noise_var_device(self)
-        t = self._noise_variance(self._s_begin, self._s_end)
-        return t, t.shape[1]
-
-    # -- what takes a Gaussian sigma per record -------------------------------------------
-    def expected_variance_reduction(self, settings=None, dims=None, sigma=None):
-        if sigma is not None:
-            raise ValueError("expected_variance_reduction(): the readings are counts, their noise is the object's own "
-                             "(yvar_noise_model(), from exposure): leave sigma out")
-        return OptBayesExpt.expected_variance_reduction(self, settings, dims, None)
-
-    def opt_setting_batch(self, n, sigma=None, distinct=False, interest=None, interest_weights=None):
-        if sigma is not None:
-            raise ValueError("opt_setting_batch(): the readings are counts, their noise is the object's own "
-                             "(yvar_noise_model(), from exposure): leave sigma out")
-        return OptBayesExpt.opt_setting_batch(self, n, None, distinct, interest, interest_weights)
-
-    def _refuse(self, name):
-        raise NotImplementedError(f"{name}() takes readings with a Gaussian sigma per record, but this object's "
-                                  "readings are counts (k events in an exposure t): count-aware scoring, reading bands "
-                                  "and batch assimilation are not built")
-
-    def predictive_logpdf(self, settings, y_meas, sigma=None):
-        self._refuse("predictive_logpdf")
-
-    def predictive_cdf(self, settings, y_meas, sigma=None, upper=False):
-        self._refuse("predictive_cdf")
-
-    def predictive_pvalue(self, settings, y_meas, sigma=None):
-        self._refuse("predictive_pvalue")
-
-    def reading_quantile(self, q, settings=None, sigma=None, max_passes=48, full_output=False):
-        self._refuse("reading_quantile")
-
-    def reading_interval(self, level=0.95, settings=None, sigma=None, max_passes=48, full_output=False):
-        self._refuse("reading_interval")
-
-    def records_loglik(self, settings, y_meas, sigma=None):
-        self._refuse("records_loglik")
-
-    def pdf_update_batch(self, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None):
-        self._refuse("pdf_update_batch")
+CLASS = OptBayesExptPoisson
