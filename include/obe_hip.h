@@ -1065,6 +1065,28 @@ OBE_API int obe_signal_noise_variance(const obe_model* m, const double* d_settin
                               const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
                               const double* h_noise_coef, double* d_noise_var, void* d_ws, int64_t ws_bytes,
                               void* stream);
+/* K19 — assimilating a recorded data set with THIS likelihood (extends obe_records_loglik, above, and the likelihood
+ * of this section): per particle the log of the product of the factors obe_signal_noise_likelihood gives for the records,
+ * with the 1 / sqrt(2 pi) it leaves out, and without the choke.  A record is a column, as obe_records_loglik takes
+ * records: the setting point d_settings (n_setdims, n_records) and the reading d_y_meas (C, n_records) of ALL C channels
+ * of the model.  With f = what obe_eval_over_particles writes, bit for bit, and nu = a_c + b_c |f| + c_c f^2 (the
+ * arithmetic of the likelihood's nu):
+ *   d_loglik[i] = sum_r sum_c [-(f_c(x_r; theta_i) - y_rc)^2 / (2 nu) - log(nu) / 2] + constant
+ * for EVERY particle, whatever its weight.  constant: a finite host double, the particle-independent part of the call's
+ * records (-n_records C log(2 pi) / 2 makes d_loglik the full log density).  NaN where any nu of the particle is not
+ * > 0 or not finite: a NaN or +-inf model output lands here, and so does a NaN reading.  h_noise_coef: as above.
+ * accumulate != 0: the result is ADDED to what d_loglik holds (a later tile of records of the same request, added in
+ * tile order); 0: it is stored.  obe_records_loglik's geometry: lane <-> particle, its rows in registers; the records
+ * are packed once per call into a table (setting | y) that is read with wave-uniform indices; grid = particle tiles x
+ * record chunks of at least 32 records, the chunk partials added in chunk order: no atomics, the same bits from run to
+ * run, and a permuted cloud gives the permuted bits.  Per evaluation and channel one division and one log.  Nothing is
+ * waited for.  d_ws: obe_signal_noise_records_loglik_workspace_bytes(n_particles, n_records, the model's channels)
+ * bytes, a buffer of its own; the size does not shrink when an argument grows. */
+OBE_API int64_t obe_signal_noise_records_loglik_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels);
+OBE_API int obe_signal_noise_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                                    const double* d_y_meas, int64_t ld_y, const double* h_noise_coef, double constant,
+                                    const double* d_particles, int64_t ld_p, int64_t n_particles, int32_t accumulate,
+                                    double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ---- yes/no outcomes: binomial likelihood and information-gain design (extension) ----
  * Every likelihood above is Gaussian.  Here the model's channel c gives a success probability p_c = f_c(x; theta) and a
@@ -1103,6 +1125,26 @@ OBE_API int obe_binomial_information(const obe_model* m, const double* d_setting
                              const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
                              double shots, const double* d_cost, double cost, double* d_information,
                              double* d_noise_var, void* d_ws, int64_t ws_bytes, void* stream);
+/* K19 — assimilating a recorded data set with THIS likelihood (extends obe_records_loglik and
+ * obe_binomial_likelihood): a record is a column — the setting point d_settings (n_setdims, n_records), the successes
+ * d_successes (C, n_records) and the shots d_shots (C, n_records) of ALL C channels of the model.  With p = what
+ * obe_eval_over_particles writes, bit for bit:
+ *   d_loglik[i] = sum_r sum_c [k_rc log p_c(x_r; theta_i) + (n_rc - k_rc) log1p(-p_c(x_r; theta_i))] + constant
+ * for EVERY particle, whatever its weight; a term whose count is 0 is skipped (p = 0 with k = 0 contributes nothing).
+ * constant: a finite host double (sum_r sum_c log C(n_rc, k_rc) makes d_loglik the full log density).  NaN where any
+ * p_c of the particle at any record is NaN or outside [0, 1]; otherwise -inf where p = 0 meets k > 0 or p = 1 meets
+ * n - k > 0.  A record whose data cannot be one — k or n not finite or not whole, k < 0, n < 1, k > n — makes its chunk
+ * of records, and with it d_loglik, NaN for every particle (obe_records_loglik's rule for a sigma that is not > 0).
+ * Models of at most OBE_BINOMIAL_MAX_CHANNELS channels, else -1 before any launch.  accumulate, the geometry (the table
+ * holds setting | k | n - k, the difference formed once per record), the chunk partials folded in chunk order (no
+ * atomics: the same bits from run to run, a permuted cloud gives the permuted bits) and d_ws: as
+ * obe_signal_noise_records_loglik, with obe_binomial_records_loglik_workspace_bytes.  Per evaluation and channel one
+ * log and one log1p.  Nothing is waited for. */
+OBE_API int64_t obe_binomial_records_loglik_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels);
+OBE_API int obe_binomial_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                                const double* d_successes, int64_t ld_k, const double* d_shots, int64_t ld_n,
+                                double constant, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                                int32_t accumulate, double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ---- counted events: Poisson likelihood and exact information design (extension) ----
  * The model's channel c gives a RATE r_c = f_c(x; theta) in counts per unit exposure; a record holds k_c counted events
@@ -1157,6 +1199,24 @@ OBE_API int obe_poisson_information(const obe_model* m, const double* d_settings
                             double exposure, int32_t cap, const double* d_cost, double cost, double* d_information,
                             double* d_tail, double* d_pmf, double* d_noise_var, void* d_ws, int64_t ws_bytes,
                             void* stream);
+/* K19 — assimilating a recorded data set with THIS likelihood (extends obe_records_loglik and obe_poisson_likelihood):
+ * a record is a column — the setting point d_settings (n_setdims, n_records), the counted events d_counts
+ * (C, n_records) and the exposures d_exposure (C, n_records) of ALL C channels of the model.  With r = what
+ * obe_eval_over_particles writes, bit for bit, and lambda = t_rc r_c(x_r; theta_i):
+ *   d_loglik[i] = sum_r sum_c [k_rc log lambda - lambda] + constant
+ * for EVERY particle, whatever its weight; a channel with k = 0 contributes -lambda alone.  constant: a finite host
+ * double (-sum_r sum_c log k_rc! makes d_loglik the full log density).  NaN where any r_c of the particle at any record
+ * is not a rate (NaN, negative, +inf, or t r overflows); otherwise -inf where lambda = 0 meets k > 0.  A record whose
+ * data cannot be one — k not a whole number >= 0, t not finite and > 0 — makes its chunk of records, and with it
+ * d_loglik, NaN for every particle.  accumulate, the geometry (the table holds setting | k | t), the chunk partials
+ * folded in chunk order (no atomics: the same bits from run to run, a permuted cloud gives the permuted bits) and d_ws:
+ * as obe_signal_noise_records_loglik, with obe_poisson_records_loglik_workspace_bytes.  Per evaluation and channel one
+ * log.  Nothing is waited for. */
+OBE_API int64_t obe_poisson_records_loglik_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels);
+OBE_API int obe_poisson_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                               const double* d_counts, int64_t ld_k, const double* d_exposure, int64_t ld_t,
+                               double constant, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                               int32_t accumulate, double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);

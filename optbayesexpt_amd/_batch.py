@@ -4,8 +4,9 @@ in adaptively tempered stages.
 
 ``pdf_update()`` takes one reading at a time; a recorded spectrum, yesterday's scan or a second model to compare
 evidences meant a loop of R calls.  Here ``records_loglik()`` forms ``l_i = sum_r log p(y_r | x_r, theta_i)`` with
-records x particles evaluations that stay on the chip (csrc/obe_predict.hip, K13a), and ``pdf_update_batch()`` multiplies
-the weights by ``exp(kappa delta (l_i - m))`` stage by stage (csrc/obe_batch.hip, K13b + the existing
+records x particles evaluations that stay on the chip (csrc/obe_predict.hip, K13a; K19 for the classes of
+_ownnoise.py, whose likelihood is their own: ``OptBayesExpt._batch_records()`` is the seam), and ``pdf_update_batch()``
+multiplies the weights by ``exp(kappa delta (l_i - m))`` stage by stage (csrc/obe_batch.hip, K13b + the existing
 ``obe_bayes_update_lik``), each stage's ``delta`` the largest that keeps ``N_eff / N`` at the resample threshold, with
 the reference's resample (particlepdf.py:260-310) between stages.  The argument checks and the stage search are plain
 functions of this module (no device needed); ``OptBayesExpt`` has the methods.
@@ -56,7 +57,7 @@ def refuse_host_model(obe):
                         "(models.from_function / models.from_expression turn a formula into one), not a plain "
                         "Python model_function")
     if obe._likelihood_overridden():
-        raise TypeError("a batch update forms the Gaussian likelihood of the records on the device; this object "
+        raise TypeError("a batch update forms the object's own likelihood of the records on the device; this object "
                         "overrides likelihood(): loop pdf_update() instead")
 
 
@@ -96,40 +97,84 @@ def ess_fraction(s1, s2, n_particles):
 
 
 # ------------------------------------------------------------------------------------------------- device calls
-def _records_on_device(obe, settings, y_meas, sigma):
-    """``(stacked device rows [x; y; sigma], n_setdims, has_sigma)`` of the checked records."""
-    import torch
-    rows = _noise_rows(obe)
-    x, y, s, _ = check_records(settings, y_meas, sigma, obe.allsettings.shape[0], obe.n_channels, rows)
-    stacked = torch.from_numpy(np.vstack([x, y] + ([] if s is None else [s]))).to(obe._device)
-    return stacked, x.shape[0], s is not None
+class GaussianRecords:
+    """The records of a request on the device and ``loglik()``, the (N_p,) device tensor of l for the object's PRESENT
+    cloud: the one seam of the engine below.  ``OptBayesExpt._batch_records()`` returns what serves the object's
+    likelihood; this one is the Gaussian with a sigma per record or from the cloud's noise rows (K13a), the classes of
+    _ownnoise.py bring their own (``OwnRecords``)."""
+
+    def __init__(self, obe, settings, y_meas, sigma):
+        import torch
+        rows = _noise_rows(obe)
+        x, y, s, _ = check_records(settings, y_meas, sigma, obe.allsettings.shape[0], obe.n_channels, rows)
+        self.obe = obe
+        #: stacked device rows [x; y; sigma]
+        self.stacked = torch.from_numpy(np.vstack([x, y] + ([] if s is None else [s]))).to(obe._device)
+        self.n_s, self.has_sigma = x.shape[0], s is not None
+
+    def loglik(self):
+        """Tiled by RECORDS_PER_CALL per library call (later tiles are added, in tile order); a workspace of its
+        own."""
+        import torch
+        obe, n_s = self.obe, self.n_s
+        rows = None if self.has_sigma else _noise_rows(obe)
+        n_c = obe.n_channels
+        p = obe._parameters.tensor()                # (host edits of the cloud are uploaded here)
+        n_p = p.shape[1]
+        out = torch.empty(n_p, dtype=torch.float64, device=obe._device)
+        for start, part in _column_tiles(self.stacked, RECORDS_PER_CALL):
+            n = part.shape[1]
+            d_x, d_y = part[:n_s], part[n_s:n_s + n_c]
+            d_s = _ptr(part[n_s + n_c:]) if self.has_sigma else None
+            nbytes = int(obe._mlib.cdll.obe_records_loglik_workspace_bytes(n_p, n, n_c))
+            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=obe._device)
+            obe._mlib.call("obe_records_loglik", obe._model_struct, _ptr(d_x), n, n, _ptr(d_y), n, d_s, n,
+                           None if rows is None else _lib.host_ptr(rows), _ptr(p), n_p, n_p, 1 if start else 0,
+                           _ptr(out), _ptr(ws), nbytes, obe._stream())
+        return out
 
 
-def _loglik_device(obe, stacked, n_s, has_sigma):
-    """The (N_p,) device tensor of l for the records, tiled by RECORDS_PER_CALL per library call (later tiles are
-    added, in tile order); a workspace of its own."""
-    import torch
-    rows = None if has_sigma else _noise_rows(obe)
-    n_c = obe.n_channels
-    p = obe._parameters.tensor()                # (host edits of the cloud are uploaded here)
-    n_p = p.shape[1]
-    out = torch.empty(n_p, dtype=torch.float64, device=obe._device)
-    for start, part in _column_tiles(stacked, RECORDS_PER_CALL):
-        n = part.shape[1]
-        d_x, d_y = part[:n_s], part[n_s:n_s + n_c]
-        d_s = _ptr(part[n_s + n_c:]) if has_sigma else None
-        nbytes = int(obe._mlib.cdll.obe_records_loglik_workspace_bytes(n_p, n, n_c))
-        ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=obe._device)
-        obe._mlib.call("obe_records_loglik", obe._model_struct, _ptr(d_x), n, n, _ptr(d_y), n, d_s, n,
-                       None if rows is None else _lib.host_ptr(rows), _ptr(p), n_p, n_p, 1 if start else 0,
-                       _ptr(out), _ptr(ws), nbytes, obe._stream())
-    return out
+class OwnRecords:
+    """The seam for a class whose likelihood is its own (_ownnoise.py): ``rows`` (n_setdims + (1 + side) C, n_r) host
+    rows [x; reading; side data], ``constants(begin, end)`` the particle-independent part of the records [begin, end)
+    as a host double, ``entry`` the class's ``*_records_loglik`` entry point and ``extra`` the host arrays it takes
+    between the reading's stride and ``constant`` (``side_rows`` True: the side data's address and stride instead)."""
+
+    def __init__(self, obe, entry, rows, n_setdims, side_rows, constants, extra=()):
+        import torch
+        self.obe, self.entry, self.n_s, self.side_rows = obe, entry, n_setdims, side_rows
+        self.stacked = torch.from_numpy(np.ascontiguousarray(rows)).to(obe._device)
+        self.constants, self.extra = constants, tuple(extra)
+
+    def loglik(self):
+        import torch
+        obe, n_s, n_c = self.obe, self.n_s, self.obe.n_channels
+        p = obe._parameters.tensor()                # (host edits of the cloud are uploaded here)
+        n_p = p.shape[1]
+        out = torch.empty(n_p, dtype=torch.float64, device=obe._device)
+        size = getattr(obe._mlib.cdll, self.entry + "_workspace_bytes")
+        for start, part in _column_tiles(self.stacked, RECORDS_PER_CALL):
+            n = part.shape[1]
+            side = (_ptr(part[n_s + n_c:]), n) if self.side_rows else ()
+            nbytes = int(size(n_p, n, n_c))
+            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=obe._device)
+            obe._mlib.call(self.entry, obe._model_struct, _ptr(part[:n_s]), n, n, _ptr(part[n_s:n_s + n_c]), n, *side,
+                           *[_lib.host_ptr(a) for a in self.extra], float(self.constants(start, start + n)), _ptr(p),
+                           n_p, n_p, 1 if start else 0, _ptr(out), _ptr(ws), nbytes, obe._stream())
+        return out
 
 
-def records_loglik(obe, settings, y_meas, sigma=None):
+def _records_of(obe, settings, y_meas, sigma, side):
+    """What ``obe._batch_records()`` gives; the Gaussian records for whatever has no such method."""
+    make = getattr(obe, "_batch_records", None)
+    if make is None:
+        return GaussianRecords(obe, settings, y_meas, sigma)
+    return make(settings, y_meas, sigma, **side)
+
+
+def records_loglik(obe, settings, y_meas, sigma=None, **side):
     refuse_host_model(obe)
-    stacked, n_s, has_sigma = _records_on_device(obe, settings, y_meas, sigma)
-    return _loglik_device(obe, stacked, n_s, has_sigma).cpu().numpy()
+    return _records_of(obe, settings, y_meas, sigma, side).loglik().cpu().numpy()
 
 
 class _Sums:
@@ -173,12 +218,12 @@ def _n_eff(sum_w2):
     return 1.0 / sum_w2 if sum_w2 != 0.0 else float("inf")
 
 
-def pdf_update_batch(obe, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None):
+def pdf_update_batch(obe, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None, **side):
     from .obe_base import _LazyState
     tempered, max_stages = check_batch_arguments(tempered, max_stages, on_stage)
     refuse_host_model(obe)
     kappa = check_choke(obe.choke)
-    stacked, n_s, has_sigma = _records_on_device(obe, settings, y_meas, sigma)
+    records = _records_of(obe, settings, y_meas, sigma, side)
     # it behaves like an update: a sweep enqueued ahead reads the weights this call changes
     obe._drop_speculative_sweep()
     obe._await_host_moments()
@@ -206,7 +251,7 @@ def pdf_update_batch(obe, settings, y_meas, sigma=None, tempered=True, max_stage
                           resamples=report["resamples"], log_evidence=report["log_evidence"]))
 
     while True:
-        sums.loglik = loglik = _loglik_device(obe, stacked, n_s, has_sigma)      # (of the cloud as it is now)
+        sums.loglik = loglik = records.loglik()       # (of the cloud as it is now)
         delta_max = 1.0 - beta
         last = not tempered
         if tempered and len(report["stages"]) + 1 >= max_stages:

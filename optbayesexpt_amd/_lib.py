@@ -147,7 +147,10 @@ MODEL_ENTRY_POINTS = ("obe_model_validate", "obe_workspace_bytes", "obe_sweep_se
                       "obe_output_cross_covariance_workspace_bytes", "obe_output_cross_covariance",
                       "obe_signal_noise_likelihood", "obe_signal_noise_workspace_bytes", "obe_signal_noise_variance",
                       "obe_binomial_likelihood", "obe_binomial_workspace_bytes", "obe_binomial_information",
-                      "obe_poisson_likelihood", "obe_poisson_workspace_bytes", "obe_poisson_information")
+                      "obe_poisson_likelihood", "obe_poisson_workspace_bytes", "obe_poisson_information",
+                      "obe_signal_noise_records_loglik_workspace_bytes", "obe_signal_noise_records_loglik",
+                      "obe_binomial_records_loglik_workspace_bytes", "obe_binomial_records_loglik",
+                      "obe_poisson_records_loglik_workspace_bytes", "obe_poisson_records_loglik")
 
 
 class HipLib:

@@ -2,15 +2,68 @@
 variance are the object's own passes over the cloud (csrc/obe_cloud_pass.h), not the base class's Gaussian with a given
 sigma.  Each class keeps its argument checks, its ``state_fields`` / ``kwargs_from_state`` and the calls of its own
 entry points; ``_state.OWN_NOISE`` lists their modules."""
+import math
+
 import numpy as np
 import torch
 
-from . import _lib
+from . import _batch, _lib
+from ._scoring import _numbers, check_records
 from .models import DeviceModel
 from .obe_base import OptBayesExpt, _LazyState, _overridden
 from .particlepdf import _ptr
 
 INFORMATION = "mutual_information"
+
+
+# ---------------------------------------------------------------------------------------- argument checks (host)
+def check_side(name, value, n_channels):
+    """``(C, 1)`` or ``(C, n_r)`` float64 of a record's side data (``shots``, ``exposure``) from a scalar, ``(C,)``
+    (for one channel also ``(n_r,)``) or ``(C, n_r)``, as ``_scoring.check_sigma`` reads a sigma; the values are the
+    class's to check."""
+    a = _numbers(value, name)
+    if a.ndim == 0:
+        a = np.full((n_channels, 1), float(a))
+    elif a.ndim == 1 and n_channels == 1:
+        a = a.reshape(1, -1)
+    elif a.ndim == 1:
+        if a.size != n_channels:
+            raise ValueError(f"the model has {n_channels} channels, {name} has {a.size} values")
+        a = a.reshape(n_channels, 1)
+    elif a.shape[0] != n_channels:
+        raise ValueError(f"the model has {n_channels} channels, {name} has {a.shape[0]} rows")
+    if a.shape[1] == 0:
+        raise ValueError(f"{name} must hold at least one value")
+    return a
+
+
+def check_own_records(settings, y_meas, name, side, n_setdims, n_channels):
+    """``(x (n_setdims, n_r), readings (C, n_r), side (C, n_r) or None)``, everything broadcast to one ``n_r``:
+    ``_scoring.check_records`` for the settings and the readings, ``check_side`` for ``side`` (None: the class has
+    none)."""
+    x, y, _, _ = check_records(settings, y_meas, None, n_setdims, n_channels, True)
+    if side is None:
+        return x, y, None
+    b = check_side(name, side, n_channels)
+    lengths = {x.shape[1], b.shape[1]} - {1}
+    if len(lengths) > 1:
+        raise ValueError(f"settings, y_meas and {name} do not broadcast to one number of records: {sorted(lengths)}")
+    n_r = lengths.pop() if lengths else 1
+
+    def wide(a):
+        return np.ascontiguousarray(np.broadcast_to(a, (a.shape[0], n_r)))
+    return wide(x), wide(y), wide(b)
+
+
+def lgamma_plus_one(a):
+    """``lgamma(a + 1)`` of every element (``math.lgamma``, once per distinct value): log a! of whole numbers."""
+    values, inverse = np.unique(a, return_inverse=True)
+    return np.array([math.lgamma(v + 1.0) for v in values])[inverse].reshape(np.shape(a))
+
+
+def tile_sums(terms):
+    """``constants(begin, end)`` of ``_batch.OwnRecords``: ``math.fsum`` of the (C, n_r) terms of those records."""
+    return lambda begin, end: math.fsum(terms[:, begin:end].ravel().tolist())
 
 
 class OwnCloudPasses(OptBayesExpt):
@@ -137,11 +190,30 @@ class OwnCloudPasses(OptBayesExpt):
     def reading_interval(self, level=0.95, settings=None, sigma=None, max_passes=48, full_output=False):
         self._refuse("reading_interval")
 
+    # -- a recorded data set in one call: the class's own l through the base class's engine (_batch.py) --------------
+    def _batch_records(self, settings, y_meas, sigma, **side):
+        """``_batch.OwnRecords`` of the checked records: a class gives ``_own_records(settings, y_meas, **side)``.  (A
+        ``sigma`` never gets here: the noise is the object's own.)"""
+        return self._own_records(settings, y_meas, **side)
+
+    def _no_record_sigma(self, name, sigma):
+        if sigma is not None:
+            self._refuse(name)
+
     def records_loglik(self, settings, y_meas, sigma=None):
-        self._refuse("records_loglik")
+        """``(N_p,)`` float64: per particle the joint log density of the records under the class's own likelihood (its
+        docstring), the particle-independent constant included; for every particle, whatever its weight.  NaN where a
+        particle has a model value the likelihood does not take, -inf where a record is impossible for it.  ``sigma``
+        must stay None.  Changes nothing of the object."""
+        self._no_record_sigma("records_loglik", sigma)
+        return _batch.records_loglik(self, settings, y_meas)
 
     def pdf_update_batch(self, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None):
-        self._refuse("pdf_update_batch")
+        """``OptBayesExpt.pdf_update_batch()`` with the class's own likelihood: the same stages, resamples, constraints
+        and ``last_batch_update``; ``log_evidence`` is the log of the probability (density) of the records, constants
+        included, and so comparable between models.  ``sigma`` must stay None.  No drift step is taken."""
+        self._no_record_sigma("pdf_update_batch", sigma)
+        return _batch.pdf_update_batch(self, settings, y_meas, None, tempered, max_stages, on_stage)
 
 
 class CountReadings(OwnCloudPasses):

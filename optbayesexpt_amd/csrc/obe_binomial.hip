@@ -11,9 +11,13 @@
 //                w sum_c h2, C sums of w p (1 - p) — the variance of a shot, what the Gaussian utilities divide by —
 //                and W.  No atomics: the same bits from run to run.  FP64-issue bound (C log and C log1p per
 //                evaluation).
+//   records      K19: l_i = sum_r sum_c [k log p + (n - k) log1p(-p)] + constant over a set of records, per particle:
+//                the records x particles pass of obe_records_pass.h with BinRecordTerm below.  Per evaluation and
+//                channel a log and a log1p, either skipped where its count is 0.  FP64-issue bound.
 #include <cmath>
 
 #include "obe_cloud_pass.h"
+#include "obe_records_pass.h"
 
 namespace obe {
 namespace {
@@ -140,7 +144,25 @@ __global__ __launch_bounds__(kBlock) void binomial_fold_kernel(const double* __r
 }
 
 // a count of a record: finite and integer-valued
-inline bool is_count(double v) { return v - v == 0.0 && v == std::floor(v); }      // (inf - inf and NaN - NaN are NaN)
+__host__ __device__ inline bool is_count(double v) { return v - v == 0.0 && v == std::floor(v); }      // (inf - inf and NaN - NaN are NaN)
+
+// K19's term (obe_records_pass.h): w0 = k, w1 = n - k, formed once per record; k log p + (n - k) log1p(-p), a term
+// whose count is 0 skipped (the record is the same for all lanes: a wave-uniform branch).  p = 0 with k > 0 and p = 1
+// with n - k > 0 give -inf; a p that is NaN or outside [0, 1] fails the particle.
+struct BinRecordTerm {
+    static constexpr int kSide = 1, kMaxChannels = kBinMaxCh;
+    struct Coef {};
+    __device__ __forceinline__ static bool pack(double k, double n, double& w0, double& w1) {
+        w0 = k;
+        w1 = n - k;
+        return is_count(k) && is_count(n) && k >= 0.0 && n >= 1.0 && k <= n;
+    }
+    __device__ __forceinline__ static void add(const Coef&, int, double p, double k, double f, double& acc, bool& ok) {
+        ok = ok && is_probability(p);
+        if (k > 0.0) acc += k * log(p);
+        if (f > 0.0) acc += f * log1p(-p);
+    }
+};
 
 }  // namespace
 }  // namespace obe
@@ -231,6 +253,19 @@ int obe_binomial_information(const obe_model* m, const double* d_settings, int64
             return 0;
         }
     });
+}
+
+int64_t obe_binomial_records_loglik_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels) {
+    return records_pass_bytes(n_particles, n_records, n_channels);
+}
+
+int obe_binomial_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                                const double* d_successes, int64_t ld_k, const double* d_shots, int64_t ld_n,
+                                double constant, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                                int32_t accumulate, double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream) {
+    return own_records_loglik<BinRecordTerm>("obe_binomial_records_loglik", m, d_settings, ld_s, n_records, d_successes,
+                                             ld_k, d_shots, ld_n, BinRecordTerm::Coef{}, constant, d_particles, ld_p,
+                                             n_particles, accumulate, d_loglik, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

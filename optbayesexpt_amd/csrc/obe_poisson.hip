@@ -13,11 +13,15 @@
 //                registers —, one log tau.  CAP = 0: the instantiation without outcome sums, for any channel count,
 //                which gives sum w r_c and W alone (the noise variance of the reading k / t).  No atomics: the same bits
 //                from run to run.  FP64-issue bound (5 FP64 operations per outcome and evaluation).
+//   records      K19: l_i = sum_r sum_c [k log lambda - lambda] + constant over a set of records, per particle: the
+//                records x particles pass of obe_records_pass.h with PoisRecordTerm below.  Per evaluation and channel
+//                one log, none where the count is 0.  FP64-issue bound.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 
 #include "obe_cloud_pass.h"
+#include "obe_records_pass.h"
 
 namespace obe {
 namespace {
@@ -212,8 +216,27 @@ __global__ __launch_bounds__(kBlock) void poisson_fold_kernel(const double* __re
 }
 
 // a count of a record: finite, integer-valued and >= 0
-inline bool is_count(double v) { return v - v == 0.0 && v == std::floor(v) && v >= 0.0; }     // (inf - inf is NaN)
-inline bool is_exposure(double t) { return t > 0.0 && t < kInf; }
+__host__ __device__ inline bool is_count(double v) { return v - v == 0.0 && v == std::floor(v) && v >= 0.0; }     // (inf - inf is NaN)
+__host__ __device__ inline bool is_exposure(double t) { return t > 0.0 && t < kInf; }
+
+// K19's term (obe_records_pass.h): w0 = k, w1 = t; k log lambda - lambda with lambda = t r, a channel whose count is 0
+// contributing -lambda alone (the record is the same for all lanes: a wave-uniform branch).  lambda = 0 with k > 0
+// gives -inf; an r that is not a rate fails the particle.
+struct PoisRecordTerm {
+    static constexpr int kSide = 1, kMaxChannels = OBE_MAX_CHANNELS;
+    struct Coef {};
+    __device__ __forceinline__ static bool pack(double k, double t, double& w0, double& w1) {
+        w0 = k;
+        w1 = t;
+        return is_count(k) && is_exposure(t);
+    }
+    __device__ __forceinline__ static void add(const Coef&, int, double r, double k, double t, double& acc, bool& ok) {
+        ok = ok && is_rate(r, t);
+        const double lam = t * r;
+        if (k > 0.0) acc += k * log(lam);
+        acc -= lam;
+    }
+};
 
 }  // namespace
 }  // namespace obe
@@ -317,6 +340,19 @@ int obe_poisson_information(const obe_model* m, const double* d_settings, int64_
         OBE_CHECK_LAUNCH("poisson_fold_kernel");
         return 0;
     });
+}
+
+int64_t obe_poisson_records_loglik_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels) {
+    return records_pass_bytes(n_particles, n_records, n_channels);
+}
+
+int obe_poisson_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                               const double* d_counts, int64_t ld_k, const double* d_exposure, int64_t ld_t,
+                               double constant, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                               int32_t accumulate, double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream) {
+    return own_records_loglik<PoisRecordTerm>("obe_poisson_records_loglik", m, d_settings, ld_s, n_records, d_counts,
+                                              ld_k, d_exposure, ld_t, PoisRecordTerm::Coef{}, constant, d_particles,
+                                              ld_p, n_particles, accumulate, d_loglik, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

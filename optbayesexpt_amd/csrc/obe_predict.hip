@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "obe_models.h"
+#include "obe_records_pass.h"
 #include "obe_select.h"
 
 namespace obe {
@@ -842,19 +843,11 @@ __global__ __launch_bounds__(kBlock) void predict_cov_fold_kernel(const double* 
 
 // ---- K13a: the joint log-likelihood of a set of records, per particle.  Lane = one particle, its rows in registers;
 // the chunk's records one after the other from the packed table (the same record for all lanes: scalar loads).
-constexpr int kRecMinChunk = 32;                   // records per chunk at least
+static_assert(kRecWaves == kMomentWaves, "the records pass aims at the waves of the moments");
 
 // words of one record of the table: the setting point, the reading and, known sigma, 1 / sigma per channel
 template <class M, bool ROWS>
 constexpr int rec_words() { return M::NS + M::NC + (ROWS ? 0 : M::NC); }
-inline int rec_words_bound(int n_channels) { return OBE_MAX_SETDIMS + 2 * n_channels; }
-
-inline int64_t particle_tiles(int64_t n_particles) { return (n_particles + kWave - 1) / kWave; }
-inline int record_chunks(int64_t n_records, int64_t n_particles) {
-    const int64_t by_size = (n_records + kRecMinChunk - 1) / kRecMinChunk;
-    const int64_t by_grid = std::max<int64_t>(1, kMomentWaves / particle_tiles(n_particles));
-    return (int)std::max<int64_t>(1, std::min(by_size, by_grid));
-}
 
 // table (n_records, rec_words) and chunk_log[chunk] = sum over the chunk's records and channels of log sigma (NaN if
 // one of them is not > 0; ROWS: not written).  One workgroup per chunk; the block sum has a fixed order.
@@ -888,17 +881,6 @@ __global__ __launch_bounds__(kBlock) void records_pack_kernel(const double* __re
         if (threadIdx.x == 0) chunk_log[blockIdx.x] = s;
     }
 }
-
-// A particle's rows held in registers behind the interface of ParamRef: M::eval reads th(i) with constant i
-template <class M>
-struct HeldParticle {
-    double v[M::NREAD];
-    __device__ __forceinline__ void load(const double* __restrict__ particles, int64_t ld_p, int64_t p) {
-#pragma unroll
-        for (int k = 0; k < M::NREAD; ++k) v[k] = particles[(int64_t)k * ld_p + p];
-    }
-    __device__ __forceinline__ ParamRef ref() const { return ParamRef{v, 1}; }
-};
 
 // partials (chunk, padded particles): -q / 2 - sum log sigma over the chunk's records, q = sum_r sum_c z_rc^2 in record
 // order; NaN where the particle contributes nothing
@@ -935,18 +917,6 @@ __global__ __launch_bounds__(kWave) void records_loglik_kernel(obe_model m, cons
     double l = -0.5 * q - logs;
     if (!ok || !(q < kInf)) l = __builtin_nan("");               // (a NaN or +-inf model output leaves q NaN or +inf)
     partials[(int64_t)blockIdx.y * ((int64_t)gridDim.x * kWave) + i] = l;
-}
-
-// d_loglik (n,) [+]= (the chunk partials, added in chunk order) - n_records (C / 2) log 2 pi
-__global__ __launch_bounds__(kBlock) void records_fold_kernel(const double* __restrict__ partials, int chunks, int64_t n_pad,
-                                                              int64_t n, double constant, int accumulate,
-                                                              double* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    double acc = 0.0;
-    for (int j = 0; j < chunks; ++j) acc += partials[(int64_t)j * n_pad + i];
-    acc -= constant;
-    out[i] = accumulate ? out[i] + acc : acc;
 }
 
 // ---- K14: output-output covariance.  Row r = pivot j * C + channel c' of the call's pivots, R = the rows padded to 1, 4
@@ -1279,14 +1249,9 @@ int obe_predictive_quantiles(const obe_model* m, const double* d_settings, int64
     });
 }
 
-// the table, the chunks' sum log sigma, the chunk partials: chunks x padded particles <= kMomentWaves x 64 + the padded
-// particles, whatever the number of records
+// (records_pass_bytes, obe_records_pass.h: the table, the chunks' sum log sigma, the chunk partials)
 int64_t obe_records_loglik_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels) {
-    if (n_particles < 1) n_particles = 1;
-    if (n_records < 1) n_records = 1;
-    n_channels = std::min(std::max(n_channels, 1), OBE_MAX_CHANNELS);
-    return (n_records * rec_words_bound(n_channels) + kMomentWaves
-            + ((int64_t)kMomentWaves + particle_tiles(n_particles)) * kWave) * (int64_t)sizeof(double);
+    return records_pass_bytes(n_particles, n_records, n_channels);
 }
 
 int obe_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
@@ -1317,7 +1282,7 @@ int obe_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_
     hipStream_t st = as_stream(stream);
     double* table = static_cast<double*>(d_ws);
     double* chunk_log = table + n_records * rec_words_bound(mm.n_channels);
-    double* partials = chunk_log + kMomentWaves;
+    double* partials = chunk_log + kRecWaves;
     return dispatch_model(mm, [&](auto M) -> int {
         using Model = decltype(M);
         const dim3 grid((unsigned)tiles, (unsigned)used);

@@ -11,7 +11,11 @@
 //               scalar loads), grid = setting tiles x particle chunks, chunk partials folded in chunk order.  ONE pass:
 //               both sums are sums of non-negative terms and need no centring; W rides along.  No atomics: the same
 //               bits from run to run.  FP64-issue bound, like its sibling.
+//   records     K19: l_i = sum_r sum_c [-(f - y)^2 / (2 nu) - log(nu) / 2] + constant over a set of records, per particle:
+//               the records x particles pass of obe_records_pass.h with NoiseRecordTerm below.  Per evaluation and
+//               channel one division and one log.  FP64-issue bound.
 #include "obe_cloud_pass.h"
+#include "obe_records_pass.h"
 
 namespace obe {
 namespace {
@@ -65,6 +69,24 @@ __global__ __launch_bounds__(kBlock) void signal_noise_lik_kernel(obe_model m, L
         lik[p] = l;
     }
 }
+
+// K19's term (obe_records_pass.h): w0 = the reading; -(f - y)^2 / (2 nu) - log(nu) / 2 with nu at the particle's own f.
+// A nu that is not > 0 or not finite (a NaN or +-inf model output lands here) fails the particle.
+struct NoiseRecordTerm {
+    static constexpr int kSide = 0, kMaxChannels = OBE_MAX_CHANNELS;
+    using Coef = NoiseCoef;
+    __device__ __forceinline__ static bool pack(double y, double, double& w0, double&) {
+        w0 = y;
+        return true;
+    }
+    __device__ __forceinline__ static void add(const Coef& k, int c, double f, double y, double, double& acc, bool& ok) {
+        const double nu = nu_of(k, c, f);
+        ok = ok && nu > 0.0 && nu < kInf;                        // (NaN fails)
+        const double d = f - y;
+        acc -= (d * d) / (2.0 * nu);
+        acc -= 0.5 * log(nu);
+    }
+};
 
 // a lane's sums, nu_slots(C) of them: per channel sum w |y| and sum w y^2 over the chunk, then the chunk's W
 template <int C>
@@ -196,6 +218,24 @@ int obe_signal_noise_variance(const obe_model* m, const double* d_settings, int6
         OBE_CHECK_LAUNCH("signal_noise_fold_kernel");
         return 0;
     });
+}
+
+int64_t obe_signal_noise_records_loglik_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels) {
+    return records_pass_bytes(n_particles, n_records, n_channels);
+}
+
+int obe_signal_noise_records_loglik(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                                    const double* d_y_meas, int64_t ld_y, const double* h_noise_coef, double constant,
+                                    const double* d_particles, int64_t ld_p, int64_t n_particles, int32_t accumulate,
+                                    double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!m) return bad_arg("obe_signal_noise_records_loglik: null pointer");
+    obe_model mm = *m;
+    if (int rc = obe_model_validate(&mm)) return rc;
+    NoiseCoef k;
+    if (int rc = fill_noise_coef("obe_signal_noise_records_loglik", k, h_noise_coef, mm.n_channels)) return rc;
+    return own_records_loglik<NoiseRecordTerm>("obe_signal_noise_records_loglik", m, d_settings, ld_s, n_records,
+                                               d_y_meas, ld_y, nullptr, 0, k, constant, d_particles, ld_p, n_particles,
+                                               accumulate, d_loglik, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -496,6 +496,11 @@ class OptBayesExpt(ParticlePDF):
         output that is not finite).  Changes nothing of the object."""
         return _batch.records_loglik(self, settings, y_meas, sigma)
 
+    def _batch_records(self, settings, y_meas, sigma):
+        """What a batch update reads its records through (_batch.py): they go to the device once, ``loglik()`` is l of
+        the cloud as it is then.  A class whose likelihood is its own returns its own."""
+        return _batch.GaussianRecords(self, settings, y_meas, sigma)
+
     def pdf_update_batch(self, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None):
         """Bayesian update from all the records at once; returns ``(particles, particle_weights)`` as ``pdf_update()``
         does.  ``tempered=False``: one stage, ``w' ~ w exp(kappa l)`` (kappa = ``choke``, or 1), then the ordinary

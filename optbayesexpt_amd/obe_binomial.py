@@ -17,8 +17,8 @@ Gaussian approximation of these counts.  The count checks are plain functions of
 import numpy as np
 import torch
 
-from . import _lib
-from ._ownnoise import INFORMATION, CountReadings
+from . import _batch, _lib
+from ._ownnoise import INFORMATION, CountReadings, check_own_records, lgamma_plus_one, tile_sums
 from .particlepdf import _P, _ptr
 
 MAX_CHANNELS = _lib.OBE_BINOMIAL_MAX_CHANNELS
@@ -78,6 +78,21 @@ def check_counts(successes, shots, n_channels):
     return n_lik, kk, nn
 
 
+def check_count_table(successes, shots):
+    """``check_counts``' rules for every record at once: ``successes`` and ``shots`` (C, n_r), finite and
+    integer-valued with 0 <= k <= n and n >= 1, or ``ValueError``.  Returns ``log C(n, k)`` per record and channel,
+    (C, n_r): what the records bring that no particle changes."""
+    k, n = np.asarray(successes, dtype=np.float64), np.asarray(shots, dtype=np.float64)
+    for name, v in (("the successes of the records", k), ("the shots of the records", n)):
+        if not np.all(np.isfinite(v)) or np.any(v != np.floor(v)):
+            raise ValueError(f"{name} must be finite and integer-valued: the readings are counts")
+    if np.any(n < 1):
+        raise ValueError("the shots of the records must be >= 1")
+    if np.any(k < 0) or np.any(k > n):
+        raise ValueError("the successes of the records must lie in 0..shots")
+    return lgamma_plus_one(n) - lgamma_plus_one(k) - lgamma_plus_one(n - k)
+
+
 def state_fields(obj):
     """What a snapshot keeps of this class besides the base class's (_state.py): ``shots``."""
     return {"shots": np.array(obj.shots, dtype=np.float64)}
@@ -98,10 +113,12 @@ class OptBayesExptBinomial(CountReadings):
     SHOT, whatever ``shots`` is) or any name the base class knows, which then works on the Gaussian approximation
     ``yvar_noise_model()`` gives.  ``pdf_update((setting, k))`` or ``((setting, k, n))``; ``likelihood()``:
     ``L_i = exp(sum_c [k_c log p_c,i + (n_c - k_c) log1p(-p_c,i)])``, 0 for a particle with a probability that is NaN
-    or outside [0, 1].  The summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``."""
+    or outside [0, 1].  ``records_loglik()`` and ``pdf_update_batch()`` take a recorded table of clicks at once.  The
+    summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``."""
     _NOISE_FROM = "shots"
     _REFUSAL = ("takes readings with a Gaussian sigma per record, but this object's readings are counts (k successes "
-                "in n shots): count-aware scoring, reading bands and batch assimilation are not built")
+                "in n shots): count-aware scoring and reading bands are not built (records_loglik() and "
+                "pdf_update_batch() take the records without sigma)")
 
     def __init__(self, measurement_model, setting_values, parameter_samples, constants, shots=1,
                  utility_method=INFORMATION, **kwargs):
@@ -119,6 +136,31 @@ class OptBayesExptBinomial(CountReadings):
         shots = check_shots(self.shots, self.n_channels) if given is None else given
         n, kk, nn = check_counts(measurement_record[1], shots, self.n_channels)
         return self._likelihood_call("obe_binomial_likelihood", y_model, measurement_record[0], (kk, nn), n)
+
+    # -- a recorded data set in one call ---------------------------------------------------
+    def _own_records(self, settings, y_meas, shots=None):
+        """The records of ``records_loglik()`` / ``pdf_update_batch()``: successes of all C channels and their shots;
+        ``l`` carries sum log C(n, k), the full log probability."""
+        shots = check_shots(self.shots, self.n_channels) if shots is None else shots
+        x, k, n = check_own_records(settings, y_meas, "shots", shots, self.allsettings.shape[0], self.n_channels)
+        log_binom = check_count_table(k, n)
+        return _batch.OwnRecords(self, "obe_binomial_records_loglik", np.vstack([x, k, n]), x.shape[0], True,
+                                 tile_sums(log_binom))
+
+    def records_loglik(self, settings, y_meas, sigma=None, *, shots=None):
+        """``(N_p,)`` float64: ``l_i = sum_r sum_c [k log p + (n - k) log1p(-p) + log C(n, k)]``, the log probability of
+        the recorded successes ``y_meas`` (all C channels) per particle, whatever its weight.  ``shots``: None (the
+        object's ``shots``), a scalar, ``(C,)``, ``(C, n_r)`` or for one channel ``(n_r,)``.  NaN where a probability
+        is NaN or outside [0, 1], -inf where a record is impossible.  ``sigma`` must stay None."""
+        self._no_record_sigma("records_loglik", sigma)
+        return _batch.records_loglik(self, settings, y_meas, shots=shots)
+
+    def pdf_update_batch(self, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None, *, shots=None):
+        """``OptBayesExpt.pdf_update_batch()`` with the binomial likelihood of the recorded successes; ``shots`` as
+        ``records_loglik()`` takes it.  ``last_batch_update["log_evidence"]`` is the log probability of the records,
+        binomial coefficients included.  ``sigma`` must stay None."""
+        self._no_record_sigma("pdf_update_batch", sigma)
+        return _batch.pdf_update_batch(self, settings, y_meas, None, tempered, max_stages, on_stage, shots=shots)
 
     # -- one pass over settings x particles: the information and the variance of a shot --
     def _pass(self, begin, end, want_information):

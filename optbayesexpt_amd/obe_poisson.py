@@ -21,8 +21,8 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
-from ._ownnoise import INFORMATION, CountReadings
+from . import _batch, _lib
+from ._ownnoise import INFORMATION, CountReadings, check_own_records, lgamma_plus_one, tile_sums
 from .particlepdf import _P, _ptr
 
 MAX_CHANNELS = _lib.OBE_MAX_CHANNELS
@@ -82,6 +82,18 @@ def check_record_counts(counts, exposure, n_channels):
     return n_lik, kk, tt, lf
 
 
+def check_count_table(counts, exposure):
+    """``check_record_counts``' rules for every record at once: ``counts`` (C, n_r) whole numbers >= 0, ``exposure``
+    (C, n_r) finite and > 0, or ``ValueError``.  Returns ``-log k!`` per record and channel, (C, n_r): what the records
+    bring that no particle changes."""
+    k, t = np.asarray(counts, dtype=np.float64), np.asarray(exposure, dtype=np.float64)
+    if not np.all(np.isfinite(k)) or np.any(k != np.floor(k)) or np.any(k < 0):
+        raise ValueError("the counts of the records must be whole numbers >= 0: the readings are counted events")
+    if not np.all(np.isfinite(t)) or np.any(t <= 0):
+        raise ValueError("the exposure of the records must be finite and > 0")
+    return -lgamma_plus_one(k)
+
+
 def state_fields(obj):
     """What a snapshot keeps of this class besides the base class's (_state.py): ``exposure`` and ``count_cap``."""
     return {"exposure": np.array(obj.exposure, dtype=np.float64), "count_cap": int(obj.count_cap)}
@@ -104,10 +116,12 @@ class OptBayesExptPoisson(CountReadings):
     ``L_i = exp(sum_c [k_c log lambda_c,i - lambda_c,i - log k_c!])``, ``lambda = t r``, 0 for a particle with a rate that
     is NaN, negative or infinite.  ``last_information`` holds ``{"cap", "tail_max"}`` of the last information pass:
     ``tail_max``, the largest mass of the outcome ">= cap" over this rank's settings, says whether ``count_cap`` is large
-    enough for the rates.  The summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``."""
+    enough for the rates.  ``records_loglik()`` and ``pdf_update_batch()`` take a recorded spectrum of counts at once.
+    The summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``."""
     _NOISE_FROM = "exposure"
     _REFUSAL = ("takes readings with a Gaussian sigma per record, but this object's readings are counts (k events in "
-                "an exposure t): count-aware scoring, reading bands and batch assimilation are not built")
+                "an exposure t): count-aware scoring and reading bands are not built (records_loglik() and "
+                "pdf_update_batch() take the records without sigma)")
 
     def __init__(self, measurement_model, setting_values, parameter_samples, constants, exposure=1.0, count_cap=32,
                  utility_method=INFORMATION, **kwargs):
@@ -131,6 +145,32 @@ class OptBayesExptPoisson(CountReadings):
         exposure = check_exposure(self.exposure, self.n_channels) if given is None else given
         n, kk, tt, lf = check_record_counts(measurement_record[1], exposure, self.n_channels)
         return self._likelihood_call("obe_poisson_likelihood", y_model, measurement_record[0], (kk, tt, lf), n)
+
+    # -- a recorded data set in one call ---------------------------------------------------
+    def _own_records(self, settings, y_meas, exposure=None):
+        """The records of ``records_loglik()`` / ``pdf_update_batch()``: counts of all C channels and their exposures;
+        ``l`` carries -sum log k!, the full log probability."""
+        exposure = check_exposure(self.exposure, self.n_channels) if exposure is None else exposure
+        x, k, t = check_own_records(settings, y_meas, "exposure", exposure, self.allsettings.shape[0], self.n_channels)
+        neg_log_fact = check_count_table(k, t)
+        return _batch.OwnRecords(self, "obe_poisson_records_loglik", np.vstack([x, k, t]), x.shape[0], True,
+                                 tile_sums(neg_log_fact))
+
+    def records_loglik(self, settings, y_meas, sigma=None, *, exposure=None):
+        """``(N_p,)`` float64: ``l_i = sum_r sum_c [k log lambda - lambda - log k!]``, ``lambda = t r``, the log
+        probability of the recorded counts ``y_meas`` (all C channels) per particle, whatever its weight.
+        ``exposure``: None (the object's ``exposure``), a scalar, ``(C,)``, ``(C, n_r)`` or for one channel ``(n_r,)``.
+        NaN where a rate is NaN, negative or infinite, -inf where a record is impossible.  ``sigma`` must stay None."""
+        self._no_record_sigma("records_loglik", sigma)
+        return _batch.records_loglik(self, settings, y_meas, exposure=exposure)
+
+    def pdf_update_batch(self, settings, y_meas, sigma=None, tempered=True, max_stages=64, on_stage=None, *,
+                         exposure=None):
+        """``OptBayesExpt.pdf_update_batch()`` with the Poisson likelihood of the recorded counts; ``exposure`` as
+        ``records_loglik()`` takes it.  ``last_batch_update["log_evidence"]`` is the log probability of the records,
+        ``-log k!`` included: comparable between models of the same counts.  ``sigma`` must stay None."""
+        self._no_record_sigma("pdf_update_batch", sigma)
+        return _batch.pdf_update_batch(self, settings, y_meas, None, tempered, max_stages, on_stage, exposure=exposure)
 
     # -- one pass over settings x particles ----------------------------------------------
     def _call(self, x, ld_s, n, exposure, cost_t, cost_s, info, tail, pmf, nu):

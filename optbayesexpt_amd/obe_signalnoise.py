@@ -13,11 +13,13 @@ multiplicative noise fraction).  The likelihood takes nu at every particle's own
 by its average over the whole weighted cloud, per setting: one more settings x particles pass that never leaves the
 chip (csrc/obe_signal_noise.hip).  The coefficient checks are plain functions of this module (no device needed).
 """
+import math
+
 import numpy as np
 import torch
 
-from . import _lib
-from ._ownnoise import OwnCloudPasses
+from . import _batch, _lib
+from ._ownnoise import OwnCloudPasses, check_own_records
 from .particlepdf import _P, _ptr
 
 _FIELDS = ("noise_floor", "noise_gain", "noise_relative")
@@ -72,8 +74,9 @@ class OptBayesExptSignalNoise(OwnCloudPasses):
     ``likelihood()``: ``L_i = prod_c exp(-(y_c,i - y_meas,c)^2 / (2 nu_c(y_c,i))) / sqrt(nu_c(y_c,i))``.  The summaries
     that take a per-record ``sigma`` do not know ``nu(y)`` yet and raise ``NotImplementedError``."""
     _PASS_SUMS = "the noise is averaged"
-    _REFUSAL = ("takes a fixed sigma per record, but this object's noise depends on the signal: these summaries do not "
-                "know nu(y) yet, and a fixed sigma would contradict the object's own likelihood")
+    _REFUSAL = ("takes a fixed sigma per record, but this object's noise depends on the signal: the predictive "
+                "summaries do not know nu(y) yet, and a fixed sigma would contradict the object's own likelihood "
+                "(records_loglik() and pdf_update_batch() take the records without sigma)")
 
     def __init__(self, measurement_model, setting_values, parameter_samples, constants,
                  noise_floor=0.0, noise_gain=1.0, noise_relative=0.0, **kwargs):
@@ -92,6 +95,14 @@ class OptBayesExptSignalNoise(OwnCloudPasses):
         n, yy, _ = self._record_channels(measurement_record[1], None)
         return self._likelihood_call("obe_signal_noise_likelihood", y_model, measurement_record[0],
                                      (yy, self._coefficients()), n)
+
+    def _own_records(self, settings, y_meas):
+        """The records of ``records_loglik()`` / ``pdf_update_batch()``: readings of all C channels, nu at every
+        particle's own model value; ``l`` carries -R C log(2 pi) / 2, the full log density."""
+        x, y, _ = check_own_records(settings, y_meas, None, None, self.allsettings.shape[0], self.n_channels)
+        per_record = -0.5 * self.n_channels * math.log(2.0 * math.pi)
+        return _batch.OwnRecords(self, "obe_signal_noise_records_loglik", np.vstack([x, y]), x.shape[0], False,
+                                 lambda begin, end: (end - begin) * per_record, (self._coefficients(),))
 
     def _noise_variance(self, begin, end):
         """Device ``(C, end - begin)``: nu_bar of the settings [begin, end) of the design grid, cached until the
