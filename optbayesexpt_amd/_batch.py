@@ -15,9 +15,10 @@ import math
 import warnings
 
 import numpy as np
+import torch
 
 from . import _lib
-from ._predictive import _column_tiles, _device_model, _ptr
+from ._devcall import column_tiles, model_call, ptr as _ptr
 from ._scoring import _noise_rows, check_records
 
 RECORDS_PER_CALL = 1 << 16                     # records one library call is given
@@ -104,7 +105,6 @@ class GaussianRecords:
     _ownnoise.py bring their own (``OwnRecords``)."""
 
     def __init__(self, obe, settings, y_meas, sigma):
-        import torch
         rows = _noise_rows(obe)
         x, y, s, _ = check_records(settings, y_meas, sigma, obe.allsettings.shape[0], obe.n_channels, rows)
         self.obe = obe
@@ -115,22 +115,19 @@ class GaussianRecords:
     def loglik(self):
         """Tiled by RECORDS_PER_CALL per library call (later tiles are added, in tile order); a workspace of its
         own."""
-        import torch
         obe, n_s = self.obe, self.n_s
         rows = None if self.has_sigma else _noise_rows(obe)
         n_c = obe.n_channels
         p = obe._parameters.tensor()                # (host edits of the cloud are uploaded here)
         n_p = p.shape[1]
         out = torch.empty(n_p, dtype=torch.float64, device=obe._device)
-        for start, part in _column_tiles(self.stacked, RECORDS_PER_CALL):
+        for start, part in column_tiles(self.stacked, RECORDS_PER_CALL):
             n = part.shape[1]
             d_x, d_y = part[:n_s], part[n_s:n_s + n_c]
             d_s = _ptr(part[n_s + n_c:]) if self.has_sigma else None
-            nbytes = int(obe._mlib.cdll.obe_records_loglik_workspace_bytes(n_p, n, n_c))
-            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=obe._device)
-            obe._mlib.call("obe_records_loglik", obe._model_struct, _ptr(d_x), n, n, _ptr(d_y), n, d_s, n,
-                           None if rows is None else _lib.host_ptr(rows), _ptr(p), n_p, n_p, 1 if start else 0,
-                           _ptr(out), _ptr(ws), nbytes, obe._stream())
+            model_call(obe, "obe_records_loglik", "obe_records_loglik_workspace_bytes", (n_p, n, n_c),
+                       _ptr(d_x), n, n, _ptr(d_y), n, d_s, n, None if rows is None else _lib.host_ptr(rows),
+                       _ptr(p), n_p, n_p, 1 if start else 0, _ptr(out))
         return out
 
 
@@ -141,26 +138,22 @@ class OwnRecords:
     between the reading's stride and ``constant`` (``side_rows`` True: the side data's address and stride instead)."""
 
     def __init__(self, obe, entry, rows, n_setdims, side_rows, constants, extra=()):
-        import torch
         self.obe, self.entry, self.n_s, self.side_rows = obe, entry, n_setdims, side_rows
         self.stacked = torch.from_numpy(np.ascontiguousarray(rows)).to(obe._device)
         self.constants, self.extra = constants, tuple(extra)
 
     def loglik(self):
-        import torch
         obe, n_s, n_c = self.obe, self.n_s, self.obe.n_channels
         p = obe._parameters.tensor()                # (host edits of the cloud are uploaded here)
         n_p = p.shape[1]
         out = torch.empty(n_p, dtype=torch.float64, device=obe._device)
-        size = getattr(obe._mlib.cdll, self.entry + "_workspace_bytes")
-        for start, part in _column_tiles(self.stacked, RECORDS_PER_CALL):
+        for start, part in column_tiles(self.stacked, RECORDS_PER_CALL):
             n = part.shape[1]
             side = (_ptr(part[n_s + n_c:]), n) if self.side_rows else ()
-            nbytes = int(size(n_p, n, n_c))
-            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=obe._device)
-            obe._mlib.call(self.entry, obe._model_struct, _ptr(part[:n_s]), n, n, _ptr(part[n_s:n_s + n_c]), n, *side,
-                           *[_lib.host_ptr(a) for a in self.extra], float(self.constants(start, start + n)), _ptr(p),
-                           n_p, n_p, 1 if start else 0, _ptr(out), _ptr(ws), nbytes, obe._stream())
+            model_call(obe, self.entry, self.entry + "_workspace_bytes", (n_p, n, n_c),
+                       _ptr(part[:n_s]), n, n, _ptr(part[n_s:n_s + n_c]), n, *side,
+                       *[_lib.host_ptr(a) for a in self.extra], float(self.constants(start, start + n)), _ptr(p),
+                       n_p, n_p, 1 if start else 0, _ptr(out))
         return out
 
 
@@ -182,7 +175,6 @@ class _Sums:
     landing zone of the call's own."""
 
     def __init__(self, obe):
-        import torch
         self.obe, self.loglik = obe, None
         self.ws = torch.empty(TEMPERED_WS_BYTES // 8, dtype=torch.float64, device=obe._device)
         self.host = _lib.pinned_array(2 + 2 * TRIALS_PER_PASS)
@@ -204,8 +196,7 @@ class _Sums:
 def _apply_stage(obe, loglik, exponent, shift):
     """w <- normalised(w exp(exponent (l - shift))) through obe_tempered_likelihood + obe_bayes_update_lik; returns
     sum w'^2."""
-    import torch
-    n = loglik.shape[0]
+    n =loglik.shape[0]
     lik = torch.empty(n, dtype=torch.float64, device=obe._device)
     obe._lib.call("obe_tempered_likelihood", _ptr(loglik), n, float(exponent), float(shift), _ptr(lik), obe._stream())
     w = obe._weights.tensor()

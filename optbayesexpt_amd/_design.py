@@ -19,9 +19,11 @@ what is left, ``[sum_d a_d G_d(x | picks) / V_d] / cost``.  The same caveat: exa
 parameters with a Gaussian cloud, a heuristic otherwise, and greedy.
 """
 import numpy as np
+import torch
 
 from . import _interest, _lib, _predictive
-from ._predictive import _column_tiles, _device_model, _inputs, _ptr
+from ._devcall import column_tiles, model_call, ptr as _ptr
+from ._predictive import _device_model, _inputs, moments as _moments
 
 ROWS_PER_CALL = 8                              # obe_output_cross_covariance: rows (pivots x channels) one call serves
 MAX_ROWS = 128                                 # n x C of one batch: the factor store is n C C N_s doubles
@@ -62,11 +64,10 @@ def pivots_per_call(n_channels):
 def _cross(obe, x, pivots, p, w, mean=None):
     """Device ``(n_pivots, C, C, n_x)`` for device settings ``x`` and pivots ``(n_setdims, n_pivots)``; ``mean``: the
     ``(C, n_x)`` mean of ``obe_predictive_moments`` if the caller holds it."""
-    import torch
     n_x, n_p, n_c, dev = x.shape[1], p.shape[1], obe.n_channels, obe._device
     n_piv, per = pivots.shape[1], pivots_per_call(n_c)
     cross = torch.empty((n_piv, n_c, n_c, n_x), dtype=torch.float64, device=dev)
-    for start, part in _column_tiles(x, _predictive.SETTINGS_PER_CALL):
+    for start, part in column_tiles(x, _predictive.SETTINGS_PER_CALL):
         n = part.shape[1]
         given = mean is not None
         d_mean = mean[:, start:start + n].contiguous() if given else torch.empty((n_c, n), dtype=torch.float64, device=dev)
@@ -74,12 +75,9 @@ def _cross(obe, x, pivots, p, w, mean=None):
             tile = pivots[:, j0:j0 + per].contiguous()
             nj = tile.shape[1]
             d_cross = torch.empty((nj, n_c, n_c, n), dtype=torch.float64, device=dev)
-            # (a workspace of the call's own: the object's workspace keeps the record of a sweep enqueued ahead)
-            nbytes = int(obe._mlib.cdll.obe_output_cross_covariance_workspace_bytes(n_p, n, n_c, nj))
-            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=dev)
-            obe._mlib.call("obe_output_cross_covariance", obe._model_struct, _ptr(part), n, n, _ptr(tile), nj, nj, _ptr(p),
-                           n_p, n_p, _ptr(w), _ptr(d_mean), 1 if given or j0 else 0, _ptr(d_cross), _ptr(ws), nbytes,
-                           obe._stream())
+            model_call(obe, "obe_output_cross_covariance", "obe_output_cross_covariance_workspace_bytes",
+                       (n_p, n, n_c, nj), _ptr(part), n, n, _ptr(tile), nj, nj, _ptr(p), n_p, n_p, _ptr(w), _ptr(d_mean),
+                       1 if given or j0 else 0, _ptr(d_cross))
             cross[j0:j0 + nj, :, :, start:start + n] = d_cross
     return cross
 
@@ -87,33 +85,14 @@ def _cross(obe, x, pivots, p, w, mean=None):
 def output_cross_covariance(obe, points, settings=None):
     _device_model(obe)
     pts = check_points(points, obe.allsettings.shape[0])
-    import torch
     x, p, w = _inputs(obe, settings)
     return _cross(obe, x, torch.from_numpy(pts).to(obe._device), p, w).cpu().numpy()
-
-
-def _moments(obe, x, p, w):
-    """Device ``(mean, var)``, each ``(C, n_x)``: ``predict()``'s launches."""
-    import torch
-    n_x, n_p, n_c, dev = x.shape[1], p.shape[1], obe.n_channels, obe._device
-    mean = torch.empty((n_c, n_x), dtype=torch.float64, device=dev)
-    var = torch.empty_like(mean)
-    for start, part in _column_tiles(x, _predictive.SETTINGS_PER_CALL):
-        n = part.shape[1]
-        d_mean, d_var = torch.empty((n_c, n), dtype=torch.float64, device=dev), torch.empty((n_c, n), dtype=torch.float64, device=dev)
-        ws, ws_bytes = _predictive._workspace(obe, n_p, n, 0)
-        obe._mlib.call("obe_predictive_moments", obe._model_struct, _ptr(part), n, n, _ptr(p), n_p, n_p, _ptr(w),
-                       _ptr(d_mean), _ptr(d_var), _ptr(ws), ws_bytes, obe._stream())
-        mean[:, start:start + n] = d_mean
-        var[:, start:start + n] = d_var
-    return mean, var
 
 
 class _Step:
     """The state of one greedy design on the device and the ``obe_design_step`` call on it."""
 
     def __init__(self, obe, cvar, noise_var, cost, max_rows, distinct):
-        import torch
         self.obe, self.cvar, self.n_c, self.n_x = obe, cvar, cvar.shape[0], cvar.shape[1]
         dev = obe._device
         self.nv = torch.from_numpy(np.ascontiguousarray(noise_var)).to(dev)
@@ -199,7 +178,6 @@ class _InterestStep:
     on it."""
 
     def __init__(self, obe, ycov, xcov, pvar, weights, noise_var, cost, max_rows, distinct):
-        import torch
         self.obe, self.ycov, self.xcov, self.pvar = obe, ycov, xcov, pvar
         self.n_sel, self.n_c, self.n_x = xcov.shape
         dev = obe._device

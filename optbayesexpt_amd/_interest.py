@@ -13,9 +13,11 @@ The argument checks are plain functions of this module (no device needed), the c
 ``OptBayesExpt`` has the methods.
 """
 import numpy as np
+import torch
 
 from . import _lib, _predictive
-from ._predictive import _column_tiles, _device_model, _inputs, _ptr
+from ._devcall import column_tiles, model_call, ptr as _ptr
+from ._predictive import _device_model, _inputs
 from ._scoring import check_sigma
 
 ROWS_PER_CALL = 8                              # obe_output_covariance / obe_variance_reduction: rows one call serves
@@ -100,7 +102,6 @@ def unpack_lower(packed, n_channels):
 # ------------------------------------------------------------------------------------------------- device calls
 def _blocks(obe, settings, rows):
     """Device tensors ``(mean (C, n_x), ycov (C (C + 1) / 2, n_x), xcov (n_sel, C, n_x), pvar (n_sel,))``."""
-    import torch
     _device_model(obe)
     x, p, w = _inputs(obe, settings)
     n_x, n_p, n_c, dev = x.shape[1], p.shape[1], obe.n_channels, obe._device
@@ -109,18 +110,15 @@ def _blocks(obe, settings, rows):
     def new(*shape):
         return torch.empty(shape, dtype=torch.float64, device=dev)
     mean, ycov, xcov, pvar = new(n_c, n_x), new(pairs, n_x), new(len(rows), n_c, n_x), new(len(rows))
-    for start, part in _column_tiles(x, _predictive.SETTINGS_PER_CALL):
+    for start, part in column_tiles(x, _predictive.SETTINGS_PER_CALL):
         n = part.shape[1]
         d_mean, d_ycov = new(n_c, n), new(pairs, n)
         for r0 in range(0, len(rows), ROWS_PER_CALL):
             tile = np.array(rows[r0:r0 + ROWS_PER_CALL], dtype=np.int32)
             d_xcov = new(tile.size, n_c, n)
-            # (a workspace of the call's own: the object's workspace keeps the record of a sweep enqueued ahead)
-            nbytes = int(obe._mlib.cdll.obe_output_covariance_workspace_bytes(n_p, n, n_c, tile.size))
-            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=dev)
-            obe._mlib.call("obe_output_covariance", obe._model_struct, _ptr(part), n, n, _ptr(p), n_p, p.shape[0], n_p,
-                           _ptr(w), _lib.host_ptr(tile), tile.size, _ptr(d_mean), _ptr(d_ycov) if r0 == 0 else None,
-                           _ptr(d_xcov), _ptr(pvar[r0:r0 + tile.size]), _ptr(ws), nbytes, obe._stream())
+            model_call(obe, "obe_output_covariance", "obe_output_covariance_workspace_bytes", (n_p, n, n_c, tile.size),
+                       _ptr(part), n, n, _ptr(p), n_p, p.shape[0], n_p, _ptr(w), _lib.host_ptr(tile), tile.size,
+                       _ptr(d_mean), _ptr(d_ycov) if r0 == 0 else None, _ptr(d_xcov), _ptr(pvar[r0:r0 + tile.size]))
             xcov[r0:r0 + tile.size, :, start:start + n] = d_xcov
         mean[:, start:start + n] = d_mean
         ycov[:, start:start + n] = d_ycov
@@ -130,7 +128,6 @@ def _blocks(obe, settings, rows):
 def _finish(obe, ycov, xcov, pvar, noise_var, weights=None, cost=(None, 1.0)):
     """Device ``(gain (n_sel, n_x), utility (n_x,) or None)`` from the blocks; ``weights``: form the utility too, with
     ``cost`` = (device (n_x,) or None, scalar)."""
-    import torch
     n_sel, n_c, n_x = xcov.shape
     dev = obe._device
     nv = torch.from_numpy(np.ascontiguousarray(noise_var)).to(dev)

@@ -11,7 +11,7 @@ from . import _batch, _lib
 from ._scoring import _numbers, check_records
 from .models import DeviceModel
 from .obe_base import OptBayesExpt, _LazyState, _overridden
-from .particlepdf import _ptr
+from ._devcall import ptr as _ptr
 
 INFORMATION = "mutual_information"
 
@@ -148,12 +148,6 @@ class OwnCloudPasses(OptBayesExpt):
         self._nu_bar = {k: v for k, v in self._nu_bar.items() if v[0] == key}
         self._nu_bar[(begin, end)] = (key, out)
         return out
-
-    def _pass_workspace(self, entry, *sizes):
-        """(tensor, bytes) for one call of a pass.  (A workspace of the call's own: the object's workspace keeps the
-        record of a sweep enqueued ahead.)"""
-        nbytes = int(getattr(self._mlib.cdll, entry)(*sizes))
-        return torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=self._device), nbytes
 
     def yvar_noise_model(self):
         """``(C, n_settings)`` float64: the class's ``nu_bar_c(s)`` (see its docstring) over the whole weighted cloud,

@@ -6,13 +6,14 @@ demos/find_peak/seqLor_pdfevolve.py:156-163, the histograms of docs/manual_demos
 kernels (csrc/obe_posterior.hip) and only the few result values travel.  The argument checks are plain functions of
 this module (no device needed); ``ParticlePDF`` has the methods.
 """
-import ctypes
-
 import numpy as np
+import torch
+
+from . import _lib
+from ._devcall import P as _P, ptr as _ptr, workspace
 
 MAX_Q_PER_CALL = 16          # obe_weighted_quantiles: values of q one call serves (more are served in groups)
 MAX_BINS = 1 << 24           # bins one call fills, all rows together
-_P = ctypes.c_void_p
 
 
 # ---------------------------------------------------------------------------------------- argument checks (host)
@@ -129,21 +130,11 @@ def interval_quantiles(level):
 
 
 # ------------------------------------------------------------------------------------------------- device calls
-def _ptr(t):
-    return _P(t.data_ptr())
-
-
 def _workspace(pdf, n_rows, n_bins, n_q):
-    """A workspace of the call's own (torch's caching allocator hands the same block back call after call): the
-    object's workspace keeps the record of a sweep enqueued ahead, which must stay readable."""
-    import torch
-    nbytes = int(pdf._lib.cdll.obe_posterior_workspace_bytes(pdf.n_particles, n_rows, n_bins, n_q))
-    return torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=pdf._device), nbytes
+    return workspace(pdf._lib, pdf._device, "obe_posterior_workspace_bytes", pdf.n_particles, n_rows, n_bins, n_q)
 
 
 def _auto_ranges(pdf, p, rows):
-    import torch
-    from . import _lib
     out = torch.empty(2 * len(rows), dtype=torch.float64, device=pdf._device)
     ws, ws_bytes = _workspace(pdf, len(rows), 0, 0)
     pdf._lib.call("obe_minmax_rows", _ptr(p), p.shape[1], pdf.n_dims, pdf.n_particles, _lib.host_ptr(rows), len(rows),
@@ -156,8 +147,6 @@ def _auto_ranges(pdf, p, rows):
 
 
 def marginal_histogram(pdf, dims=None, bins=64, range=None, density=False):
-    import torch
-    from . import _lib
     rows = check_dims(dims, pdf.n_dims)
     bins = check_bins(bins)
     ranges = check_range(range, len(rows))
@@ -179,7 +168,6 @@ def marginal_histogram(pdf, dims=None, bins=64, range=None, density=False):
 
 
 def joint_histogram(pdf, dim_x, dim_y, bins=64, range=None, density=False):
-    import torch
     rows = check_dims([dim_x, dim_y], pdf.n_dims)
     bx, by = check_bins2(bins)
     ranges = check_range(range, 2)
@@ -205,8 +193,6 @@ def joint_histogram(pdf, dim_x, dim_y, bins=64, range=None, density=False):
 
 
 def quantile(pdf, q, dims=None):
-    import torch
-    from . import _lib
     qs, scalar = check_q(q)
     rows = check_dims(dims, pdf.n_dims)
     p, w = pdf._pw_tensors()

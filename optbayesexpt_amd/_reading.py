@@ -14,9 +14,11 @@ import statistics
 import warnings
 
 import numpy as np
+import torch
 
 from . import _lib
-from ._predictive import _column_tiles, _device_model, _ptr, check_settings
+from ._devcall import cloud, column_tiles, model_call, ptr as _ptr
+from ._predictive import _device_model, check_settings
 from ._scoring import _noise_rows, check_sigma
 
 MAX_Q_PER_CALL = 16                            # obe_predictive_reading_quantiles: levels one call serves
@@ -70,7 +72,6 @@ def check_request(settings, sigma, n_setdims, n_channels, noise_rows, n_grid):
 
 # ------------------------------------------------------------------------------------------------- device calls
 def reading_quantile(obe, q, settings=None, sigma=None, max_passes=48, full_output=False):
-    import torch
     _device_model(obe)
     qs, scalar = check_levels(q)
     max_passes = check_max_passes(max_passes)
@@ -80,9 +81,7 @@ def reading_quantile(obe, q, settings=None, sigma=None, max_passes=48, full_outp
     zs = normal_quantiles(qs)
     dev = obe._device
     x = obe._settings_dev if x is None else torch.from_numpy(x).to(dev)      # (the whole design grid, sharded or not)
-    p, w = obe._parameters.tensor(), obe._weights.tensor()                   # (host edits of the cloud are uploaded here)
-    if p.shape[1] != w.shape[0]:
-        raise ValueError("particles and particle_weights have different lengths")
+    p, w = cloud(obe)
     n_s, n_x, n_p = x.shape[0], x.shape[1], p.shape[1]
     if s is not None:
         if s.shape[1] != n_x:
@@ -93,17 +92,15 @@ def reading_quantile(obe, q, settings=None, sigma=None, max_passes=48, full_outp
     for q0 in range(0, qs.size, MAX_Q_PER_CALL):
         part_q = np.ascontiguousarray(qs[q0:q0 + MAX_Q_PER_CALL])
         part_z = np.ascontiguousarray(zs[q0:q0 + MAX_Q_PER_CALL])
-        for start, part in _column_tiles(x, SETTINGS_PER_CALL):
+        for start, part in column_tiles(x, SETTINGS_PER_CALL):
             n = part.shape[1]
             d_out = torch.empty((part_q.size, n_c, n), dtype=torch.float64, device=dev)
             d_passes = torch.empty((part_q.size, n_c, n), dtype=torch.int32, device=dev)
-            # (a workspace of the call's own: the object's workspace keeps the record of a sweep enqueued ahead)
-            nbytes = int(obe._mlib.cdll.obe_predictive_reading_workspace_bytes(n_p, n, n_c, part_q.size))
-            ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=dev)
-            obe._mlib.call("obe_predictive_reading_quantiles", obe._model_struct, _ptr(part), n, n,
-                           None if s is None else _ptr(part[n_s:]), n, None if rows is None else _lib.host_ptr(rows),
-                           _ptr(p), n_p, n_p, _ptr(w), _lib.host_ptr(part_q), _lib.host_ptr(part_z), part_q.size,
-                           max_passes, _ptr(d_out), _ptr(d_passes), _ptr(ws), nbytes, obe._stream())
+            model_call(obe, "obe_predictive_reading_quantiles", "obe_predictive_reading_workspace_bytes",
+                       (n_p, n, n_c, part_q.size), _ptr(part), n, n, None if s is None else _ptr(part[n_s:]), n,
+                       None if rows is None else _lib.host_ptr(rows), _ptr(p), n_p, n_p, _ptr(w),
+                       _lib.host_ptr(part_q), _lib.host_ptr(part_z), part_q.size, max_passes, _ptr(d_out),
+                       _ptr(d_passes))
             out[q0:q0 + part_q.size, :, start:start + n] = d_out.cpu().numpy()
             passes[q0:q0 + part_q.size, :, start:start + n] = d_passes.cpu().numpy()
     unconverged = int(np.count_nonzero(passes < 0))

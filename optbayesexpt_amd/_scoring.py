@@ -8,9 +8,11 @@ records x particles evaluations; they are HIP kernels (csrc/obe_predict.hip, K11
 tiled over the records so that no workspace grows with the request; ``OptBayesExpt`` has the methods.
 """
 import numpy as np
+import torch
 
 from . import _lib
-from ._predictive import _column_tiles, _device_model, _ptr, check_settings
+from ._devcall import cloud, column_tiles, model_call, ptr as _ptr
+from ._predictive import _device_model, check_settings
 
 RECORDS_PER_CALL = 1 << 16                     # records one library call is given
 
@@ -109,31 +111,25 @@ def _noise_rows(obe):
 
 def _score(obe, entry, n_out, settings, y_meas, sigma):
     """The ``n_out`` device results of ``entry`` (each (rows, n_r)) for the checked records, and ``single``."""
-    import torch
     _device_model(obe)
     rows = _noise_rows(obe)
     n_c = obe.n_channels
     x, y, s, single = check_records(settings, y_meas, sigma, obe.allsettings.shape[0], n_c, rows)
-    p, w = obe._parameters.tensor(), obe._weights.tensor()          # (host edits of the cloud are uploaded here)
-    if p.shape[1] != w.shape[0]:
-        raise ValueError("particles and particle_weights have different lengths")
+    p, w = cloud(obe)
     n_r, n_p = x.shape[1], p.shape[1]
     dev = obe._device
     stacked = torch.from_numpy(np.vstack([x, y] + ([] if s is None else [s]))).to(dev)
     n_s = x.shape[0]
     out_rows = 1 if entry == "obe_predictive_logpdf" else n_c
     outs = [torch.empty((out_rows, n_r), dtype=torch.float64, device=dev) for _ in range(n_out)]
-    for start, part in _column_tiles(stacked, RECORDS_PER_CALL):
+    for start, part in column_tiles(stacked, RECORDS_PER_CALL):
         n = part.shape[1]
         d_x, d_y = part[:n_s], part[n_s:n_s + n_c]
         d_s = None if s is None else _ptr(part[n_s + n_c:])
         d_out = [torch.empty((out_rows, n), dtype=torch.float64, device=dev) for _ in range(n_out)]
-        # (a workspace of the call's own: the object's workspace keeps the record of a sweep enqueued ahead)
-        nbytes = int(obe._mlib.cdll.obe_predictive_score_workspace_bytes(n_p, n, n_c))
-        ws = torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=dev)
-        obe._mlib.call(entry, obe._model_struct, _ptr(d_x), n, n, _ptr(d_y), n, d_s, n,
-                       None if rows is None else _lib.host_ptr(rows), _ptr(p), n_p, n_p, _ptr(w),
-                       *[_ptr(t) for t in d_out], _ptr(ws), nbytes, obe._stream())
+        model_call(obe, entry, "obe_predictive_score_workspace_bytes", (n_p, n, n_c),
+                   _ptr(d_x), n, n, _ptr(d_y), n, d_s, n, None if rows is None else _lib.host_ptr(rows),
+                   _ptr(p), n_p, n_p, _ptr(w), *[_ptr(t) for t in d_out])
         for whole, piece in zip(outs, d_out):
             whole[:, start:start + n] = piece
     return [t.cpu().numpy() for t in outs], single

@@ -38,7 +38,8 @@ from ._sweepstate import Attempt, Form, Pending, SweepState, Ticket
 from . import models as _models
 from ._mirror import Mirror, TrackedArray
 from .models import DeviceModel
-from .particlepdf import ParticlePDF, _P, _ptr
+from ._devcall import P as _P, ptr as _ptr
+from .particlepdf import ParticlePDF
 
 DEFAULT_N_DRAWS = 30            # obe_base.py:19
 MAX_ENTROPY_DRAWS = 2048        # csrc/obe_yspace.hip: kMaxDraws, the samples per column obe_yspace_entropy sorts

@@ -19,7 +19,7 @@ import torch
 
 from . import _batch, _lib
 from ._ownnoise import INFORMATION, CountReadings, check_own_records, lgamma_plus_one, tile_sums
-from .particlepdf import _P, _ptr
+from ._devcall import P as _P, model_call, ptr as _ptr
 
 MAX_CHANNELS = _lib.OBE_BINOMIAL_MAX_CHANNELS
 #: the public names the library sets on an object of this class only (_state.py): ``shots`` is a likely name for an
@@ -177,12 +177,11 @@ class OptBayesExptBinomial(CountReadings):
             info = torch.empty(max(n, 1), dtype=torch.float64, device=self._device) if want_information else None
             if n > 0:
                 cost_t, cost_s = self._cost_device(whole_grid=True) if want_information else (None, 1.0)
-                ws, nbytes = self._pass_workspace("obe_binomial_workspace_bytes", n_p, n, self.n_channels)
                 into_call, rows = self._per_channel(shots)
-                self._mlib.call("obe_binomial_information", self._model_struct,
-                                _P(self._settings_dev.data_ptr() + 8 * begin), self._n_settings, n, _ptr(p), n_p, n_p,
-                                _ptr(w), into_call, None if cost_t is None else _P(cost_t.data_ptr() + 8 * begin),
-                                cost_s, None if info is None else _ptr(info), _ptr(nu), _ptr(ws), nbytes, self._stream())
+                model_call(self, "obe_binomial_information", "obe_binomial_workspace_bytes", (n_p, n, self.n_channels),
+                           _P(self._settings_dev.data_ptr() + 8 * begin), self._n_settings, n, _ptr(p), n_p, n_p,
+                           _ptr(w), into_call, None if cost_t is None else _P(cost_t.data_ptr() + 8 * begin),
+                           cost_s, None if info is None else _ptr(info), _ptr(nu))
                 if rows is not None:
                     nu /= rows
             made["info"] = info

@@ -10,7 +10,7 @@ import torch
 
 from . import _bounds, _lib
 from .obe_base import OptBayesExpt, _overridden
-from .particlepdf import _ptr
+from ._devcall import ptr as _ptr
 
 
 class OptBayesExptNoiseParameter(OptBayesExpt):

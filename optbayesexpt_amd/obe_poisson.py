@@ -21,9 +21,9 @@ import math
 import numpy as np
 import torch
 
-from . import _batch, _lib
+from . import _batch, _lib, _predictive
 from ._ownnoise import INFORMATION, CountReadings, check_own_records, lgamma_plus_one, tile_sums
-from .particlepdf import _P, _ptr
+from ._devcall import P as _P, model_call, ptr as _ptr
 
 MAX_CHANNELS = _lib.OBE_MAX_CHANNELS
 CAPS = (16, 32, 64)
@@ -179,10 +179,9 @@ class OptBayesExptPoisson(CountReadings):
         cap = check_cap(self.count_cap)
         p, w = self._pw_tensors()
         n_p = p.shape[1]
-        ws, nbytes = self._pass_workspace("obe_poisson_workspace_bytes", n_p, n, self.n_channels, cap)
         opt = [None if t is None else _ptr(t) for t in (info, tail, pmf, nu)]
-        self._mlib.call("obe_poisson_information", self._model_struct, x, ld_s, n, _ptr(p), n_p, n_p, _ptr(w),
-                        float(exposure), cap, cost_t, float(cost_s), *opt, _ptr(ws), nbytes, self._stream())
+        model_call(self, "obe_poisson_information", "obe_poisson_workspace_bytes", (n_p, n, self.n_channels, cap),
+                   x, ld_s, n, _ptr(p), n_p, n_p, _ptr(w), float(exposure), cap, cost_t, float(cost_s), *opt)
 
     def _pass(self, begin, end, want_information):
         """Device ``(information (end - begin,) or None, nu_bar (C, end - begin))`` of the settings [begin, end) of the
@@ -232,7 +231,6 @@ class OptBayesExptPoisson(CountReadings):
         ``Pbar_k = sum w Pois(k; exposure r) / W`` for k < ``count_cap`` and the mass of ">= count_cap" last, at the
         design grid or at ``settings`` (points, as ``predict()`` takes them).  What one draws against recorded counts,
         and what an outlier check sums a tail of.  Models of one channel."""
-        from . import _predictive
         if self.n_channels != 1:
             raise ValueError("count_distribution() takes a model of one channel")
         exposure = check_exposure(self.exposure, 1)

@@ -20,7 +20,7 @@ import torch
 
 from . import _batch, _lib
 from ._ownnoise import OwnCloudPasses, check_own_records
-from .particlepdf import _P, _ptr
+from ._devcall import P as _P, model_call, ptr as _ptr
 
 _FIELDS = ("noise_floor", "noise_gain", "noise_relative")
 #: the public names the library sets on an object of this class only (_state.py): none, the three coefficients are
@@ -114,10 +114,9 @@ class OptBayesExptSignalNoise(OwnCloudPasses):
             n, n_p = end - begin, p.shape[1]
             out = torch.empty((self.n_channels, max(n, 1)), dtype=torch.float64, device=self._device)
             if n > 0:
-                ws, nbytes = self._pass_workspace("obe_signal_noise_workspace_bytes", n_p, n, self.n_channels)
-                self._mlib.call("obe_signal_noise_variance", self._model_struct,
-                                _P(self._settings_dev.data_ptr() + 8 * begin), self._n_settings, n, _ptr(p), n_p, n_p,
-                                _ptr(w), _lib.host_ptr(coef), _ptr(out), _ptr(ws), nbytes, self._stream())
+                model_call(self, "obe_signal_noise_variance", "obe_signal_noise_workspace_bytes",
+                           (n_p, n, self.n_channels), _P(self._settings_dev.data_ptr() + 8 * begin), self._n_settings, n,
+                           _ptr(p), n_p, n_p, _ptr(w), _lib.host_ptr(coef), _ptr(out))
             return out
 
         return self._nu_bar_cached(begin, end, coef.tobytes(), compute)

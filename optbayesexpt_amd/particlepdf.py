@@ -7,22 +7,16 @@ for stream parity with the reference: the NumPy ``Generator`` (``self.rng``) tha
 produces the uniforms and normals of a resample, and the D x D SVD of the nudge
 covariance (LAPACK, exactly as ``Generator.multivariate_normal`` does it).
 """
-import ctypes
 import warnings
 
 import numpy as np
 import torch
 
 from . import _devrng, _drift, _lib, _posterior
+from ._devcall import P as _P, ptr as _ptr          # (module globals: the cycle pays no call to reach them)
 from ._mirror import Mirror
 
-_P = ctypes.c_void_p
-
-
 SQRT_EPS = float(np.sqrt(np.finfo(np.float64).eps))   # numpy's tolerance on sum(p) in choice()
-
-def _ptr(t):
-    return _P(t.data_ptr())
 
 
 class ParticlePDF:

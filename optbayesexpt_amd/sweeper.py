@@ -22,7 +22,8 @@ import torch
 from . import _lib
 from .obe_base import OptBayesExpt, _LazyState, _overridden
 from .obe_noiseparam import OptBayesExptNoiseParameter
-from .particlepdf import ParticlePDF, _ptr
+from ._devcall import ptr as _ptr
+from .particlepdf import ParticlePDF
 
 #: module-level generator for good_setting / random_setting, like the reference module's
 #: own ``rng`` (obe_sweeper.py:3-6)

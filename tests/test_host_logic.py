@@ -739,6 +739,7 @@ def test_released_landing_zones_wait_in_limbo(monkeypatch):
     import torch
     from optbayesexpt_amd import _lib
     monkeypatch.setattr(torch.Tensor, "pin_memory", lambda self, *a, **k: self)
+    gc.collect()                               # (objects of earlier tests still uncollected park their zones now, not below)
     monkeypatch.setattr(_lib, "_LIMBO", [])
     synced = []
     monkeypatch.setattr(torch.cuda, "synchronize", lambda d=None: synced.append(d))
