@@ -1218,6 +1218,69 @@ OBE_API int obe_poisson_records_loglik(const obe_model* m, const double* d_setti
                                double constant, const double* d_particles, int64_t ld_p, int64_t n_particles,
                                int32_t accumulate, double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream);
 
+/* ---- K20 — count-aware scoring and reading bands (extension; no reference counterpart: extends K17/K18/K19) ----
+ * "Is this count plausible?" and "where will the next count fall?" for the two counting likelihoods above.  law is
+ * OBE_COUNT_BINOMIAL (the model's channel c gives p_c, a point's side datum is its shots n_c: whole, 1 ..
+ * OBE_COUNT_MAX_OUTCOMES) or OBE_COUNT_POISSON (r_c, the exposure t_c: finite, > 0), anything else -1.  A POINT is a
+ * column — the setting d_settings (n_setdims, n_points) and the side data d_side (C, n_points), rows ld_side apart —: a
+ * setting of a design grid, or the setting of a record with its own n or t.  P_c,i(k) = Binomial(k; n_c, p_c,i) or
+ * Poisson(k; t_c r_c,i), with p and r what obe_eval_over_particles writes, bit for bit.  At a point a particle
+ * contributes when its weight is > 0 (NaN and negative weights count as zero) and EVERY channel's value there is one the
+ * law takes (p in [0, 1]; r >= 0 with t r finite); W sums the contributing weights, W == 0 — also a point whose side
+ * data are not valid — gives NaN.  All results land in the caller's DEVICE buffers, nothing is waited for.
+ *
+ * obe_count_table: d_pmf (C, count_max + 2, n_points) = Pbar_c(k) = sum_i w_i P_c,i(k) / W for k = 0 .. count_max, then
+ * the mass above count_max, max(1 - sum_k Pbar_c(k), 0) — formed from the rows (a difference of numbers near 1: absolute
+ * accuracy, about the rows' own N_p eps at worst), and exactly 0 for a binomial point with n_c <= count_max.  count_max
+ * in 0 .. OBE_COUNT_MAX_OUTCOMES, else -1.  d_logfact (OBE_COUNT_MAX_OUTCOMES + 2,): log k! for k = 0 ..
+ * OBE_COUNT_MAX_OUTCOMES + 1 on the device, the host's lgamma(k + 1) (obe_poisson_likelihood's h_logfact, as a table).
+ * Geometry: obe_poisson_information's (one wave per workgroup, lane <-> point, particle chunks streamed, chunk partials
+ * folded in chunk order: no atomics, the same bits from run to run), the outcomes in blocks of 32 (count_max < 32) or 64
+ * outcome sums per lane, one launch per channel and block, each folded into its rows before the next starts.  Every
+ * block starts from a log-space value of one of its own outcomes, so that the table is right where e^-lambda, (1 - p)^n
+ * or p^n underflows (rows below ~1e-290 lose relative accuracy, as everywhere) and a recurrence's error grows over one
+ * block only.  Poisson: exp(k0 log lambda - lambda - log k0!) of the block's first outcome k0, then
+ * P(k) = P(k - 1) lambda / k.  Binomial: a lane sums Cmax p^k (1 - p)^(n - k), Cmax the block's largest C(n, k), a
+ * geometric sequence in k that is run from its large end — upwards from k0 for p <= 1/2, downwards from the block's last
+ * outcome <= n for p > 1/2 — and the fold multiplies by C(n, k) / Cmax: right wherever in the block the mass lies
+ * (p = 1e-12 and p = 1 - 1e-12 alike).  lambda = 0, p = 0 and p = 1 give the exact point masses.  With one channel,
+ * exposure the same for all points and count_max = cap - 1 the Poisson rows k < cap hold the bits of
+ * obe_poisson_information's d_pmf (the same arithmetic in the same order; tests/test_gpu_counts.py asserts it).  d_ws:
+ * obe_count_workspace_bytes(n_particles, n_points, the model's channels, count_max) bytes; the size depends on n_points
+ * alone (not on count_max: a block's partials are K18's size) and does not shrink when an argument grows.
+ *
+ * obe_count_tails, obe_count_quantiles: light kernels on a table obe_count_table wrote, one thread per (point, channel);
+ * they take no model.  d_counts (C, n_points), rows ld_k apart: d_lower = sum_{j <= k} Pbar_c(j), d_upper = sum_{j >= k}
+ * Pbar_c(j) + the mass above, both (C, n_points), each summed from its small end; both include k itself; either may be
+ * NULL, not both; NaN where k is not a whole number in 0 .. count_max.  h_levels: n_levels (1 .. OBE_COUNT_MAX_LEVELS)
+ * host doubles in the open interval (0, 1), else -1; d_quantiles (n_levels, C, n_points) = the smallest k with
+ * sum_{j <= k} Pbar_c(j) >= q (where the mass above is exactly 0 the last row closes the sum: 1), +inf where count_max
+ * is too small for the level, NaN where W == 0.
+ *
+ * obe_count_logpmf: d_logpmf (n_records,) = log(sum_i w_i prod_c P_c,i(k_c) / W) of the records d_settings | d_counts
+ * (C, n_records) | d_side (C, n_records) — the JOINT one-step log evidence, not the product of the channels' mixtures —
+ * with the term of obe_binomial_records_loglik / obe_poisson_records_loglik per particle, merged as
+ * obe_predictive_logpdf merges (a running maximum and a scaled sum: nothing over- or underflows), plus d_constant
+ * (n_records,), what no particle changes (sum_c log C(n, k) or -sum_c log k!, the host's).  -inf where the record is
+ * impossible for every contributing particle; NaN where W == 0 or the record's data cannot be one.  d_ws as above. */
+#define OBE_COUNT_MAX_OUTCOMES 4096
+#define OBE_COUNT_MAX_LEVELS 16
+#define OBE_COUNT_BINOMIAL 0
+#define OBE_COUNT_POISSON 1
+OBE_API int64_t obe_count_workspace_bytes(int64_t n_particles, int64_t n_points, int32_t n_channels, int32_t count_max);
+OBE_API int obe_count_table(const obe_model* m, int32_t law, const double* d_settings, int64_t ld_s, int64_t n_points,
+                    const double* d_side, int64_t ld_side, const double* d_logfact, const double* d_particles,
+                    int64_t ld_p, int64_t n_particles, const double* d_weights, int32_t count_max, double* d_pmf,
+                    void* d_ws, int64_t ws_bytes, void* stream);
+OBE_API int obe_count_tails(const double* d_pmf, int32_t n_channels, int32_t count_max, int64_t n_points,
+                    const double* d_counts, int64_t ld_k, double* d_lower, double* d_upper, void* stream);
+OBE_API int obe_count_quantiles(const double* d_pmf, int32_t n_channels, int32_t count_max, int64_t n_points,
+                        const double* h_levels, int32_t n_levels, double* d_quantiles, void* stream);
+OBE_API int obe_count_logpmf(const obe_model* m, int32_t law, const double* d_settings, int64_t ld_s, int64_t n_records,
+                     const double* d_counts, int64_t ld_k, const double* d_side, int64_t ld_side,
+                     const double* d_constant, const double* d_particles, int64_t ld_p, int64_t n_particles,
+                     const double* d_weights, double* d_logpmf, void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---- timing on the launch stream (bench.py roofline leg) ---- */
 OBE_API int obe_timer_create(void** timer);
 OBE_API int obe_timer_start(void* timer, void* stream);

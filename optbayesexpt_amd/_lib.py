@@ -33,6 +33,9 @@ OBE_FAST_DIMS = _H["OBE_FAST_DIMS"]                  # cloud kernels compiled fo
 OBE_CLOUD_MAX_DIMS = _H["OBE_CLOUD_MAX_DIMS"]        # what the tiled cloud kernels take (ParticlePDF alone)
 OBE_BINOMIAL_MAX_CHANNELS = _H["OBE_BINOMIAL_MAX_CHANNELS"]      # channels of a model of yes/no outcomes
 OBE_POISSON_MAX_CAP = _H["OBE_POISSON_MAX_CAP"]      # the largest censoring count of a counted reading's information
+# count-aware scoring (K20): the largest count_max / shots / scored count, the levels of one call, the two laws
+OBE_COUNT_MAX_OUTCOMES, OBE_COUNT_MAX_LEVELS = _H["OBE_COUNT_MAX_OUTCOMES"], _H["OBE_COUNT_MAX_LEVELS"]
+OBE_COUNT_BINOMIAL, OBE_COUNT_POISSON = _H["OBE_COUNT_BINOMIAL"], _H["OBE_COUNT_POISSON"]
 OBE_WS_RESULT_OFFSET = _H["OBE_WS_RESULT_OFFSET"]    # doubles
 # bits of obe_sweep_utility's `shifted` argument
 OBE_SWEEP_SHIFTED, OBE_SWEEP_SAFE = _H["OBE_SWEEP_SHIFTED"], _H["OBE_SWEEP_SAFE"]
@@ -150,7 +153,9 @@ MODEL_ENTRY_POINTS = ("obe_model_validate", "obe_workspace_bytes", "obe_sweep_se
                       "obe_poisson_likelihood", "obe_poisson_workspace_bytes", "obe_poisson_information",
                       "obe_signal_noise_records_loglik_workspace_bytes", "obe_signal_noise_records_loglik",
                       "obe_binomial_records_loglik_workspace_bytes", "obe_binomial_records_loglik",
-                      "obe_poisson_records_loglik_workspace_bytes", "obe_poisson_records_loglik")
+                      "obe_poisson_records_loglik_workspace_bytes", "obe_poisson_records_loglik",
+                      "obe_count_workspace_bytes", "obe_count_table", "obe_count_tails", "obe_count_quantiles",
+                      "obe_count_logpmf")
 
 
 class HipLib:

@@ -7,7 +7,7 @@ import math
 import numpy as np
 import torch
 
-from . import _batch, _lib
+from . import _batch, _counts, _lib
 from ._scoring import _numbers, check_records
 from .models import DeviceModel
 from .obe_base import OptBayesExpt, _LazyState, _overridden
@@ -254,3 +254,43 @@ class CountReadings(OwnCloudPasses):
     def opt_setting_batch(self, n, sigma=None, distinct=False, interest=None, interest_weights=None):
         self._no_sigma("opt_setting_batch", sigma)
         return OptBayesExpt.opt_setting_batch(self, n, None, distinct, interest, interest_weights)
+
+    # -- count-aware scoring and reading bands (_counts.py; csrc/obe_counts.hip) ----------------------------------------
+    # ``side``: the class's ``_NOISE_FROM`` (``shots``, ``exposure``), which each class takes under that name; None: the
+    # object's attribute.  ``P_c,i(k)``: the class's pmf of channel c at particle i (its docstring); a particle
+    # contributes where its weight is > 0 and every channel's model value is one the class takes, W sums those weights,
+    # and W == 0 gives NaN.  Nothing is kept on the object.
+    _COUNT_LAW = None
+
+    def count_logpmf(self, settings, counts, *, side=None):
+        """``(n_r,)`` float64, or a float for one record given as ``pdf_update`` takes it: the JOINT one-step log
+        evidence ``log(sum_i w_i prod_c P_c,i(k_c) / W)`` of each record, ``log C(n, k)`` / ``-log k!`` included (not
+        the product of the channels' mixtures).  Records as ``records_loglik()`` takes them; counts (and shots) at most
+        OBE_COUNT_MAX_OUTCOMES.  -inf where the record is impossible for every contributing particle."""
+        return _counts.count_logpmf(self, settings, counts, side)
+
+    def count_cdf(self, settings, counts, upper=False, *, side=None):
+        """``(C, n_r)``: per channel ``P(K_c <= k_c)`` of the recorded count under the mixture
+        ``Pbar_c(k) = sum_i w_i P_c,i(k) / W``; ``upper=True``: ``P(K_c >= k_c)``.  Both tails include k itself."""
+        return _counts.count_cdf(self, settings, counts, upper, side)
+
+    def count_pvalue(self, settings, counts, *, side=None):
+        """``(C, n_r)``: the two-sided p-value per channel, ``min(2 min(lower, upper), 1)`` of ``count_cdf()``'s
+        tails."""
+        return _counts.count_pvalue(self, settings, counts, side)
+
+    def count_pmf(self, settings=None, count_max=None, *, side=None):
+        """``(n_x, C, count_max + 2)``: ``Pbar_c(k) = sum_i w_i P_c,i(k) / W`` for k = 0 .. ``count_max``, then the mass
+        above ``count_max``, at the whole design grid (None; on a sharded object too) or at ``settings`` (points, as
+        ``predict()`` takes them).  ``side``: a scalar or ``(C,)``.  ``count_max``: at most OBE_COUNT_MAX_OUTCOMES."""
+        return _counts.count_pmf(self, settings, count_max, side)
+
+    def count_quantile(self, q, settings=None, count_max=None, full_output=False, *, side=None):
+        """``(n_q, C, n_x)`` float64 holding whole numbers (``(C, n_x)`` for a scalar ``q``): the smallest k with
+        ``P(K_c <= k) >= q``, levels in the open interval (0, 1).  NaN where the level is not reached within
+        ``count_max`` (one ``RuntimeWarning`` counts such results; ``full_output`` adds ``{"beyond": n}``)."""
+        return _counts.count_quantile(self, q, settings, count_max, full_output, side)
+
+    def count_interval(self, level=0.95, settings=None, count_max=None, full_output=False, *, side=None):
+        """``(lo, hi)``: ``count_quantile()`` at ``(1 -+ level) / 2`` — the band to draw against recorded counts."""
+        return _counts.count_interval(self, level, settings, count_max, full_output, side)

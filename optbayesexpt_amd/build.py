@@ -152,7 +152,7 @@ def library_is_stale():
 #: where generated models are compiled to; OBE_PLUGIN_DIR overrides (e.g. a read-only installation)
 PLUGIN_DIR = os.environ.get("OBE_PLUGIN_DIR", os.path.join(OUT_DIR, "plugins"))
 PLUGIN_SOURCES = ["obe_capi.hip", "obe_update.hip", "obe_sweep.hip", "obe_yspace.hip", "obe_predict.hip",
-                  "obe_signal_noise.hip", "obe_binomial.hip", "obe_poisson.hip"]   # model-dependent
+                  "obe_signal_noise.hip", "obe_binomial.hip", "obe_poisson.hip", "obe_counts.hip"]   # model-dependent
 #: linked into every plugin as well, but the same for every model: the object the LIBRARY build left in lib/obj is
 #: reused (its ~45 kernel instantiations took 9 of the 10 s of a formula's first use when each plugin recompiled them)
 PLUGIN_COMMON_SOURCES = ["obe_update_common.hip"]

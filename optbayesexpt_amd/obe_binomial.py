@@ -19,6 +19,7 @@ import torch
 
 from . import _batch, _lib
 from ._ownnoise import INFORMATION, CountReadings, check_own_records, lgamma_plus_one, tile_sums
+from ._counts import Law as CountLaw
 from ._devcall import P as _P, model_call, ptr as _ptr
 
 MAX_CHANNELS = _lib.OBE_BINOMIAL_MAX_CHANNELS
@@ -114,11 +115,15 @@ class OptBayesExptBinomial(CountReadings):
     ``yvar_noise_model()`` gives.  ``pdf_update((setting, k))`` or ``((setting, k, n))``; ``likelihood()``:
     ``L_i = exp(sum_c [k_c log p_c,i + (n_c - k_c) log1p(-p_c,i)])``, 0 for a particle with a probability that is NaN
     or outside [0, 1].  ``records_loglik()`` and ``pdf_update_batch()`` take a recorded table of clicks at once.  The
-    summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``."""
+    summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``; for counts ask ``count_logpmf()``,
+    ``count_cdf()``, ``count_pvalue()`` (is this record plausible?) and ``count_pmf()``, ``count_quantile()``,
+    ``count_interval()`` (where will the next k fall?), with ``shots`` at most OBE_COUNT_MAX_OUTCOMES."""
     _NOISE_FROM = "shots"
     _REFUSAL = ("takes readings with a Gaussian sigma per record, but this object's readings are counts (k successes "
-                "in n shots): count-aware scoring and reading bands are not built (records_loglik() and "
-                "pdf_update_batch() take the records without sigma)")
+                "in n shots): count_logpmf(), count_cdf(), count_pvalue(), count_quantile() and count_interval() "
+                "score and band them (records_loglik() and pdf_update_batch() take the records without sigma)")
+    _COUNT_LAW = CountLaw(_lib.OBE_COUNT_BINOMIAL, "shots", check_shots, check_count_table,
+                          lambda shots: int(np.max(shots)), True)
 
     def __init__(self, measurement_model, setting_values, parameter_samples, constants, shots=1,
                  utility_method=INFORMATION, **kwargs):
@@ -161,6 +166,34 @@ class OptBayesExptBinomial(CountReadings):
         binomial coefficients included.  ``sigma`` must stay None."""
         self._no_record_sigma("pdf_update_batch", sigma)
         return _batch.pdf_update_batch(self, settings, y_meas, None, tempered, max_stages, on_stage, shots=shots)
+
+    # -- count-aware scoring and reading bands: CountReadings' methods under this class's keyword ----------------------
+    def count_logpmf(self, settings, counts, *, shots=None):
+        """``CountReadings.count_logpmf()``: the joint one-step log evidence of each record, ``log C(n, k)`` included.
+        ``shots`` as ``records_loglik()`` takes it."""
+        return CountReadings.count_logpmf(self, settings, counts, side=shots)
+
+    def count_cdf(self, settings, counts, upper=False, *, shots=None):
+        """``CountReadings.count_cdf()``: per channel P(K <= k), or P(K >= k), of the recorded successes.  ``shots`` as
+        ``records_loglik()`` takes it."""
+        return CountReadings.count_cdf(self, settings, counts, upper, side=shots)
+
+    def count_pvalue(self, settings, counts, *, shots=None):
+        """``CountReadings.count_pvalue()``: the two-sided p-value of the recorded successes, per channel."""
+        return CountReadings.count_pvalue(self, settings, counts, side=shots)
+
+    def count_pmf(self, settings=None, count_max=None, *, shots=None):
+        """``CountReadings.count_pmf()``: the predicted histogram of the next reading, ``(n_x, C, count_max + 2)``.
+        ``count_max`` None: the largest ``shots`` (nothing lies above).  ``shots``: None (the object's), a scalar or ``(C,)``."""
+        return CountReadings.count_pmf(self, settings, count_max, side=shots)
+
+    def count_quantile(self, q, settings=None, count_max=None, full_output=False, *, shots=None):
+        """``CountReadings.count_quantile()``: the smallest k with P(K <= k) >= q, ``(n_q, C, n_x)``."""
+        return CountReadings.count_quantile(self, q, settings, count_max, full_output, side=shots)
+
+    def count_interval(self, level=0.95, settings=None, count_max=None, full_output=False, *, shots=None):
+        """``CountReadings.count_interval()``: ``(lo, hi)``, the band the next reading's successes fall in."""
+        return CountReadings.count_interval(self, level, settings, count_max, full_output, side=shots)
 
     # -- one pass over settings x particles: the information and the variance of a shot --
     def _pass(self, begin, end, want_information):

@@ -23,6 +23,7 @@ import torch
 
 from . import _batch, _lib, _predictive
 from ._ownnoise import INFORMATION, CountReadings, check_own_records, lgamma_plus_one, tile_sums
+from ._counts import Law as CountLaw
 from ._devcall import P as _P, model_call, ptr as _ptr
 
 MAX_CHANNELS = _lib.OBE_MAX_CHANNELS
@@ -117,11 +118,17 @@ class OptBayesExptPoisson(CountReadings):
     is NaN, negative or infinite.  ``last_information`` holds ``{"cap", "tail_max"}`` of the last information pass:
     ``tail_max``, the largest mass of the outcome ">= cap" over this rank's settings, says whether ``count_cap`` is large
     enough for the rates.  ``records_loglik()`` and ``pdf_update_batch()`` take a recorded spectrum of counts at once.
-    The summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``."""
+    The summaries that take a per-record Gaussian ``sigma`` raise ``NotImplementedError``; for counts ask
+    ``count_logpmf()``, ``count_cdf()``, ``count_pvalue()`` (is this record plausible?) and ``count_pmf()``,
+    ``count_quantile()``, ``count_interval()`` (where will the next k fall?): every channel, any rate, windows up to
+    OBE_COUNT_MAX_OUTCOMES, where ``count_distribution()`` serves one channel up to ``count_cap``."""
     _NOISE_FROM = "exposure"
     _REFUSAL = ("takes readings with a Gaussian sigma per record, but this object's readings are counts (k events in "
-                "an exposure t): count-aware scoring and reading bands are not built (records_loglik() and "
-                "pdf_update_batch() take the records without sigma)")
+                "an exposure t): count_logpmf(), count_cdf(), count_pvalue(), count_quantile() and count_interval() "
+                "score and band them (records_loglik() and pdf_update_batch() take the records without sigma)")
+    DEFAULT_COUNT_MAX = 256
+    _COUNT_LAW = CountLaw(_lib.OBE_COUNT_POISSON, "exposure", check_exposure, check_count_table,
+                          lambda exposure: OptBayesExptPoisson.DEFAULT_COUNT_MAX, False)
 
     def __init__(self, measurement_model, setting_values, parameter_samples, constants, exposure=1.0, count_cap=32,
                  utility_method=INFORMATION, **kwargs):
@@ -171,6 +178,34 @@ class OptBayesExptPoisson(CountReadings):
         ``-log k!`` included: comparable between models of the same counts.  ``sigma`` must stay None."""
         self._no_record_sigma("pdf_update_batch", sigma)
         return _batch.pdf_update_batch(self, settings, y_meas, None, tempered, max_stages, on_stage, exposure=exposure)
+
+    # -- count-aware scoring and reading bands: CountReadings' methods under this class's keyword ----------------------
+    def count_logpmf(self, settings, counts, *, exposure=None):
+        """``CountReadings.count_logpmf()``: the joint one-step log evidence of each record, ``-log k!`` included.
+        ``exposure`` as ``records_loglik()`` takes it."""
+        return CountReadings.count_logpmf(self, settings, counts, side=exposure)
+
+    def count_cdf(self, settings, counts, upper=False, *, exposure=None):
+        """``CountReadings.count_cdf()``: per channel P(K <= k), or P(K >= k), of the recorded counts.  ``exposure`` as
+        ``records_loglik()`` takes it."""
+        return CountReadings.count_cdf(self, settings, counts, upper, side=exposure)
+
+    def count_pvalue(self, settings, counts, *, exposure=None):
+        """``CountReadings.count_pvalue()``: the two-sided p-value of the recorded counts, per channel."""
+        return CountReadings.count_pvalue(self, settings, counts, side=exposure)
+
+    def count_pmf(self, settings=None, count_max=None, *, exposure=None):
+        """``CountReadings.count_pmf()``: the predicted histogram of the next reading, ``(n_x, C, count_max + 2)``.
+        ``count_max`` None: 256.  ``exposure``: None (the object's), a scalar or ``(C,)``."""
+        return CountReadings.count_pmf(self, settings, count_max, side=exposure)
+
+    def count_quantile(self, q, settings=None, count_max=None, full_output=False, *, exposure=None):
+        """``CountReadings.count_quantile()``: the smallest k with P(K <= k) >= q, ``(n_q, C, n_x)``."""
+        return CountReadings.count_quantile(self, q, settings, count_max, full_output, side=exposure)
+
+    def count_interval(self, level=0.95, settings=None, count_max=None, full_output=False, *, exposure=None):
+        """``CountReadings.count_interval()``: ``(lo, hi)``, the band the next reading's counts fall in."""
+        return CountReadings.count_interval(self, level, settings, count_max, full_output, side=exposure)
 
     # -- one pass over settings x particles ----------------------------------------------
     def _call(self, x, ld_s, n, exposure, cost_t, cost_s, info, tail, pmf, nu):
