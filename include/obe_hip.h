@@ -1087,6 +1087,45 @@ OBE_API int obe_signal_noise_records_loglik(const obe_model* m, const double* d_
                                     const double* d_y_meas, int64_t ld_y, const double* h_noise_coef, double constant,
                                     const double* d_particles, int64_t ld_p, int64_t n_particles, int32_t accumulate,
                                     double* d_loglik, void* d_ws, int64_t ws_bytes, void* stream);
+/* K21 — the posterior predictive of a READING under THIS noise: obe_predictive_logpdf, obe_predictive_tails and
+ * obe_predictive_reading_quantiles (above) with h_noise_coef in place of their d_sigma, ld_sigma, h_noise_rows.  The
+ * predictive is still a mixture of n_particles Gaussians; component i of channel c has the mean f_c(x; theta_i) — what
+ * obe_eval_over_particles writes, bit for bit — and the variance nu_c(f_c(x; theta_i)) = a_c + b_c |f| + c_c f^2, the
+ * arithmetic of the likelihood's nu (an f whose square overflows behaves as it does there).  Who CONTRIBUTES is the
+ * likelihood's rule: a particle with a weight > 0 (NaN and negative weights count as zero) whose nu is > 0 and finite in
+ * EVERY channel.  A NaN or +-inf model value in ANY channel therefore removes the particle from ALL channels — a stated
+ * difference from obe_predictive_tails, where +-inf counts as mass at infinity.  The normalisers are those of the calls
+ * above: the density and the tails divide by the sum of ALL positive weights (a left-out particle is counted there: its
+ * likelihood is 0, which keeps the density the one-step evidence); the quantiles use T = sum w over the contributing
+ * particles, the same for every channel.  h_noise_coef: as above, -1 before any launch.  The geometry of the calls above:
+ * lane = record or setting, the particles of a chunk one after the other, setting tiles x particle chunks (x level
+ * groups), chunk partials folded in chunk order, no atomics: the same bits from run to run.  All results land in the
+ * caller's DEVICE buffers, nothing is waited for.
+ * d_logpdf (n_records,) = log(sum_i w_i prod_c N(y_c; f_c,i, nu_c,i) / sum w) as a running (max, scaled sum) pair,
+ * l_i = sum_c [-(f_c - y_c)^2 / (2 nu_c) - log(nu_c) / 2] (obe_signal_noise_records_loglik's term for one record), minus
+ * (C / 2) log 2 pi; -inf if nobody contributed, NaN if sum w == 0.
+ * d_lower, d_upper (C, n_records) = sum w erfc(+-z_c / sqrt 2) / 2 over sum w with z_c = (f_c - y_c) / sqrt(nu_c), both
+ * sums of positive terms; 0 if nobody contributed, NaN if sum w == 0.  d_ws of both:
+ * obe_predictive_score_workspace_bytes(n_particles, n_records, the model's channels) bytes, a buffer of its own.
+ * d_quantiles, d_passes (n_q, C, n_settings): obe_predictive_reading_quantiles' levels (h_q, h_z, 1..16 of them), bracket
+ * (per level the min of f + z_lo sqrt(nu) and the max of f + z_hi sqrt(nu): it holds for a width per particle), pass
+ * budget (max_passes 1..64), Newton step on log A, stopping rule and pass counts; D = sum w phi(z) / sqrt(nu), sqrt(nu)
+ * and its reciprocal formed once per (setting, particle, channel) and shared by a level group.  T == 0 gives NaN.  d_ws:
+ * obe_predictive_reading_workspace_bytes(n_particles, n_settings, the model's channels, n_q) bytes, a buffer of its
+ * own. */
+OBE_API int obe_signal_noise_logpdf(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                            const double* d_y_meas, int64_t ld_y, const double* h_noise_coef,
+                            const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                            double* d_logpdf, void* d_ws, int64_t ws_bytes, void* stream);
+OBE_API int obe_signal_noise_tails(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                           const double* d_y_meas, int64_t ld_y, const double* h_noise_coef,
+                           const double* d_particles, int64_t ld_p, int64_t n_particles, const double* d_weights,
+                           double* d_lower, double* d_upper, void* d_ws, int64_t ws_bytes, void* stream);
+OBE_API int obe_signal_noise_reading_quantiles(const obe_model* m, const double* d_settings, int64_t ld_s,
+                                       int64_t n_settings, const double* h_noise_coef, const double* d_particles,
+                                       int64_t ld_p, int64_t n_particles, const double* d_weights, const double* h_q,
+                                       const double* h_z, int32_t n_q, int32_t max_passes, double* d_quantiles,
+                                       int32_t* d_passes, void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ---- yes/no outcomes: binomial likelihood and information-gain design (extension) ----
  * Every likelihood above is Gaussian.  Here the model's channel c gives a success probability p_c = f_c(x; theta) and a

@@ -155,7 +155,8 @@ MODEL_ENTRY_POINTS = ("obe_model_validate", "obe_workspace_bytes", "obe_sweep_se
                       "obe_binomial_records_loglik_workspace_bytes", "obe_binomial_records_loglik",
                       "obe_poisson_records_loglik_workspace_bytes", "obe_poisson_records_loglik",
                       "obe_count_workspace_bytes", "obe_count_table", "obe_count_tails", "obe_count_quantiles",
-                      "obe_count_logpmf")
+                      "obe_count_logpmf",
+                      "obe_signal_noise_logpdf", "obe_signal_noise_tails", "obe_signal_noise_reading_quantiles")
 
 
 class HipLib:

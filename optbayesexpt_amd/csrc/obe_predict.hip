@@ -27,44 +27,20 @@
 
 #include "obe_models.h"
 #include "obe_records_pass.h"
+#include "obe_score_pass.h"
 #include "obe_select.h"
 
 namespace obe {
 namespace {
 
-constexpr int kPredHeader = 8;                     // words: [0] sum w, [1] k (scale_kernel)
-constexpr int kPredHeadWords = kPredHeader + kPostPartials + kMaxQ;
-constexpr int kMomentWaves = 8192;                 // waves a moments pass aims at (32 per CU): chunks = this / setting tiles
-constexpr int kMomentMinChunk = 256;               // particles per chunk at least
+// (the header, the moment chunks and the carved workspace: obe_score_pass.h)
 constexpr int kTileRows = 64;                      // (setting, channel) rows whose values are kept at a time: 64 x N_p doubles
 
-inline int64_t setting_tiles(int64_t n_settings) { return (n_settings + kWave - 1) / kWave; }
-inline int moment_chunks(int64_t n_particles, int64_t n_settings) {
-    const int64_t by_size = (n_particles + kMomentMinChunk - 1) / kMomentMinChunk;
-    const int64_t by_grid = std::max<int64_t>(1, kMomentWaves / setting_tiles(n_settings));
-    return (int)std::max<int64_t>(1, std::min(by_size, by_grid));
-}
-// chunks x padded settings <= kMomentWaves x 64 + the padded settings, whatever the cloud
-inline int64_t moment_words(int64_t n_settings, int n_channels) {
-    return ((int64_t)kMomentWaves + setting_tiles(n_settings)) * kWave * n_channels;
-}
 inline int64_t tile_rows_bound(int64_t n_settings, int n_channels) { return std::min<int64_t>(n_settings * n_channels, kTileRows); }
 // the tile's values, its digit histograms, prefixes, targets and results, its row list
 inline int64_t select_words(int64_t n_particles, int64_t n_settings, int n_channels, int n_q) {
     const int64_t rows = tile_rows_bound(n_settings, n_channels);
     return rows * n_particles + rows * n_q * (int64_t)(kDigits + 3) + (rows + 1) / 2;
-}
-
-struct PredWs {
-    u64* hdr;
-    double* partials;
-    double* q;
-    u64* body;
-};
-inline PredWs carve(void* d_ws) {
-    u64* base = static_cast<u64*>(d_ws);
-    return PredWs{base, reinterpret_cast<double*>(base + kPredHeader),
-                  reinterpret_cast<double*>(base + kPredHeader + kPostPartials), base + kPredHeadWords};
 }
 
 // ---- moments.  One wave per workgroup; lane = one setting, the chunk's particles one after the other.
@@ -154,46 +130,13 @@ __global__ __launch_bounds__(kBlock) void predict_deliver_kernel(const double* _
     out[((int64_t)j * n_channels + c) * n_s + s0 + s] = found[(s * n_channels + c) * n_q + j];
 }
 
-int check_inputs(const char* who, const obe_model* m, const void* d_settings, int64_t ld_s, int64_t n_settings,
-                 const void* d_particles, int64_t ld_p, int64_t n_particles, const void* d_weights, const void* d_ws) {
-    static thread_local std::string msg;
-    const char* what = nullptr;
-    if (!m || !d_settings || !d_particles || !d_weights || !d_ws) what = "null pointer";
-    else if (n_settings < 1 || ld_s < n_settings) what = "n_settings < 1 or a row of settings shorter than that";
-    else if (n_particles < 1 || ld_p < n_particles) what = "bad cloud size";
-    if (!what) return 0;
-    msg = std::string(who) + ": " + what;
-    return bad_arg(msg.c_str());
-}
-
-int enqueue_scale(const double* d_weights, int64_t n, const PredWs& ws, hipStream_t st) {
-    const int nb = std::min(stream_blocks(n, kBlock * 8), kPostPartials);
-    wsum_partial_kernel<<<nb, kBlock, 0, st>>>(d_weights, n, ws.partials);
-    OBE_CHECK_LAUNCH("wsum_partial_kernel");
-    scale_kernel<<<1, kBlock, 0, st>>>(ws.partials, nb, ws.hdr);
-    OBE_CHECK_LAUNCH("scale_kernel");
-    return 0;
-}
-
 // ---- K11: scoring.  Lane = one record (a setting point, the reading y_meas[c], a known sigma[c]); the chunk's particles
 // one after the other, particle, weight and noise rows the same for all lanes.  z_c = (y_c - y_meas_c) / sigma_c with y
-// the model value.  A particle enters only with a weight > 0 and, ROWS, every noise row > 0 (NaN fails both).
-constexpr double kInf = __builtin_huge_val();
-constexpr double kHalfLog2Pi = 0.91893853320467274178;      // log(2 pi) / 2
-constexpr double kSqrtHalf = 0.70710678118654752440;
-
+// the model value.  A particle enters only with a weight > 0 and, ROWS, every noise row > 0 (NaN fails both).  The folds
+// (score_logpdf_fold_kernel, score_tails_fold_kernel) and lse_add: obe_score_pass.h.
 struct ScoreRows {
     int row[OBE_MAX_CHANNELS];
 };
-
-// (m, S) <- (m, S) + s exp(l): S exp(m) is the sum so far, m the largest exponent seen.  One exp; l finite, m finite or
-// -inf (never +inf), so no inf - inf is formed.
-__device__ __forceinline__ void lse_add(double& m, double& S, double l, double s) {
-    const bool up = l > m;
-    const double e = exp(up ? m - l : l - m);
-    S = up ? S * e + s : S + s * e;
-    m = up ? l : m;
-}
 
 // the record's reading and, known sigma, 1 / sigma and -sum log sigma; false: a sigma of the record is not > 0
 template <class M, bool ROWS>
@@ -267,23 +210,6 @@ __global__ __launch_bounds__(kWave) void score_logpdf_kernel(obe_model m, const 
     partials[((int64_t)blockIdx.y * 2 + 1) * n_pad + s] = S;
 }
 
-// d_logpdf (n_records,) = m + log S - log sum w - (C / 2) log 2 pi, the chunks' (m_j, S_j) merged in chunk order
-__global__ __launch_bounds__(kBlock) void score_logpdf_fold_kernel(const double* __restrict__ partials, int chunks,
-                                                                   int n_channels, int64_t n_pad, int64_t n_r,
-                                                                   const u64* __restrict__ hdr, double* __restrict__ out) {
-    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (s >= n_r) return;
-    const double sw = __longlong_as_double((long long)hdr[0]);
-    double top = -kInf, S = 0.0;
-    for (int j = 0; j < chunks; ++j) {
-        const double mj = partials[((int64_t)j * 2 + 0) * n_pad + s];
-        if (mj > -kInf) lse_add(top, S, mj, partials[((int64_t)j * 2 + 1) * n_pad + s]);
-    }
-    double r = __builtin_nan("");
-    if (sw > 0.0) r = top > -kInf ? top + log(S) - log(sw) - n_channels * kHalfLog2Pi : -kInf;
-    out[s] = r;
-}
-
 // partials (chunk, 2 C, padded records): sum w P(Y_c <= y_meas_c | particle), then sum w P(Y_c >= y_meas_c | particle).
 // The small one of the two is erfc(|z| / sqrt 2) / 2 itself, the large one 1 - that (>= 1/2: correctly rounded).
 template <class M, bool ROWS>
@@ -327,22 +253,6 @@ __global__ __launch_bounds__(kWave) void score_tails_kernel(obe_model m, const d
     }
 }
 
-// d_lower, d_upper (C, n_records) = (the chunk partials, added in chunk order) / sum w
-__global__ __launch_bounds__(kBlock) void score_tails_fold_kernel(const double* __restrict__ partials, int chunks,
-                                                                  int n_channels, int64_t n_pad, int64_t n_r,
-                                                                  const u64* __restrict__ hdr, double* __restrict__ lower,
-                                                                  double* __restrict__ upper) {
-    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (s >= n_r) return;
-    const double sw = __longlong_as_double((long long)hdr[0]);
-    for (int k = 0; k < 2 * n_channels; ++k) {
-        double acc = 0.0;
-        for (int j = 0; j < chunks; ++j) acc += partials[((int64_t)j * 2 * n_channels + k) * n_pad + s];
-        double* out = k < n_channels ? lower : upper;
-        out[(int64_t)(k % n_channels) * n_r + s] = acc / sw;
-    }
-}
-
 // ---- K15: quantiles of the next reading, the inverse of the tails above.  For a setting, a channel c and a level q the
 // y with L_c(y) = q T_c (q <= 1/2) or U_c(y) = (1 - q) T_c (q > 1/2): L, U the tails as score_tails_kernel forms them,
 // T_c = sum w over the particles that contribute to the channel — weight > 0, ROWS: every noise row > 0, f_c finite (a
@@ -357,53 +267,8 @@ __global__ __launch_bounds__(kBlock) void score_tails_fold_kernel(const double* 
 //             bracket (midpoint when the Newton point leaves the open bracket, is not finite, or the step exceeds half
 //             the previous one); keeps the number of open rows per (group, setting tile), which the next pass's
 //             workgroups read before anything else.
-// No atomics: the same bits from run to run.
-constexpr int kReadWaves = 4096;                   // waves a pass aims at per level group
-constexpr int kReadSlots = 8;                      // (trial, A, D) triples a lane holds
-constexpr double kInvSqrt2Pi = 0.39894228040143267794;
-constexpr double kReadClose = 0x1p-36;             // a row closes at |A - target| <= this x target ...
-constexpr double kReadUlps = 4.0;                  // ... or when its bracket is no wider than this many ulp of its larger end
-constexpr double kReadHair = 1e-9;                 // z -+ kReadHair (1 + |z|): an inexact inverse normal CDF keeps the root
-
-inline int read_group_of(int n_channels) { return n_channels < kReadSlots ? kReadSlots / n_channels : 1; }
-inline int read_chunks(int64_t n_particles, int64_t n_settings) {
-    const int64_t by_size = (n_particles + kMomentMinChunk - 1) / kMomentMinChunk;
-    const int64_t by_grid = std::max<int64_t>(1, kReadWaves / setting_tiles(n_settings));
-    return (int)std::max<int64_t>(1, std::min(by_size, by_grid));
-}
-
-// the levels of a call, by value in the kernel arguments
-struct ReadLevels {
-    int n;
-    int upper[kMaxQ];                              // the level solves in U (q > 1/2)
-    double frac[kMaxQ];                            // target / T: q or 1 - q
-    double z_lo[kMaxQ], z_hi[kMaxQ];
-};
-
-// row = level * C + channel; every array (rows, padded settings) but tile_open (groups, setting tiles)
-struct ReadState {
-    double *lo, *hi, *trial, *step, *target;
-    int32_t* open;
-    int32_t* tile_open;
-    double* partials;
-};
-// the state, then the chunk partials of the wider pass (the bracket's C (1 + 2 n_q) slots): chunks x padded settings <=
-// (kReadWaves + setting tiles) x 64, whatever the cloud
-inline int64_t read_words(int64_t n_settings, int n_channels, int n_q) {
-    const int64_t tiles = setting_tiles(n_settings), cells = (int64_t)n_q * n_channels * tiles * kWave;
-    return 5 * cells + (cells + 1) / 2 + (n_q * tiles + 1) / 2
-           + ((int64_t)kReadWaves + tiles) * kWave * n_channels * (1 + 2 * n_q);
-}
-inline ReadState read_carve(u64* body, int64_t n_settings, int n_channels, int n_q) {
-    const int64_t tiles = setting_tiles(n_settings), cells = (int64_t)n_q * n_channels * tiles * kWave;
-    double* d = reinterpret_cast<double*>(body);
-    ReadState st;
-    st.lo = d, st.hi = d + cells, st.trial = d + 2 * cells, st.step = d + 3 * cells, st.target = d + 4 * cells;
-    st.open = reinterpret_cast<int32_t*>(d + 5 * cells);
-    st.tile_open = reinterpret_cast<int32_t*>(d + 5 * cells + (cells + 1) / 2);
-    st.partials = d + 5 * cells + (cells + 1) / 2 + (n_q * tiles + 1) / 2;
-    return st;
-}
+// No atomics: the same bits from run to run.  The levels, the rows' state, the init and the step kernel and the chunk
+// plan see no sigma: obe_score_pass.h.
 
 // the sigma of the lane's setting (known sigma); false: one of them is not finite and > 0
 template <class M>
@@ -416,17 +281,6 @@ __device__ __forceinline__ bool load_sigma(int64_t sc, const double* __restrict_
         inv[c] = 1.0 / sg[c];
     }
     return ok;
-}
-
-// the open rows of this workgroup's block: what the threads of one (64, rows of a group) workgroup found, counted wave
-// by wave in thread order
-__device__ __forceinline__ int count_open_rows(bool open, int* cnt) {
-    const int n = __popcll(__ballot(open));
-    if (threadIdx.x == 0) cnt[threadIdx.y] = n;
-    __syncthreads();
-    int total = 0;
-    for (int k = 0; k < (int)blockDim.y; ++k) total += cnt[k];
-    return total;
 }
 
 // partials (chunk, C (1 + 2 n_q), padded settings): T_c, then per (level, channel) the min of f + z_lo sigma and the max
@@ -500,44 +354,6 @@ __global__ __launch_bounds__(kWave) void reading_bracket_kernel(obe_model m, con
     }
 }
 
-// The state of every row from the bracket's partials, folded in chunk order; workgroup (64 settings, the rows of a level
-// group), grid (setting tiles, groups).  T_c == 0: NaN, 0 passes, never open.
-__global__ void reading_init_kernel(int chunks, int n_channels, int group, ReadLevels lv, int64_t n_pad, int64_t n_s,
-                                    ReadState st, double* __restrict__ out, int32_t* __restrict__ passes) {
-    __shared__ int cnt[kReadSlots];
-    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
-    const int j = blockIdx.y * group + threadIdx.y / n_channels, c = threadIdx.y % n_channels;
-    bool open = false;
-    if (j < lv.n) {
-        const int64_t slots = (int64_t)n_channels * (1 + 2 * lv.n), at = n_channels + (j * n_channels + c) * 2;
-        double T = 0.0, mn = kInf, mx = -kInf;
-        for (int k = 0; k < chunks; ++k) {
-            const double* part = st.partials + k * slots * n_pad + s;
-            T += part[c * n_pad];
-            mn = fmin(mn, part[at * n_pad]);
-            mx = fmax(mx, part[(at + 1) * n_pad]);
-        }
-        const int64_t row = (int64_t)j * n_channels + c, idx = row * n_pad + s;
-        if (s < n_s) {
-            if (T > 0.0) {
-                const double lo = nextafter(mn, -kInf), hi = nextafter(mx, kInf);      // (the sums f + z sigma are rounded)
-                st.lo[idx] = lo;
-                st.hi[idx] = hi;
-                st.trial[idx] = 0.5 * lo + 0.5 * hi;
-                st.step[idx] = hi - lo;
-                st.target[idx] = lv.frac[j] * T;
-                open = true;
-            } else {
-                out[row * n_s + s] = __builtin_nan("");
-                passes[row * n_s + s] = 0;
-            }
-        }
-        st.open[idx] = open;
-    }
-    const int total = count_open_rows(open, cnt);
-    if (threadIdx.x == 0 && threadIdx.y == 0) st.tile_open[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
-}
-
 // partials (chunk, n_q C, 2, padded settings): A and sqrt(2 pi) D of the open rows at their trials.  The model is
 // evaluated once per (setting, particle) and shared by the group's levels.  A workgroup whose tile has no open row in
 // its group returns at once: the count was written by the launch before.
@@ -606,70 +422,11 @@ __global__ __launch_bounds__(kWave) void reading_pass_kernel(obe_model m, const 
     }
 }
 
-// Between two passes: the open rows' A and D folded in chunk order, then the bracket shrunk by the sign of A - target
-// and the trial moved.  d_quantiles, d_passes (n_q, C, n_settings) are written when a row closes (passes = this pass)
-// and, pass == max_passes, for a row still open (its bracket's midpoint, -max_passes).  The workgroup of the init kernel.
-__global__ void reading_step_kernel(int chunks, int n_channels, int group, ReadLevels lv, int64_t n_pad, int64_t n_s,
-                                    ReadState st, int pass, int max_passes, double* __restrict__ out,
-                                    int32_t* __restrict__ passes) {
-    __shared__ int cnt[kReadSlots];
-    int32_t* word = st.tile_open + (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (*word == 0) return;                                      // (the whole workgroup: nothing of this tile is open)
-    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
-    const int j = blockIdx.y * group + threadIdx.y / n_channels, c = threadIdx.y % n_channels;
-    const int64_t row = (int64_t)j * n_channels + c, idx = row * n_pad + s;
-    bool open = j < lv.n && st.open[idx] != 0;
-    if (open) {
-        double A = 0.0, D = 0.0;
-        for (int k = 0; k < chunks; ++k) {
-            const double* part = st.partials + ((int64_t)k * (2 * n_channels * lv.n) + row * 2) * n_pad + s;
-            A += part[0];
-            D += part[n_pad];
-        }
-        D *= kInvSqrt2Pi;
-        const bool up = lv.upper[j] != 0;
-        const double y = st.trial[idx], target = st.target[idx];
-        double lo = st.lo[idx], hi = st.hi[idx], result = y;
-        bool done = fabs(A - target) <= kReadClose * target;
-        if (!done) {
-            if ((A > target) != up) hi = y;                      // L rises with y, U falls
-            else lo = y;
-            const double big = fmax(fabs(lo), fabs(hi)), mid = 0.5 * lo + 0.5 * hi;
-            result = mid;
-            done = hi - lo <= kReadUlps * (nextafter(big, kInf) - big);
-            if (!done) {
-                const double dy = (A / D) * log(A / target);     // Newton on log A: towards the root with the sign below
-                double move = up ? dy : -dy;
-                // a step below the resolution of y would leave the trial on the bracket's end it has just become, and
-                // the far end where it is: two ulp in Newton's direction instead, so that the far end comes in
-                const double ulp2 = 2.0 * (nextafter(fabs(y), kInf) - fabs(y));
-                if (fabs(move) < ulp2) move = copysign(ulp2, move);
-                double next = y + move;
-                if (!(next > lo && next < hi) || !(fabs(dy) <= 0.5 * st.step[idx])) next = mid;
-                st.lo[idx] = lo;
-                st.hi[idx] = hi;
-                st.step[idx] = fabs(next - y);
-                st.trial[idx] = next;
-            }
-        }
-        if (done || pass == max_passes) {
-            out[row * n_s + s] = result;
-            passes[row * n_s + s] = done ? pass : -max_passes;
-            st.open[idx] = 0;
-            open = false;
-        }
-    }
-    const int total = count_open_rows(open, cnt);
-    if (threadIdx.x == 0 && threadIdx.y == 0) *word = total;
-}
-
-// What the scoring entry points and K15 share: everything that can refuse the call, then the launch geometry.
-struct Score {
+// What the scoring entry points and K15 share: everything that can refuse the call, then the launch geometry
+// (ScorePlan, obe_score_pass.h).
+struct Score : ScorePlan {
     obe_model mm;
     ScoreRows rows;
-    PredWs ws;
-    int64_t tiles, chunk_len;
-    int used;
     int prepare(const char* who, const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
                 const double* d_y_meas, int64_t ld_y, const double* d_sigma, int64_t ld_sigma,
                 const int32_t* h_noise_rows, const double* d_particles, int64_t ld_p, int64_t n_particles,
@@ -691,15 +448,7 @@ struct Score {
             rows.row[c] = (h_noise_rows && c < mm.n_channels) ? h_noise_rows[c] : 0;
             if (rows.row[c] && (rows.row[c] < 0 || rows.row[c] >= mm.n_params)) return refuse("noise row index out of range");
         }
-        const int64_t need = n_q ? obe_predictive_reading_workspace_bytes(n_particles, n_records, mm.n_channels, n_q)
-                                 : obe_predictive_score_workspace_bytes(n_particles, n_records, mm.n_channels);
-        if (ws_bytes < need) return refuse("workspace too small");
-        tiles = setting_tiles(n_records);
-        if (tiles > 0x7fffffff) return refuse("too many records for one call");
-        const int chunks = n_q ? read_chunks(n_particles, n_records) : moment_chunks(n_particles, n_records);
-        chunk_len = ((n_particles + chunks - 1) / chunks + kWave - 1) / kWave * kWave;      // whole waves of particles
-        used = (int)((n_particles + chunk_len - 1) / chunk_len);
-        ws = carve(d_ws);
+        if (const char* what = plan(n_particles, n_records, mm.n_channels, n_q, d_ws, ws_bytes)) return refuse(what);
         return 0;
     }
 };
@@ -1005,9 +754,7 @@ extern "C" {
 
 int64_t obe_predictive_score_workspace_bytes(int64_t n_particles, int64_t n_records, int32_t n_channels) {
     (void)n_particles;                                           // (the partials are per chunk: bounded whatever the cloud)
-    if (n_records < 1) n_records = 1;
-    if (n_channels < 1) n_channels = 1;
-    return (kPredHeadWords + moment_words(n_records, 2 * n_channels)) * (int64_t)sizeof(u64);
+    return score_ws_bytes(n_records, n_channels);
 }
 
 int obe_predictive_logpdf(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
@@ -1075,10 +822,7 @@ int obe_predictive_tails(const obe_model* m, const double* d_settings, int64_t l
 
 int64_t obe_predictive_reading_workspace_bytes(int64_t n_particles, int64_t n_settings, int32_t n_channels, int32_t n_q) {
     (void)n_particles;                                           // (the partials are per chunk: bounded whatever the cloud)
-    if (n_settings < 1) n_settings = 1;
-    n_channels = std::min(std::max(n_channels, 1), OBE_MAX_CHANNELS);
-    n_q = std::min(std::max(n_q, 1), kMaxQ);
-    return (kPredHeadWords + read_words(n_settings, n_channels, n_q)) * (int64_t)sizeof(u64);
+    return reading_ws_bytes(n_settings, n_channels, n_q);
 }
 
 int obe_predictive_reading_quantiles(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
@@ -1088,19 +832,8 @@ int obe_predictive_reading_quantiles(const obe_model* m, const double* d_setting
                                      double* d_quantiles, int32_t* d_passes, void* d_ws, int64_t ws_bytes, void* stream) {
     const char* who = "obe_predictive_reading_quantiles";
     if (!h_q || !h_z || !d_quantiles || !d_passes) return bad_arg("obe_predictive_reading_quantiles: null pointer");
-    if (n_q < 1 || n_q > kMaxQ) return bad_arg("obe_predictive_reading_quantiles: 1..16 levels per call");
-    if (max_passes < 1 || max_passes > 64) return bad_arg("obe_predictive_reading_quantiles: max_passes outside 1..64");
-    ReadLevels lv{};
-    lv.n = n_q;
-    for (int j = 0; j < n_q; ++j) {
-        const double q = h_q[j], z = h_z[j];
-        if (!(q > 0.0 && q < 1.0)) return bad_arg("obe_predictive_reading_quantiles: q outside (0, 1)");
-        if (!(std::fabs(z) < kInf)) return bad_arg("obe_predictive_reading_quantiles: h_z is not finite");
-        lv.upper[j] = q > 0.5;
-        lv.frac[j] = q > 0.5 ? 1.0 - q : q;                      // (1 - q is exact there)
-        lv.z_lo[j] = z - kReadHair * (1.0 + std::fabs(z));
-        lv.z_hi[j] = z + kReadHair * (1.0 + std::fabs(z));
-    }
+    ReadLevels lv;
+    if (int rc = fill_read_levels(who, lv, h_q, h_z, n_q, max_passes)) return rc;
     Score sc;
     if (int rc = sc.prepare(who, m, d_settings, ld_s, n_settings, nullptr, 0, d_sigma, ld_sigma, h_noise_rows, d_particles,
                             ld_p, n_particles, d_weights, d_ws, ws_bytes, n_q))

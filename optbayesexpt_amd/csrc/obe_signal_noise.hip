@@ -14,14 +14,24 @@
 //   records     K19: l_i = sum_r sum_c [-(f - y)^2 / (2 nu) - log(nu) / 2] + constant over a set of records, per particle:
 //               the records x particles pass of obe_records_pass.h with NoiseRecordTerm below.  Per evaluation and
 //               channel one division and one log.  FP64-issue bound.
+//   scoring     K21: the predictive of a READING, a mixture of N_p Gaussians whose component i has the mean f_c(x; theta_i)
+//               and the variance nu_c(f_c(x; theta_i)): its log-density and tails for recorded readings (K11's geometry,
+//               lane <-> record) and its quantiles for the next one (K15's, lane <-> setting, level groups).  Four
+//               kernels — logpdf, tails, bracket, pass — further down; the folds, K15's state, its init and step
+//               kernels and the chunk plans see no sigma and come from obe_score_pass.h.  A particle contributes by the
+//               likelihood's rule: a weight > 0 and EVERY channel's nu > 0 and finite, so a NaN or +-inf model value in
+//               any channel removes it from all channels — a stated difference from K11's tails, where +-inf counts as
+//               mass at infinity.  The normalisers are K11's and K15's: the density and the tails divide by the sum of
+//               ALL positive weights (a left-out particle has likelihood 0: the density stays the one-step evidence),
+//               the quantiles by T over the contributing particles.  FP64-issue bound.
 #include "obe_cloud_pass.h"
 #include "obe_records_pass.h"
+#include "obe_score_pass.h"
 
 namespace obe {
 namespace {
 
 constexpr int kNuWaves = 8192;                     // waves the pass aims at (32 per CU): chunks = this / setting tiles
-constexpr double kInf = __builtin_huge_val();
 
 constexpr int nu_slots(int n_channels) { return 2 * n_channels + 1; }      // per channel sum w |y|, sum w y^2; then W
 
@@ -148,6 +158,254 @@ int fill_noise_coef(const char* who, NoiseCoef& k, const double* h_noise_coef, i
     return bad_arg(msg.c_str());
 }
 
+// ---- K21: scoring a reading and quantiles of the next one with nu at every particle's own model value.  The kernels of
+// K11 / K15 (obe_predict.hip) with the width taken from the model value just computed instead of from a row of the cloud;
+// their partials have K11's / K15's layout, so obe_score_pass.h's folds, init and step kernels read them.
+
+// nu of every channel at a particle's model values y; false: one of them is not > 0 or not finite (NaN fails) — the
+// likelihood's rule, one verdict for all channels
+template <class M>
+__device__ __forceinline__ bool noise_of(const NoiseCoef& k, const double* y, double* nu) {
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        nu[c] = nu_of(k, c, y[c]);
+        ok = ok && nu[c] > 0.0 && nu[c] < kInf;
+    }
+    return ok;
+}
+
+// partials (chunk, 2, padded records): the chunk's (m, S) of sum_i w_i exp(l_i), l_i = sum_c [-(f_c - y_c)^2 / (2 nu_c) -
+// log(nu_c) / 2] — NoiseRecordTerm's arithmetic.  Lane = one record.
+template <class M>
+__global__ __launch_bounds__(kWave) void signal_logpdf_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                              int64_t n_r, const double* __restrict__ y_meas, int64_t ld_y,
+                                                              NoiseCoef k, const double* __restrict__ particles,
+                                                              int64_t ld_p, int64_t n, const double* __restrict__ w,
+                                                              int64_t chunk_len, double* __restrict__ partials) {
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_r ? s : n_r - 1;                    // (the padding lanes repeat the last record)
+    double x[M::NS], ym[M::NC];
+#pragma unroll
+    for (int d = 0; d < M::NS; ++d) x[d] = settings[(int64_t)d * ld_s + sc];
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) ym[c] = y_meas[(int64_t)c * ld_y + sc];
+    double top = -kInf, S = 0.0;
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p] and the particle are the same for all lanes)
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        double y[M::NC], nu[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+        const bool ok = noise_of<M>(k, y, nu);
+        double l = 0.0;
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const double d = y[c] - ym[c];
+            l -= (d * d) / (2.0 * nu[c]);
+            l -= 0.5 * log(nu[c]);
+        }
+        if (ok && fabs(l) < kInf) lse_add(top, S, l, wp);          // (NaN and -inf contribute nothing)
+    }
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+    partials[((int64_t)blockIdx.y * 2 + 0) * n_pad + s] = top;
+    partials[((int64_t)blockIdx.y * 2 + 1) * n_pad + s] = S;
+}
+
+// partials (chunk, 2 C, padded records): sum w P(Y_c <= y_meas_c | particle), then sum w P(Y_c >= y_meas_c | particle),
+// z_c = (f_c - y_meas_c) / sqrt(nu_c).  The small one of the two is erfc(|z| / sqrt 2) / 2 itself, the large one 1 - that.
+template <class M>
+__global__ __launch_bounds__(kWave) void signal_tails_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                             int64_t n_r, const double* __restrict__ y_meas, int64_t ld_y,
+                                                             NoiseCoef k, const double* __restrict__ particles,
+                                                             int64_t ld_p, int64_t n, const double* __restrict__ w,
+                                                             int64_t chunk_len, double* __restrict__ partials) {
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_r ? s : n_r - 1;
+    double x[M::NS], ym[M::NC], lo[M::NC], hi[M::NC];
+#pragma unroll
+    for (int d = 0; d < M::NS; ++d) x[d] = settings[(int64_t)d * ld_s + sc];
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        ym[c] = y_meas[(int64_t)c * ld_y + sc];
+        lo[c] = hi[c] = 0.0;
+    }
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        double y[M::NC], nu[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+        if (!noise_of<M>(k, y, nu)) continue;                    // (this lane's: the others go on)
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const double z = (y[c] - ym[c]) * (1.0 / sqrt(nu[c]));      // > 0: the model lies above the reading
+            if (z == z) {
+                const double small = 0.5 * erfc(fabs(z) * kSqrtHalf), large = 1.0 - small;
+                lo[c] += wp * (z > 0.0 ? small : large);
+                hi[c] += wp * (z > 0.0 ? large : small);
+            }
+        }
+    }
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        partials[((int64_t)blockIdx.y * 2 * M::NC + c) * n_pad + s] = lo[c];
+        partials[((int64_t)blockIdx.y * 2 * M::NC + M::NC + c) * n_pad + s] = hi[c];
+    }
+}
+
+// partials (chunk, C (1 + 2 n_q), padded settings): T_c, then per (level, channel) the min of f + z_lo sqrt(nu) and the
+// max of f + z_hi sqrt(nu) over the contributing particles: the bracket argument holds for a width per particle.  T_c is
+// the same for every channel (one verdict per particle) and is written by the first level group.
+template <class M>
+__global__ __launch_bounds__(kWave) void signal_bracket_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                               int64_t n_s, NoiseCoef k,
+                                                               const double* __restrict__ particles, int64_t ld_p,
+                                                               int64_t n, const double* __restrict__ w, int64_t chunk_len,
+                                                               ReadLevels lv, double* __restrict__ partials) {
+    constexpr int G = M::NC < kReadSlots ? kReadSlots / M::NC : 1;
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_s ? s : n_s - 1;                    // (the padding lanes repeat the last setting)
+    const int j0 = blockIdx.z * G;
+    double x[M::NS], T = 0.0, mn[G][M::NC], mx[G][M::NC], zl[G], zh[G];
+#pragma unroll
+    for (int d = 0; d < M::NS; ++d) x[d] = settings[(int64_t)d * ld_s + sc];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const int j = j0 + g < lv.n ? j0 + g : lv.n - 1;         // (levels beyond the call's repeat the last: not written)
+        zl[g] = lv.z_lo[j];
+        zh[g] = lv.z_hi[j];
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) mn[g][c] = kInf, mx[g][c] = -kInf;
+    }
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p] and the particle are the same for all lanes)
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        double y[M::NC], nu[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+        if (!noise_of<M>(k, y, nu)) continue;                    // (a finite nu: every f is finite too)
+        T += wp;
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const double sg = sqrt(nu[c]);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                mn[g][c] = fmin(mn[g][c], y[c] + zl[g] * sg);
+                mx[g][c] = fmax(mx[g][c], y[c] + zh[g] * sg);
+            }
+        }
+    }
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+    double* out = partials + (int64_t)blockIdx.y * (M::NC * (1 + 2 * lv.n)) * n_pad + s;
+#pragma unroll
+    for (int c = 0; c < M::NC; ++c) {
+        if (blockIdx.z == 0) out[c * n_pad] = T;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (j0 + g < lv.n) {
+                out[(M::NC + ((j0 + g) * M::NC + c) * 2) * n_pad] = mn[g][c];
+                out[(M::NC + ((j0 + g) * M::NC + c) * 2 + 1) * n_pad] = mx[g][c];
+            }
+        }
+    }
+}
+
+// partials (chunk, n_q C, 2, padded settings): A and sqrt(2 pi) D = sum w exp(-z^2 / 2) / sqrt(nu) of the open rows at
+// their trials.  The model, sqrt(nu) and its reciprocal are formed once per (setting, particle, channel) and shared by the
+// group's levels.  A workgroup whose tile has no open row in its group returns at once: the count was written by the
+// launch before.
+template <class M>
+__global__ __launch_bounds__(kWave) void signal_pass_kernel(obe_model m, const double* __restrict__ settings, int64_t ld_s,
+                                                            int64_t n_s, NoiseCoef k, const double* __restrict__ particles,
+                                                            int64_t ld_p, int64_t n, const double* __restrict__ w,
+                                                            int64_t chunk_len, ReadLevels lv, ReadState st) {
+    constexpr int G = M::NC < kReadSlots ? kReadSlots / M::NC : 1;
+    if (st.tile_open[(int64_t)blockIdx.z * gridDim.x + blockIdx.x] == 0) return;
+    const int64_t s = (int64_t)blockIdx.x * kWave + threadIdx.x;
+    const int64_t sc = s < n_s ? s : n_s - 1;                    // (the padding lanes repeat the last setting: never open)
+    const int64_t n_pad = (int64_t)gridDim.x * kWave;
+    const int j0 = blockIdx.z * G;
+    double x[M::NS], yt[G][M::NC], A[G][M::NC], D[G][M::NC];
+    bool open[G][M::NC], up[G];
+#pragma unroll
+    for (int d = 0; d < M::NS; ++d) x[d] = settings[(int64_t)d * ld_s + sc];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const bool live = j0 + g < lv.n;
+        up[g] = live && lv.upper[live ? j0 + g : 0] != 0;
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const int64_t idx = ((int64_t)(live ? j0 + g : 0) * M::NC + c) * n_pad + s;
+            open[g][c] = live && st.open[idx] != 0;
+            yt[g][c] = open[g][c] ? st.trial[idx] : 0.0;
+            A[g][c] = D[g][c] = 0.0;
+        }
+    }
+    const int64_t p0 = (int64_t)blockIdx.y * chunk_len;
+    const int64_t p1 = p0 + chunk_len < n ? p0 + chunk_len : n;
+    for (int64_t p = p0; p < p1; ++p) {                          // (p, w[p] and the particle are the same for all lanes)
+        const double wp = clean_weight(w[p]);
+        if (wp == 0.0) continue;
+        double y[M::NC], nu[M::NC];
+        M::eval(x, ParamRef{particles + p, ld_p}, m, y);
+        if (!noise_of<M>(k, y, nu)) continue;
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            const double inv = 1.0 / sqrt(nu[c]);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (open[g][c]) {
+                    const double z = (y[c] - yt[g][c]) * inv;             // > 0: the model lies above the trial
+                    const double small = 0.5 * erfc(fabs(z) * kSqrtHalf), large = 1.0 - small;
+                    A[g][c] += wp * ((z > 0.0) == up[g] ? large : small);
+                    D[g][c] += wp * (exp(-0.5 * (z * z)) * inv);
+                }
+            }
+        }
+    }
+    double* out = st.partials + (int64_t)blockIdx.y * (2 * M::NC * lv.n) * n_pad + s;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int c = 0; c < M::NC; ++c) {
+            if (open[g][c]) {
+                out[(((j0 + g) * M::NC + c) * 2) * n_pad] = A[g][c];
+                out[(((j0 + g) * M::NC + c) * 2 + 1) * n_pad] = D[g][c];
+            }
+        }
+    }
+}
+
+// What the three entry points of K21 share: everything that can refuse the call — the coefficients among it, before any
+// launch —, then the launch geometry (ScorePlan, obe_score_pass.h).
+struct NoiseScore : ScorePlan {
+    obe_model mm;
+    NoiseCoef k;
+    int prepare(const char* who, const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                const double* d_y_meas, int64_t ld_y, const double* h_noise_coef, const double* d_particles, int64_t ld_p,
+                int64_t n_particles, const double* d_weights, void* d_ws, int64_t ws_bytes, int n_q = 0) {      // n_q > 0: no y_meas
+        static thread_local std::string msg;
+        auto refuse = [&](const char* what) {
+            msg = std::string(who) + ": " + what;
+            return bad_arg(msg.c_str());
+        };
+        if (!d_y_meas && !n_q) return refuse("null pointer");
+        if (int rc = check_inputs(who, m, d_settings, ld_s, n_records, d_particles, ld_p, n_particles, d_weights, d_ws))
+            return rc;
+        if (!n_q && ld_y < n_records) return refuse("a row of y_meas shorter than n_records");
+        mm = *m;
+        if (int rc = obe_model_validate(&mm)) return rc;
+        if (int rc = fill_noise_coef(who, k, h_noise_coef, mm.n_channels)) return rc;
+        if (const char* what = plan(n_particles, n_records, mm.n_channels, n_q, d_ws, ws_bytes)) return refuse(what);
+        return 0;
+    }
+};
+
 }  // namespace
 }  // namespace obe
 
@@ -236,6 +494,95 @@ int obe_signal_noise_records_loglik(const obe_model* m, const double* d_settings
     return own_records_loglik<NoiseRecordTerm>("obe_signal_noise_records_loglik", m, d_settings, ld_s, n_records,
                                                d_y_meas, ld_y, nullptr, 0, k, constant, d_particles, ld_p, n_particles,
                                                accumulate, d_loglik, d_ws, ws_bytes, stream);
+}
+
+int obe_signal_noise_logpdf(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                            const double* d_y_meas, int64_t ld_y, const double* h_noise_coef, const double* d_particles,
+                            int64_t ld_p, int64_t n_particles, const double* d_weights, double* d_logpdf, void* d_ws,
+                            int64_t ws_bytes, void* stream) {
+    if (!d_logpdf) return bad_arg("obe_signal_noise_logpdf: null pointer");
+    NoiseScore sc;
+    if (int rc = sc.prepare("obe_signal_noise_logpdf", m, d_settings, ld_s, n_records, d_y_meas, ld_y, h_noise_coef,
+                            d_particles, ld_p, n_particles, d_weights, d_ws, ws_bytes))
+        return rc;
+    hipStream_t st = as_stream(stream);
+    double* partials = reinterpret_cast<double*>(sc.ws.body);
+    if (int rc = enqueue_scale(d_weights, n_particles, sc.ws, st)) return rc;
+    return dispatch_model(sc.mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        signal_logpdf_kernel<Model><<<dim3((unsigned)sc.tiles, (unsigned)sc.used), kWave, 0, st>>>(
+            sc.mm, d_settings, ld_s, n_records, d_y_meas, ld_y, sc.k, d_particles, ld_p, n_particles, d_weights,
+            sc.chunk_len, partials);
+        OBE_CHECK_LAUNCH("signal_logpdf_kernel");
+        score_logpdf_fold_kernel<<<(int)((n_records + kBlock - 1) / kBlock), kBlock, 0, st>>>(
+            partials, sc.used, Model::NC, sc.tiles * kWave, n_records, sc.ws.hdr, d_logpdf);
+        OBE_CHECK_LAUNCH("score_logpdf_fold_kernel");
+        return 0;
+    });
+}
+
+int obe_signal_noise_tails(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_records,
+                           const double* d_y_meas, int64_t ld_y, const double* h_noise_coef, const double* d_particles,
+                           int64_t ld_p, int64_t n_particles, const double* d_weights, double* d_lower, double* d_upper,
+                           void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_lower || !d_upper) return bad_arg("obe_signal_noise_tails: null pointer");
+    NoiseScore sc;
+    if (int rc = sc.prepare("obe_signal_noise_tails", m, d_settings, ld_s, n_records, d_y_meas, ld_y, h_noise_coef,
+                            d_particles, ld_p, n_particles, d_weights, d_ws, ws_bytes))
+        return rc;
+    hipStream_t st = as_stream(stream);
+    double* partials = reinterpret_cast<double*>(sc.ws.body);
+    if (int rc = enqueue_scale(d_weights, n_particles, sc.ws, st)) return rc;
+    return dispatch_model(sc.mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        signal_tails_kernel<Model><<<dim3((unsigned)sc.tiles, (unsigned)sc.used), kWave, 0, st>>>(
+            sc.mm, d_settings, ld_s, n_records, d_y_meas, ld_y, sc.k, d_particles, ld_p, n_particles, d_weights,
+            sc.chunk_len, partials);
+        OBE_CHECK_LAUNCH("signal_tails_kernel");
+        score_tails_fold_kernel<<<(int)((n_records + kBlock - 1) / kBlock), kBlock, 0, st>>>(
+            partials, sc.used, Model::NC, sc.tiles * kWave, n_records, sc.ws.hdr, d_lower, d_upper);
+        OBE_CHECK_LAUNCH("score_tails_fold_kernel");
+        return 0;
+    });
+}
+
+int obe_signal_noise_reading_quantiles(const obe_model* m, const double* d_settings, int64_t ld_s, int64_t n_settings,
+                                       const double* h_noise_coef, const double* d_particles, int64_t ld_p,
+                                       int64_t n_particles, const double* d_weights, const double* h_q, const double* h_z,
+                                       int32_t n_q, int32_t max_passes, double* d_quantiles, int32_t* d_passes, void* d_ws,
+                                       int64_t ws_bytes, void* stream) {
+    const char* who = "obe_signal_noise_reading_quantiles";
+    if (!d_quantiles || !d_passes) return bad_arg("obe_signal_noise_reading_quantiles: null pointer");
+    ReadLevels lv;
+    if (int rc = fill_read_levels(who, lv, h_q, h_z, n_q, max_passes)) return rc;
+    NoiseScore sc;
+    if (int rc = sc.prepare(who, m, d_settings, ld_s, n_settings, nullptr, 0, h_noise_coef, d_particles, ld_p, n_particles,
+                            d_weights, d_ws, ws_bytes, n_q))
+        return rc;
+    hipStream_t st = as_stream(stream);
+    const ReadState state = read_carve(sc.ws.body, n_settings, sc.mm.n_channels, n_q);
+    return dispatch_model(sc.mm, [&](auto M) -> int {
+        using Model = decltype(M);
+        const int group = read_group_of(Model::NC), groups = (n_q + group - 1) / group;
+        const dim3 grid((unsigned)sc.tiles, (unsigned)sc.used, (unsigned)groups);
+        const dim3 fold_grid((unsigned)sc.tiles, (unsigned)groups), fold_block(kWave, (unsigned)(group * Model::NC));
+        const int64_t n_pad = sc.tiles * kWave;
+        signal_bracket_kernel<Model><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_settings, sc.k, d_particles, ld_p,
+                                                             n_particles, d_weights, sc.chunk_len, lv, state.partials);
+        OBE_CHECK_LAUNCH("signal_bracket_kernel");
+        reading_init_kernel<<<fold_grid, fold_block, 0, st>>>(sc.used, Model::NC, group, lv, n_pad, n_settings, state,
+                                                              d_quantiles, d_passes);
+        OBE_CHECK_LAUNCH("reading_init_kernel");
+        for (int pass = 1; pass <= max_passes; ++pass) {         // a fixed budget: nothing is waited for
+            signal_pass_kernel<Model><<<grid, kWave, 0, st>>>(sc.mm, d_settings, ld_s, n_settings, sc.k, d_particles, ld_p,
+                                                              n_particles, d_weights, sc.chunk_len, lv, state);
+            OBE_CHECK_LAUNCH("signal_pass_kernel");
+            reading_step_kernel<<<fold_grid, fold_block, 0, st>>>(sc.used, Model::NC, group, lv, n_pad, n_settings, state, pass,
+                                                                  max_passes, d_quantiles, d_passes);
+            OBE_CHECK_LAUNCH("reading_step_kernel");
+        }
+        return 0;
+    });
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@ import math
 import numpy as np
 import torch
 
-from . import _batch, _lib
+from . import _batch, _lib, _signal
 from ._ownnoise import OwnCloudPasses, check_own_records
 from ._devcall import P as _P, model_call, ptr as _ptr
 
@@ -71,12 +71,20 @@ class OptBayesExptSignalNoise(OwnCloudPasses):
     ``pdf_update((setting, y_meas[, sigma]))`` ignores a record's ``sigma``; ``yvar_noise_model()`` returns the
     ``(C, n_settings)`` average of ``nu`` over the cloud, ``nu_bar_c(s) = a_c + b_c sum w |y| / W + c_c sum w y^2 / W``,
     which every ``utility_method``, ``expected_variance_reduction()`` without ``sigma`` and ``opt_setting_batch()`` use.
-    ``likelihood()``: ``L_i = prod_c exp(-(y_c,i - y_meas,c)^2 / (2 nu_c(y_c,i))) / sqrt(nu_c(y_c,i))``.  The summaries
-    that take a per-record ``sigma`` do not know ``nu(y)`` yet and raise ``NotImplementedError``."""
+    ``likelihood()``: ``L_i = prod_c exp(-(y_c,i - y_meas,c)^2 / (2 nu_c(y_c,i))) / sqrt(nu_c(y_c,i))``.
+
+    Is a reading plausible, and where will the next one fall?  ``signal_logpdf()``, ``signal_cdf()``,
+    ``signal_pvalue()``, ``signal_quantile()`` and ``signal_interval()`` answer with the object's own noise: the
+    predictive of a reading is the mixture of N_p Gaussians whose component i has the mean ``f_c(x; theta_i)`` and the
+    variance ``nu_c(f_c(x; theta_i))``.  A particle contributes with a weight > 0 and a ``nu`` that is > 0 and finite in
+    EVERY channel (the likelihood's rule: a NaN or infinite model value in any channel leaves it out of all of them).
+    The summaries of the base class that take a per-record ``sigma`` (``predictive_logpdf()`` ...) raise
+    ``NotImplementedError`` and point at these."""
     _PASS_SUMS = "the noise is averaged"
-    _REFUSAL = ("takes a fixed sigma per record, but this object's noise depends on the signal: the predictive "
-                "summaries do not know nu(y) yet, and a fixed sigma would contradict the object's own likelihood "
-                "(records_loglik() and pdf_update_batch() take the records without sigma)")
+    _REFUSAL = ("takes a fixed sigma per record, but this object's noise depends on the signal, and a fixed sigma "
+                "would contradict the object's own likelihood: signal_logpdf(), signal_cdf(), signal_pvalue(), "
+                "signal_quantile() and signal_interval() score a reading and draw its band with nu at every "
+                "particle's own model value (records_loglik() and pdf_update_batch() take the records without sigma)")
 
     def __init__(self, measurement_model, setting_values, parameter_samples, constants,
                  noise_floor=0.0, noise_gain=1.0, noise_relative=0.0, **kwargs):
@@ -120,6 +128,38 @@ class OptBayesExptSignalNoise(OwnCloudPasses):
             return out
 
         return self._nu_bar_cached(begin, end, coef.tobytes(), compute)
+
+    # -- nu(y)-aware scoring and reading bands (_signal.py; csrc/obe_signal_noise.hip, K21) ---------------------------
+    # The coefficients are the attributes as they stand when the call starts.  A particle contributes with a weight > 0
+    # and a nu > 0 and finite in every channel; the density and the tails divide by the sum of ALL positive weights, the
+    # quantiles by the contributing ones.  Nothing is kept on the object.
+    def signal_logpdf(self, settings, y_meas):
+        """``(n_r,)`` float64, or a float for one record given as ``pdf_update`` takes it: the joint log density of each
+        reading under the predictive, ``log(sum_i w_i prod_c N(y_c; f_c,i, nu_c(f_c,i)) / sum_i w_i)`` — for the record
+        about to be used the one-step log evidence.  -inf where nobody contributes, NaN where sum w == 0."""
+        return _signal.signal_logpdf(self, settings, y_meas)
+
+    def signal_cdf(self, settings, y_meas, upper=False):
+        """``(C, n_r)``: per channel ``P(Y_c <= y_c)`` of the reading under the predictive; ``upper=True``:
+        ``P(Y_c >= y_c)``.  Both are sums of positive terms, so a far tail keeps its relative accuracy."""
+        return _signal.signal_cdf(self, settings, y_meas, upper)
+
+    def signal_pvalue(self, settings, y_meas):
+        """``(C, n_r)``: the two-sided p-value per channel, ``min(2 min(lower, upper), 1)`` of ``signal_cdf()``'s tails."""
+        return _signal.signal_pvalue(self, settings, y_meas)
+
+    def signal_quantile(self, q, settings=None, max_passes=48, full_output=False):
+        """``(n_q, C, n_x)`` (``(C, n_x)`` for a scalar ``q``): the y with ``P(Y_c <= y) = q`` for the next reading at
+        the whole design grid (None; on a sharded object too) or at ``settings`` (points, as ``predict()`` takes them);
+        levels in the open interval (0, 1).  NaN where nobody contributes.  ``max_passes`` (1..64): rows still open
+        then deliver their bracket's midpoint (one ``RuntimeWarning`` counts them); ``full_output`` adds
+        ``{"passes": ..., "unconverged": n}``."""
+        return _signal.signal_quantile(self, q, settings, max_passes, full_output)
+
+    def signal_interval(self, level=0.95, settings=None, max_passes=48, full_output=False):
+        """``(lo, hi)``: ``signal_quantile()`` at ``(1 -+ level) / 2`` per channel and setting — the band to draw
+        against measured points.  Per channel, not joint."""
+        return _signal.signal_interval(self, level, settings, max_passes, full_output)
 
 
 CLASS = OptBayesExptSignalNoise
